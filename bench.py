@@ -5,7 +5,14 @@ A step = one forward + backward pass of the Gaussian-splat rasterizer-with-depth
 view: 1.5 M synthetic Gaussians (SURVEY.md §8d recipe, seed 0), 1920x1080, sh_degree 3, upstream
 gradient dL/dcolor ~ N(0,1). Inputs are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up (W steps + min(K, 20) settling steps), times the K steps and prints the headline (value,
+ms_per_step). --full adds everything else this script measures: the per-stage table (K more steps, every stage bracketed by
+hipEvents, in place of the settling steps), the roofline of the dominant kernel (its launches bracketed inside the timed
+region), the CPU baselines, the training iteration and the SVD denoise step (--path, --no-cpu-baseline and --svd-steps choose
+among those). --dump-outputs DIR writes what the last timed step returned (dump_outputs) as float32 .npy files, the same
+inputs on every run with the same arguments.
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N ...`: one process per GPU, every rank renders a DIFFERENT view of the replicated scene
@@ -64,6 +71,47 @@ def view_camera(rank, W, H):
     cam_pos = centre - R @ np.array([0.0, 0.0, 4.5])       # orbit at the same distance
     T = -R.T @ cam_pos
     return syn.make_camera(W, H, 50.0, R, T)
+
+
+DUMP_BYTES = 64 * 10**6           # --dump-outputs: all files together stay under this
+
+
+def dump_outputs(out_dir, images, rows, P):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files in `out_dir`, DUMP_BYTES at most.
+    images: name -> [C, H, W] tensor, written whole (on a seeded pixel sample, pixel_index.npy, if they would take more than
+    60 % of the budget); rows: name -> per-Gaussian [P, ...] tensor, written on a seeded sample of Gaussians sized to the rest
+    of the budget (gaussian_index.npy, sorted). The samples depend on the arguments only, so two builds compare row for row."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES - (1 << 20)                      # room for the .npy headers
+    rng = np.random.default_rng(0)
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+    def sample(n, k):                                    # k of n indices (all of them if k >= n), sorted, as a device tensor
+        idx = np.arange(n) if k >= n else np.sort(rng.choice(n, k, replace=False))
+        return torch.from_numpy(idx).to(dev)
+
+    dev = next(iter(images.values())).device
+    ch = sum(int(t.shape[0]) for t in images.values())
+    HW = int(next(iter(images.values()))[0].numel())
+    if ch * HW * 4 <= budget * 3 // 5:
+        for n, t in images.items():
+            save(n, t)
+        budget -= ch * HW * 4
+    else:
+        k = (budget * 3 // 5) // (4 * ch + 8)
+        pix = sample(HW, k)
+        for n, t in images.items():
+            save(n, t.reshape(t.shape[0], HW).index_select(1, pix))
+        np.save(os.path.join(out_dir, "pixel_index.npy"), pix.cpu().numpy().astype(np.float64))
+        budget -= k * (4 * ch + 8)
+    width = sum(int(t[0].numel()) for t in rows.values())
+    k = min(P, budget // (4 * width + 8))
+    idx = sample(P, k)
+    for n, t in rows.items():
+        save(n, t.index_select(0, idx))
+    np.save(os.path.join(out_dir, "gaussian_index.npy"), idx.cpu().numpy().astype(np.float64))
 
 
 def cpu_baseline():
@@ -174,17 +222,21 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--sh-degree", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, 64 MB at most)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-stage table, roofline, CPU baselines, training iteration and SVD denoise step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baselines")
     ap.add_argument("--path", choices=["both", "raster", "svd"], default="both",
-                    help="hot-path halves to run at N=1 (the SVD denoise loop is replicas-only across GPUs)")
-    ap.add_argument("--svd-steps", type=int, default=5)
+                    help="(--full) hot-path halves to run at N=1 (the SVD denoise loop is replicas-only across GPUs)")
+    ap.add_argument("--svd-steps", type=int, default=5, help="(--full) timed SVD denoise steps")
     args = ap.parse_args()
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     svd_result = None
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or any(k.startswith(("ROCPROF", "ROCPROFILER")) for k in os.environ)
-    if world == 1 and args.gpus == 1 and args.path in ("both", "svd") and not under_profiler:
+    if args.full and world == 1 and args.gpus == 1 and args.path in ("both", "svd") and not under_profiler:
         # child processes, started BEFORE this process loads the HIP library or touches the GPU in any way (under rocprofv3 the
         # preloaded tool has already initialised the GPU: no children then, the SVD leg runs in this process further down)
         svd_result = svd_leg(args.svd_steps)
@@ -258,20 +310,20 @@ def main():
         if compacted:
             R.rasterize_backward(rs, st, g_img, t["means3D"], out=bucket.views, sh_grad="factor", **kw)
             bucket.exchange_support(t["means3D"], rs.campos, st.tensor("grad_support", (N,), torch.uint8))
-            return st, radii
+            return color, radii, depth, st
         if ranged:
             R.rasterize_backward_ranged(rs, st, g_img, t["means3D"], t["shs"], t["scales"], t["rotations"], bucket)
-            return st, radii
+            return color, radii, depth, st
         if factored:
             # the all-gather of the colour factors starts right behind the render backward and runs under the chain rule
             R.rasterize_backward_split(rs, st, g_img, t["means3D"], t["shs"], t["scales"], t["rotations"], bucket.views,
                                        after_render=lambda: bucket.begin_gather(rs.campos))
             bucket.finish(t["means3D"])
-            return st, radii
+            return color, radii, depth, st
         R.rasterize_backward(rs, st, g_img, t["means3D"], out=bucket.views, sh_grad="dense", **kw)
         if distributed:
             bucket.all_reduce()
-        return st, radii
+        return color, radii, depth, st
 
     def barrier():
         if world > 1 or force_dist:
@@ -279,32 +331,40 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        st, radii = step()
+        color, radii, depth, st = step()
     barrier()
-    # Pass 1 (not timed): every stage bracketed by hipEvents on the launch stream -> the per-stage table. An event record
-    # serialises the queue: ~10 us of idle GPU per bracketed stage boundary, 84 us per step with all 8 stages (measured:
-    # tools/experiments/raster_gaps.sh), which is why the timed region below brackets ONLY the roofline kernel.
-    L.mvi_raster_timing_enable(1)
-    for _ in range(args.steps):
-        st, radii = step()
-    barrier()
-    L.mvi_raster_timing_enable(0)
-    ms_all = (C.c_float * 8)()
-    calls_all = (C.c_int32 * 8)()
-    _lib.check(L.mvi_raster_timing_read(ms_all, calls_all), "timing_read")
-    dom_i = max(range(8), key=lambda i: ms_all[i])
-    # Timed region: exactly K steps, the dominant kernel's launches timed live with events on its stream (roofline.achieved)
-    L.mvi_raster_timing_enable_stages(1 << dom_i)
+    if args.full:
+        # Pass 1 (not timed): every stage bracketed by hipEvents on the launch stream -> the per-stage table. An event record
+        # serialises the queue: ~10 us of idle GPU per bracketed stage boundary, 84 us per step with all 8 stages (measured:
+        # tools/experiments/raster_gaps.sh), which is why the timed region below brackets ONLY the roofline kernel.
+        L.mvi_raster_timing_enable(1)
+        for _ in range(args.steps):
+            color, radii, depth, st = step()
+        barrier()
+        L.mvi_raster_timing_enable(0)
+        ms_all = (C.c_float * 8)()
+        calls_all = (C.c_int32 * 8)()
+        _lib.check(L.mvi_raster_timing_read(ms_all, calls_all), "timing_read")
+        dom_i = max(range(8), key=lambda i: ms_all[i])
+        # --full: the dominant kernel's launches in the timed region are timed live with events on its stream (roofline.achieved)
+        L.mvi_raster_timing_enable_stages(1 << dom_i)
+    else:
+        # untimed settling steps, as many as pass 1 gives the --full run up to 20: the first steps behind a short warm-up run
+        # ~1.5 % slow, which a timed region of 20 steps does not amortise
+        for _ in range(min(args.steps, 20)):
+            color, radii, depth, st = step()
+    # Timed region: exactly K steps
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        st, radii = step()
+        color, radii, depth, st = step()
     barrier()
     dt = time.perf_counter() - t0
-    L.mvi_raster_timing_enable(0)
-    ms = (C.c_float * 8)()
-    calls = (C.c_int32 * 8)()
-    _lib.check(L.mvi_raster_timing_read(ms, calls), "timing_read")
+    if args.full:
+        L.mvi_raster_timing_enable(0)
+        ms = (C.c_float * 8)()
+        calls = (C.c_int32 * 8)()
+        _lib.check(L.mvi_raster_timing_read(ms, calls), "timing_read")
     per_rank_ms = [round(dt / args.steps * 1e3, 4)]
     if world > 1 or force_dist:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -313,55 +373,17 @@ def main():
         per_rank_ms = [round(float(x.item()) / args.steps * 1e3, 4) for x in every]
         td.all_reduce(tt, op=td.ReduceOp.MAX)
         dt = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the step receives: the image, radii and depth of the forward, the gradients of the backward
+        dump_outputs(args.dump_outputs, {"color": color, "depth": depth},
+                     {"radii": radii, **{"grad_" + n: v for n, v in bucket.views.items() if torch.is_tensor(v) and v.shape[0] == N}}, N)
 
     if rank == 0:
         D = st.D
         V = int((radii > 0).sum().item())
         T = ((W + 15) // 16) * ((H + 15) // 16)
         Ppix = W * H
-        fwd_b, bwd_b = algorithmic_bytes(N, V, D, M, Ppix, T, n_pass=1)
-        stage_bytes = {**fwd_b, **bwd_b}
-        # The SURVEY §8d formula prices the per-Gaussian chain rule as dense: every Gaussian's parameters read, every gradient
-        # written. Since round 3 only the gradient support G (Gaussians the render backward touched) is read and computed, and
-        # the dense zero-fill of the outputs rides inside the render backward. The per-stage table uses that restated split
-        # (so no stage reads above the HBM peak); `whole_step` keeps the §8d total for comparability across rounds and shows
-        # the restated total next to it.
-        G = int(st.tensor("grad_support", (N,), torch.uint8).sum().item()) if L.mvi_raster_backward_mode(-1) == 0 else N
-        restated = dict(stage_bytes)
-        # Since round 4 the SH rows (12 M bytes per Gaussian) are not read by the preprocess kernel: a colour is evaluated the
-        # first time a tile stages the Gaussian, by the kernels of the render_forward stage (E Gaussians: their SH row, position
-        # and the 17 bytes written back). The restated split moves those bytes; the §8d total stays what it was.
-        rgbd = st.tensor("rgbd", (N, 4), torch.float32)
-        E = int(((radii > 0) & ~(rgbd[:, :3] < 0).any(1)).sum().item()) if L.mvi_raster_color_mode(-1) == 1 else V
-        if E < V:
-            restated["preprocess_forward"] = fwd_b["preprocess_forward"] - N * 12 * M
-            restated["render_forward"] = fwd_b["render_forward"] + E * (12 * M + 12 + 17)
-        if G < N:
-            restated["render_backward"] = bwd_b["render_backward"] + N * (52 + 12 * M)            # + zero-fill of the outputs
-            restated["preprocess_backward"] = N + G * (129 + 12 * M) + G * (52 + 12 * M)           # flags + support rows in / out
-        stages = {}
-        for i in range(8):
-            name = L.mvi_raster_stage_name(i).decode()
-            if calls_all[i]:
-                avg_ms = ms_all[i] / args.steps              # a stage may be bracketed more than once per step
-                stages[name] = dict(ms=round(avg_ms, 4), GBs=round(restated[name] / avg_ms / 1e6, 1))
-        dom = L.mvi_raster_stage_name(dom_i).decode()
-        dom_ms = ms[dom_i] / args.steps                      # measured inside the timed region
-        dom_gbs = round(stage_bytes[dom] / dom_ms / 1e6, 1)       # SURVEY §8d bytes of the kernel (not the restated ones)
-        # HBM bytes per launch of the dominant stage from the committed PMC passes (FETCH_SIZE / WRITE_SIZE,
-        # separate rocprofv3 --pmc runs, gfx950 correction applied: profiles/raster_traffic.json); null if absent
-        # ... and only while they were measured on THIS build (digest of the rasterizer sources recorded in the file)
-        traffic, issue = None, None
-        try:
-            with open(os.path.join(ROOT, "profiles", "raster_traffic.json")) as fh:
-                tj = json.load(fh)
-            if tj.get("build") == _lib.raster_source_digest():
-                traffic = tj["per_step_bytes_by_stage"].get(dom)
-                issue = next((v for k, v in tj.get("issue_per_kernel", {}).items() if k.startswith(dom + "_kernel")), None)
-        except (OSError, KeyError, ValueError):
-            pass
         ms_step = dt / args.steps * 1e3
-        total_bytes = sum(stage_bytes.values())
         ranges = st.tensor("ranges", (T, 2), torch.int32).long()
         lens = (ranges[:, 1] - ranges[:, 0]).float()
         nc = st.tensor("n_contrib", (H, W), torch.int32).float()
@@ -395,56 +417,99 @@ def main():
                                                            + (f" (support-compacted: union of the ranks' gradient supports {bucket.last_union_fraction:.3f} of the Gaussians, "
                                                               f"{'taken' if bucket.last_compacted else 'not taken'})" if compacted else "")
                                                            if distributed else "")},
+        }
+        if args.full:
+            fwd_b, bwd_b = algorithmic_bytes(N, V, D, M, Ppix, T, n_pass=1)
+            stage_bytes = {**fwd_b, **bwd_b}
+            # The SURVEY §8d formula prices the per-Gaussian chain rule as dense: every Gaussian's parameters read, every gradient
+            # written. Since round 3 only the gradient support G (Gaussians the render backward touched) is read and computed, and
+            # the dense zero-fill of the outputs rides inside the render backward. The per-stage table uses that restated split
+            # (so no stage reads above the HBM peak); `whole_step` keeps the §8d total for comparability across rounds and shows
+            # the restated total next to it.
+            G = int(st.tensor("grad_support", (N,), torch.uint8).sum().item()) if L.mvi_raster_backward_mode(-1) == 0 else N
+            restated = dict(stage_bytes)
+            # Since round 4 the SH rows (12 M bytes per Gaussian) are not read by the preprocess kernel: a colour is evaluated the
+            # first time a tile stages the Gaussian, by the kernels of the render_forward stage (E Gaussians: their SH row, position
+            # and the 17 bytes written back). The restated split moves those bytes; the §8d total stays what it was.
+            rgbd = st.tensor("rgbd", (N, 4), torch.float32)
+            E = int(((radii > 0) & ~(rgbd[:, :3] < 0).any(1)).sum().item()) if L.mvi_raster_color_mode(-1) == 1 else V
+            if E < V:
+                restated["preprocess_forward"] = fwd_b["preprocess_forward"] - N * 12 * M
+                restated["render_forward"] = fwd_b["render_forward"] + E * (12 * M + 12 + 17)
+            if G < N:
+                restated["render_backward"] = bwd_b["render_backward"] + N * (52 + 12 * M)            # + zero-fill of the outputs
+                restated["preprocess_backward"] = N + G * (129 + 12 * M) + G * (52 + 12 * M)           # flags + support rows in / out
+            stages = {}
+            for i in range(8):
+                name = L.mvi_raster_stage_name(i).decode()
+                if calls_all[i]:
+                    avg_ms = ms_all[i] / args.steps              # a stage may be bracketed more than once per step
+                    stages[name] = dict(ms=round(avg_ms, 4), GBs=round(restated[name] / avg_ms / 1e6, 1))
+            dom = L.mvi_raster_stage_name(dom_i).decode()
+            dom_ms = ms[dom_i] / args.steps                      # measured inside the timed region
+            dom_gbs = round(stage_bytes[dom] / dom_ms / 1e6, 1)       # SURVEY §8d bytes of the kernel (not the restated ones)
+            # HBM bytes per launch of the dominant stage from the committed PMC passes (FETCH_SIZE / WRITE_SIZE,
+            # separate rocprofv3 --pmc runs, gfx950 correction applied: profiles/raster_traffic.json); null if absent
+            # ... and only while they were measured on THIS build (digest of the rasterizer sources recorded in the file)
+            traffic, issue = None, None
+            try:
+                with open(os.path.join(ROOT, "profiles", "raster_traffic.json")) as fh:
+                    tj = json.load(fh)
+                if tj.get("build") == _lib.raster_source_digest():
+                    traffic = tj["per_step_bytes_by_stage"].get(dom)
+                    issue = next((v for k, v in tj.get("issue_per_kernel", {}).items() if k.startswith(dom + "_kernel")), None)
+            except (OSError, KeyError, ValueError):
+                pass
+            total_bytes = sum(stage_bytes.values())
             # achieved = algorithmic bytes of the dominant kernel's launch / its launch time, against the HBM peak.
             # The render kernels are not HBM-bound (most of their list gathers are L2 hits: `traffic` is BELOW the algorithmic
             # bytes), which is exactly what a low fraction says; what they ARE bound by rides along as information only:
             # `issue` (vector instructions issued per launch from the PMC passes, as a share of the launch's SIMD cycles — a
             # utilisation, not a roof: it rewards wasted instructions) and `compute` (useful fp32 work: evaluated (pixel,
             # Gaussian) pairs x FLOPs per pair against the 157.3 TFLOP/s vector peak).
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": dom_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(dom_gbs / HBM_PEAK_GBS, 5),
-                         "traffic": traffic,
-                         "launch_ms": round(dom_ms, 4),
-                         "algorithmic_bytes_per_launch": int(stage_bytes[dom]),
-                         "restated": {"bytes_per_launch": int(restated[dom]),
-                                      "frac": round(restated[dom] / dom_ms / 1e6 / HBM_PEAK_GBS, 5),
-                                      "note": "with the zero-fill of the dense gradient outputs that rides inside this kernel since round 3"},
-                         "counters_build": _lib.raster_source_digest(),
-                         "whole_step": {"algorithmic_bytes": int(total_bytes),
-                                        "GBs": round(total_bytes / ms_step / 1e6, 1),
-                                        "frac": round(total_bytes / ms_step / 1e6 / HBM_PEAK_GBS, 5),
-                                        "formula": "SURVEY.md 8d, dense chain rule (comparable across rounds)",
-                                        "restated_bytes": int(sum(restated.values())),
-                                        "restated_frac": round(sum(restated.values()) / ms_step / 1e6 / HBM_PEAK_GBS, 5),
-                                        "gradient_support": G, "colours_evaluated": E},
-                         "compute": {"evaluated_pairs": int(nc.double().sum().item()),
-                                     "flops_per_pair": PAIR_FLOPS.get(dom),
-                                     "TFLOPs": (round(float(nc.double().sum().item()) * PAIR_FLOPS[dom] / dom_ms / 1e9, 2)
-                                                if dom in PAIR_FLOPS else None),
-                                     "peak": FP32_VECTOR_PEAK_TFLOPS,
-                                     "frac": (round(float(nc.double().sum().item()) * PAIR_FLOPS[dom] / dom_ms / 1e9 / FP32_VECTOR_PEAK_TFLOPS, 4)
-                                              if dom in PAIR_FLOPS else None),
-                                     "note": "pairs = sum of n_contrib (list entries each pixel walks); FLOPs per pair counted "
-                                             "from the kernel's arithmetic (DESIGN.md §4)"},
-                         **({"issue": {"valu_wave_instructions_per_launch": int(issue["SQ_INSTS_VALU"]),
-                                       "share_of_simd_cycles": issue["valu_issue_frac"]}} if issue else {})},
-            "stages": stages,
-            "stages_note": "per-stage times from a separate pass of K steps with every stage bracketed by hipEvents (each "
-                           "bracketed boundary idles the GPU ~10 us); the timed region brackets only the roofline kernel. GB/s of "
-                           "render_backward / preprocess_backward use the restated bytes (zero-fill inside the render backward, "
-                           "chain rule on the gradient support only), preprocess_forward / render_forward the restated bytes of the "
-                           "deferred SH colours (SH rows read for the colours_evaluated Gaussians only, by the render_forward stage: "
-                           "mark_front + resolve_marked + render_forward kernels), every other stage the SURVEY 8d bytes",
-        }
-        if world == 1 and not args.no_cpu_baseline:
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": dom_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(dom_gbs / HBM_PEAK_GBS, 5),
+                               "traffic": traffic,
+                               "launch_ms": round(dom_ms, 4),
+                               "algorithmic_bytes_per_launch": int(stage_bytes[dom]),
+                               "restated": {"bytes_per_launch": int(restated[dom]),
+                                            "frac": round(restated[dom] / dom_ms / 1e6 / HBM_PEAK_GBS, 5),
+                                            "note": "with the zero-fill of the dense gradient outputs that rides inside this kernel since round 3"},
+                               "counters_build": _lib.raster_source_digest(),
+                               "whole_step": {"algorithmic_bytes": int(total_bytes),
+                                              "GBs": round(total_bytes / ms_step / 1e6, 1),
+                                              "frac": round(total_bytes / ms_step / 1e6 / HBM_PEAK_GBS, 5),
+                                              "formula": "SURVEY.md 8d, dense chain rule (comparable across rounds)",
+                                              "restated_bytes": int(sum(restated.values())),
+                                              "restated_frac": round(sum(restated.values()) / ms_step / 1e6 / HBM_PEAK_GBS, 5),
+                                              "gradient_support": G, "colours_evaluated": E},
+                               "compute": {"evaluated_pairs": int(nc.double().sum().item()),
+                                           "flops_per_pair": PAIR_FLOPS.get(dom),
+                                           "TFLOPs": (round(float(nc.double().sum().item()) * PAIR_FLOPS[dom] / dom_ms / 1e9, 2)
+                                                      if dom in PAIR_FLOPS else None),
+                                           "peak": FP32_VECTOR_PEAK_TFLOPS,
+                                           "frac": (round(float(nc.double().sum().item()) * PAIR_FLOPS[dom] / dom_ms / 1e9 / FP32_VECTOR_PEAK_TFLOPS, 4)
+                                                    if dom in PAIR_FLOPS else None),
+                                           "note": "pairs = sum of n_contrib (list entries each pixel walks); FLOPs per pair counted "
+                                                   "from the kernel's arithmetic (DESIGN.md §4)"},
+                               **({"issue": {"valu_wave_instructions_per_launch": int(issue["SQ_INSTS_VALU"]),
+                                             "share_of_simd_cycles": issue["valu_issue_frac"]}} if issue else {})}
+            out["stages"] = stages
+            out["stages_note"] = ("per-stage times from a separate pass of K steps with every stage bracketed by hipEvents (each "
+                                  "bracketed boundary idles the GPU ~10 us); the timed region brackets only the roofline kernel. GB/s of "
+                                  "render_backward / preprocess_backward use the restated bytes (zero-fill inside the render backward, "
+                                  "chain rule on the gradient support only), preprocess_forward / render_forward the restated bytes of the "
+                                  "deferred SH colours (SH rows read for the colours_evaluated Gaussians only, by the render_forward stage: "
+                                  "mark_front + resolve_marked + render_forward kernels), every other stage the SURVEY 8d bytes")
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
-        if world == 1 and args.path == "both":
+        if args.full and world == 1 and args.path == "both":
             # SURVEY.md §8f rows either side of the rasterizer: one full training iteration, fused HIP ops vs PyTorch ops
             t = bucket = st = g_img = None
             torch.cuda.empty_cache()
             from multiview_inpaint_amd import bench_train
             out["train_iteration"] = bench_train.run_both(steps=20, warmup=5)
-        if world == 1 and args.path in ("both", "svd"):
+        if args.full and world == 1 and args.path in ("both", "svd"):
             # second half of the BASELINE.json metric: SVD 14-frame 576x1024 denoise steps/s
             t = bucket = st = g_img = None
             torch.cuda.empty_cache()

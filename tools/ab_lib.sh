@@ -8,8 +8,8 @@ cd $R
 for rep in 1 2; do
   for lib in shipped "$@"; do
     name=$(basename $lib .so)
-    if [ "$lib" = shipped ]; then env -u MVI_HIP_LIB python bench.py --path raster --no-cpu-baseline > $OUT/${name}_$rep.json 2>/dev/null
-    else MVI_HIP_LIB=$R/$lib python bench.py --path raster --no-cpu-baseline > $OUT/${name}_$rep.json 2>/dev/null; fi
+    if [ "$lib" = shipped ]; then env -u MVI_HIP_LIB python bench.py --full --path raster --no-cpu-baseline > $OUT/${name}_$rep.json 2>/dev/null
+    else MVI_HIP_LIB=$R/$lib python bench.py --full --path raster --no-cpu-baseline > $OUT/${name}_$rep.json 2>/dev/null; fi
   done
 done
 python3 - <<PY

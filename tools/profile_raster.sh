@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 5 --warmup 1 --path raster --no-cpu-baseline"
+B="python3 $R/bench.py --full --steps 5 --warmup 1 --path raster --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $B > $OUT/bench_under_trace.json 2> /dev/null
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $B > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE TCC_EA0_ATOMIC_sum --output-format csv -d $OUT/pmc_write -- $B > /dev/null 2>&1
@@ -21,5 +21,5 @@ cp $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
 rm -rf $OUT/trace $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_sq $OUT/pmc_clk
 # counters of THIS build first (the file carries the digest of the rasterizer sources), then the un-profiled bench line that quotes them
 python3 $R/tools/make_traffic_json.py $OUT $TAG > $OUT/traffic_by_stage.json && cp $R/profiles/raster_traffic.json $OUT/raster_traffic.json
-python3 $R/bench.py --steps 20 --warmup 3 --path raster > $OUT/bench.json 2> /dev/null
+python3 $R/bench.py --full --steps 20 --warmup 3 --path raster > $OUT/bench.json 2> /dev/null
 ls -la $OUT

@@ -9,7 +9,7 @@ mkdir -p $OUT /tmp/mvi_miopen_regen
 rm -f /tmp/mvi_miopen_regen/*
 export MIOPEN_USER_DB_PATH=/tmp/mvi_miopen_regen
 cd $R; T0=$(date +%s)
-MVI_SVD_MIOPEN_FIND=1 python bench.py --path svd --no-cpu-baseline --svd-steps 2 > $OUT/bench_first.json 2> $OUT/bench_first.err
+MVI_SVD_MIOPEN_FIND=1 python bench.py --full --path svd --no-cpu-baseline --svd-steps 2 > $OUT/bench_first.json 2> $OUT/bench_first.err
 echo "first run: $(( $(date +%s) - T0 )) s"; cp /tmp/mvi_miopen_regen/* $OUT/ 2>/dev/null
 ls -la $OUT
 tail -2 $OUT/bench_first.err
