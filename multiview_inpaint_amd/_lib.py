@@ -1,4 +1,5 @@
-"""ctypes binding of the C-ABI HIP library (include/mvi_raster.h, include/mvi_unet_ops.h, include/mvi_train_ops.h).
+"""ctypes binding of the C-ABI HIP library (include/mvi_raster.h, include/mvi_unet_ops.h, include/mvi_train_ops.h,
+include/mvi_box_region.h).
 
 There is NO fallback: if libmvi_hip.so is missing or does not export a declared symbol this
 module raises, and every op of the package fails with it."""
@@ -140,6 +141,7 @@ def lib():
     L.mvi_raster_dev_stamps.argtypes = [C.c_int, vp]
     _bind_unet_ops(L)
     _bind_train_ops(L)
+    _bind_box_region(L)
     _lib = L
     return L
 
@@ -186,6 +188,18 @@ def _bind_train_ops(L):
     L.mvi_gaussian_activations.argtypes = [i32, i32] + [vp] * 10
     L.mvi_gaussian_activations_backward.restype = C.c_int
     L.mvi_gaussian_activations_backward.argtypes = [i32, i32] + [vp] * 13
+
+
+def _bind_box_region(L):
+    """include/mvi_box_region.h"""
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.mvi_box_region_last_error.restype = C.c_char_p
+    L.mvi_mesh_intersect.restype = C.c_int
+    L.mvi_mesh_intersect.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, vp, vp]
+    L.mvi_mesh_points_inside.restype = C.c_int
+    L.mvi_mesh_points_inside.argtypes = [vp, i64, vp, i32, vp, vp]
+    L.mvi_mesh_view_masks.restype = C.c_int
+    L.mvi_mesh_view_masks.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]
 
 
 def check(rc, what):

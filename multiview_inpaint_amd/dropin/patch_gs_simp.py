@@ -43,6 +43,14 @@ What install() does (each part can be switched off):
               12 moments through train_ops.extend_optimizer_state (moments: allocate + copy + memset of the new rows instead of a
               zeros_like temporary and a concatenation each) — identical tensors, optimizer.state re-keyed the same way; a dict or an
               optimizer of another shape goes to the reference's method.
+  * mesh      utils.bounding.torchMesh.intersect (gs-simp/utils/bounding.py:101-121; gen_seq.py:47 casts one ray per pixel through it,
+              del.py:106-107 two per Gaussian, render_depth.py and vis_render.py read the same depth contract) becomes ONE launch of
+              multiview_inpaint_amd.box_region.intersect on the object's own f_v, instead of ~30 PyTorch ops per chunk of 10 000 rays;
+              `bs` is accepted and ignored. Same return shapes and dtypes (int_p [n,3], int_t [n,1], t_ind [n,1] int64, cond [n,1]
+              bool); the cross product is taken over the last axis (the reference's torch.cross without `dim` is wrong for a chunk
+              of exactly 3 rays). Rays that are not CUDA float32 [n,3] go to the reference's method (kept as
+              `torchMesh._reference_intersect`). Only when utils/bounding.py exists and defines torchMesh: otherwise nothing
+              happens.
 Nothing is patched that is not named here; a script that imported the loss functions before install() ran keeps the
 reference's (install() must come first — the runner below guarantees it)."""
 import functools
@@ -175,7 +183,22 @@ def _make_cat_tensors(reference_cat_tensors):
     return cat_tensors_to_optimizer
 
 
-def install(loss=True, optimizer=True, render=True, stats=True, surgery=True):
+def _make_intersect(reference_intersect):
+    @functools.wraps(reference_intersect)
+    def intersect(self, rayo, rayd, bs=10000):
+        import torch
+        f_v = getattr(self, "f_v", None)
+        ok = all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (rayo, rayd, f_v))
+        ok = ok and rayo.ndim == 2 and rayo.shape[1] == 3 and rayd.shape == rayo.shape and rayo.device == rayd.device == f_v.device
+        if not ok:
+            return reference_intersect(self, rayo, rayd, bs)
+        from multiview_inpaint_amd import box_region
+        return box_region.intersect(self, rayo, rayd)
+    intersect._mvi_patched = True
+    return intersect
+
+
+def install(loss=True, optimizer=True, render=True, stats=True, surgery=True, mesh=True):
     """Patches the gs-simp modules named above (they must be importable: the script's directory on sys.path). Returns the
     list of what was patched, for logging. Idempotent."""
     if _DROPIN not in sys.path:
@@ -235,6 +258,18 @@ def install(loss=True, optimizer=True, render=True, stats=True, surgery=True):
             gr._reference_render = gr.render
             gr.render = _make_render(gr.render, gm.GaussianModel)
         done.append("gaussian_renderer.render")
+    if mesh:
+        try:
+            bd = importlib.import_module("utils.bounding")
+        except ImportError:                           # a script tree without the box utilities: nothing to patch
+            bd = None
+        cls = getattr(bd, "torchMesh", None)
+        fn = isinstance(cls, type) and cls.__dict__.get("intersect")
+        if fn:
+            if not getattr(fn, "_mvi_patched", False):
+                cls._reference_intersect = fn
+                cls.intersect = _make_intersect(fn)
+            done.append("utils.bounding.torchMesh.intersect")
     return done
 
 
