@@ -10,7 +10,7 @@
 //                The Gaussians are walked in depth order and their segments are partitioned by tile column (stable): the
 //                output holds, column by column, the segments in depth order — 6 bytes per segment, 3.3 times fewer items
 //                than pairs, and the input is the 8-byte rectangle, not a list of pairs;
-//   pass 2       every column is cut into chunks of 2048 segments; a chunk's segments are expanded along y and partitioned by
+//   pass 2       every column is cut into chunks of 1536 segments; a chunk's segments are expanded along y and partitioned by
 //                tile row (stable). (row, column, depth order) IS the tile-major order, so the output is the sorted point
 //                list; the row-scan of the chunk table knows where every (row, column) starts, so the tile ranges fall out of
 //                it and the first chunk of each column writes them (every tile: empty ones get (0, 0) like the plug-in's
@@ -329,14 +329,14 @@ __global__ __launch_bounds__(kExThreads) void column_count_kernel(int P, int gx,
 }
 
 // =================================================================================================== row scans
-// Chunk table of pass 2 from the column totals: chunk_first[x] = first chunk of tile column x, chunk_first[gx] = number of
+// Chunk table of pass 2 (kEx2Chunk segments per chunk) from the column totals: chunk_first[x] = first chunk of tile column x, chunk_first[gx] = number of
 // chunks; col_start[x] = first segment of column x, col_start[gx] = number of segments. Every column owns at least one chunk
 // (an empty one writes the column's empty ranges). Built by the block of columns_scan_kernel whose arrival is last.
 __device__ __forceinline__ void build_chunk_table(const uint32_t* col_tot, int gx, int tid, uint32_t* __restrict__ chunk_first,
                                                   uint32_t* __restrict__ col_start, uint32_t* s_w4) {
     // the totals were stored by other blocks with agent-scope stores, each drained before that block's arrival: L2 loads
     const uint32_t v = tid < gx ? __hip_atomic_load(col_tot + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-    const uint32_t c = tid < gx ? max(1u, (v + (uint32_t)kExChunk - 1u) / (uint32_t)kExChunk) : 0u;
+    const uint32_t c = tid < gx ? max(1u, (v + (uint32_t)kEx2Chunk - 1u) / (uint32_t)kEx2Chunk) : 0u;
     uint32_t tv, tc;
     const uint32_t ev = block_excl_scan256(v, tid, s_w4, &tv);
     const uint32_t ec = block_excl_scan256(c, tid, s_w4, &tc);
@@ -402,8 +402,8 @@ __device__ __forceinline__ bool load_chunk(const uint32_t* __restrict__ chunk_fi
     }
     ck.x = lo;
     ck.first = c == s_first[lo];
-    ck.seg0 = s_col[lo] + (c - s_first[lo]) * (uint32_t)kExChunk;
-    ck.seg1 = min(ck.seg0 + (uint32_t)kExChunk, s_col[lo + 1]);
+    ck.seg0 = s_col[lo] + (c - s_first[lo]) * (uint32_t)kEx2Chunk;
+    ck.seg1 = min(ck.seg0 + (uint32_t)kEx2Chunk, s_col[lo + 1]);
     return true;
 }
 
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(kExThreads) void row_count_kernel(int gx, int gy, c
     Chunk ck;
     if (!load_chunk(chunk_first, col_start, gx, tid, s_first, s_col, ck)) return;
 #pragma unroll
-    for (int k = 0; k < kExItems; ++k) {
+    for (int k = 0; k < kEx2Items; ++k) {
         const uint32_t i = ck.seg0 + (uint32_t)(k * kExThreads + tid);
         if (i < ck.seg1) {
             const uint32_t yh = seg_yh[i];
@@ -475,17 +475,19 @@ __global__ __launch_bounds__(1024) void row_scan_kernel(int gx, const uint32_t* 
 }
 
 // =================================================================================================== expanding partition
-// One block = kExChunk items in 32 wave rounds of 64 (wave w loads rounds 4w .. 4w + 3). An item covers the bins
-// [a, a + n); its entries (item, bin) leave the block grouped by bin, inside a bin in item order.
+// One block = 512 x ITEMS items in 8 x ITEMS wave rounds of 64 (wave w loads rounds ITEMS w .. ITEMS w + ITEMS - 1): pass 1
+// 2048 Gaussians in 32 rounds, pass 2 1536 column segments in 24. An item covers the bins [a, a + n); its entries (item, bin)
+// leave the block grouped by bin, inside a bin in item order.
 //   A  every item ORs its lane bit into mask[round][bin] for each bin it covers (LDS atomics, nothing waits for them).
 //   B  thread (part q, bin b) — 512 threads = bins in use x parts of the rounds — counts the set bits of ITS masks; the bins'
 //      totals are scanned into the image layout, the parts of a bin follow each other.
 //   C  the same thread walks the set bits of its masks in round order = the bin's entries in item order, and writes
 //      (item, bin) words into the LDS image at consecutive places: no LDS read, no wait inside the loop.
 //   D  the image leaves in bin runs, consecutive lanes on consecutive entries; the item's payload is fetched from LDS here.
-// The image holds kCap entries; B to D repeat over groups of consecutive rounds that fit (one group for ordinary scenes; a
-// round never exceeds 64 * NB = kCap entries). Skew: a bin that holds most of the block's entries is walked by few threads
-// (all Gaussians in one tile column) — slower, never wrong.
+// The image holds CAP >= 64 * NB entries; B to D repeat over groups of consecutive rounds that fit (one group for ordinary
+// scenes; a round never exceeds 64 * NB entries). LDS sets the blocks per CU: pass 2 at <= 80 tile rows (NB 80, CAP 7168,
+// 24 rounds) takes 50 KB, three blocks per CU; NB 128 with 2048-item chunks took 77 KB, two. Skew: a bin that holds most of
+// the block's entries is walked by few threads (all Gaussians in one tile column) — slower, never wrong.
 struct ExpandArgs {
     int n_items;                        // pass 1: P
     int nbins;                          // pass 1: gx, pass 2: gy
@@ -534,21 +536,25 @@ __device__ __forceinline__ void block_excl_scan512x2(uint32_t a, uint32_t b, int
     ea = oa + ia - a; eb = ob + ib - b; ta = t;
 }
 
-template <int PASS, int NB>
+template <int PASS, int NB, int ITEMS, int CAP>
 __global__ __launch_bounds__(kExThreads) void expand_scatter_kernel(ExpandArgs A) {
-    constexpr int kCap = 64 * NB;                    // 8192 / 16384 entries
-    constexpr int kRounds = kExChunk / 64;           // 32
+    constexpr int kChunk = kExThreads * ITEMS;       // items per block: pass 1 2048, pass 2 1536
+    constexpr int kCap = CAP;                        // image entries
+    constexpr int kRounds = kChunk / 64;             // 32 / 24
     constexpr int kStride = NB + 1;                  // mask row stride (uint64): rows of one bin fall into different banks
-    static_assert(kExThreads / 64 * kExItems == kRounds, "wave w loads rounds kExItems * w ..");
+    static_assert(kCap >= 64 * NB, "a round of 64 items (<= 64 * NB entries) always fits the image");
+    static_assert(kRounds >= 16, "worker parts <= rounds");
     static_assert(kExThreads == 512, "block_excl_scan512x2");
-    __shared__ unsigned long long s_mask[kRounds * kStride + 1];
-    __shared__ uint32_t s_pay[kExChunk];
-    __shared__ uint16_t s_aux[PASS == 1 ? kExChunk : 1];
+    __shared__ alignas(16) unsigned long long s_mask[kRounds * kStride + 1];
+    __shared__ uint32_t s_pay[kChunk];
+    __shared__ uint16_t s_aux[PASS == 1 ? kChunk : 1];
     __shared__ uint32_t s_img[kCap];                 // item | bin << 16
     __shared__ uint32_t s_lstart[NB + 1], s_delta[NB];
     __shared__ uint32_t s_rtot[kRounds];
     __shared__ uint32_t s_w[2][8];
-    __shared__ uint32_t s_first[PASS == 2 ? 257 : 1], s_col[PASS == 2 ? 257 : 1];
+    // pass 2: the chunk table is read (load_chunk) before the image is written, behind the barrier after the mask clear
+    uint32_t* const s_first = s_img;
+    uint32_t* const s_col = s_img + 257;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t blk = blockIdx.x;
 
@@ -556,18 +562,18 @@ __global__ __launch_bounds__(kExThreads) void expand_scatter_kernel(ExpandArgs A
     uint32_t item0 = 0, item1 = 0;
     Chunk ck{0, 0u, 0u, false};
     if (PASS == 1) {
-        item0 = blk * (uint32_t)kExChunk;
-        item1 = min(item0 + (uint32_t)kExChunk, (uint32_t)A.n_items);
+        item0 = blk * (uint32_t)kChunk;
+        item1 = min(item0 + (uint32_t)kChunk, (uint32_t)A.n_items);
     } else {
         if (!load_chunk(A.chunk_first, A.col_start, A.gx, tid, s_first, s_col, ck)) return;
         item0 = ck.seg0; item1 = ck.seg1;
     }
     MVI_STAMP(0);
     // requested first: they travel while the masks are cleared
-    uint32_t ia[kExItems], in_[kExItems];
+    uint32_t ia[ITEMS], in_[ITEMS];
 #pragma unroll
-    for (int k = 0; k < kExItems; ++k) {
-        const int li = (wave * kExItems + k) * 64 + lane;          // item of round wave * kExItems + k, lane
+    for (int k = 0; k < ITEMS; ++k) {
+        const int li = (wave * ITEMS + k) * 64 + lane;             // item of round wave * ITEMS + k, lane
         const uint32_t i = item0 + (uint32_t)li;
         ia[k] = 0; in_[k] = 0;
         uint32_t pay = 0, aux = 0;
@@ -613,8 +619,8 @@ __global__ __launch_bounds__(kExThreads) void expand_scatter_kernel(ExpandArgs A
     // ---- A: lane bits into the masks of the covered bins
     const unsigned long long bit = 1ull << lane;
 #pragma unroll
-    for (int k = 0; k < kExItems; ++k) {
-        unsigned long long* row = s_mask + (wave * kExItems + k) * kStride;
+    for (int k = 0; k < ITEMS; ++k) {
+        unsigned long long* row = s_mask + (wave * ITEMS + k) * kStride;
         for (uint32_t i = 0; i < in_[k]; ++i) atomicOr(&row[ia[k] + i], bit);
     }
     __syncthreads();
@@ -743,12 +749,13 @@ int launch_binning2(const Frame& f, GeomView g, BinningView b, ImageView im, int
     a1.stamps = g_dev_stamps[0];
     {
         StageTimer tm(kStDup, st);
-        if (wide) hipLaunchKernelGGL((expand_scatter_kernel<1, 256>), dim3(g.nblk1), dim3(kExThreads), 0, st, a1);
-        else hipLaunchKernelGGL((expand_scatter_kernel<1, 128>), dim3(g.nblk1), dim3(kExThreads), 0, st, a1);
+        if (wide)
+            hipLaunchKernelGGL((expand_scatter_kernel<1, 256, kExItems, 64 * 256>), dim3(g.nblk1), dim3(kExThreads), 0, st, a1);
+        else hipLaunchKernelGGL((expand_scatter_kernel<1, 128, kExItems, 64 * 128>), dim3(g.nblk1), dim3(kExThreads), 0, st, a1);
     }
-    // chunks: at most segments / kExChunk + gx; the table (stride b.nsort) was sized for segments <= D
+    // chunks: at most segments / kEx2Chunk + gx; the table (stride b.nsort) was sized for segments <= D
     int nchunk = b.nsort;
-    if (segments > 0 && segments <= D) nchunk = (int)min((int64_t)b.nsort, segments / kExChunk + f.gx + 1);
+    if (segments > 0 && segments <= D) nchunk = (int)min((int64_t)b.nsort, segments / kEx2Chunk + f.gx + 1);
     ExpandArgs a2{};
     a2.nbins = f.gy; a2.gx = f.gx;
     a2.chunk_first = g.chunk_first; a2.col_start = g.col_start;
@@ -762,8 +769,13 @@ int launch_binning2(const Frame& f, GeomView g, BinningView b, ImageView im, int
                        (const uint16_t*)b.keys[0], b.block_hist, b.nsort);
     hipLaunchKernelGGL(row_scan_kernel, dim3(f.gy), dim3(1024), 0, st, f.gx, g.chunk_first, b.block_hist, b.nsort,
                        b.digit_tot, b.col_rel);
-    if (wide) hipLaunchKernelGGL((expand_scatter_kernel<2, 256>), dim3(nchunk), dim3(kExThreads), 0, st, a2);
-    else hipLaunchKernelGGL((expand_scatter_kernel<2, 128>), dim3(nchunk), dim3(kExThreads), 0, st, a2);
+    // bins = tile rows: up to 80 rows the small instantiation (~50 KB of LDS, three blocks per CU instead of two)
+    if (f.gy <= kEx2SmallNB)
+        hipLaunchKernelGGL((expand_scatter_kernel<2, kEx2SmallNB, kEx2Items, kEx2SmallCap>), dim3(nchunk), dim3(kExThreads), 0,
+                           st, a2);
+    else if (f.gy <= 128)
+        hipLaunchKernelGGL((expand_scatter_kernel<2, 128, kEx2Items, 64 * 128>), dim3(nchunk), dim3(kExThreads), 0, st, a2);
+    else hipLaunchKernelGGL((expand_scatter_kernel<2, 256, kEx2Items, 64 * 256>), dim3(nchunk), dim3(kExThreads), 0, st, a2);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 

@@ -59,7 +59,11 @@ constexpr int kDsTile = kDsThreads * kDsItems;
 constexpr int kDsSuper = 16;                        // count-table rows per super row (two-level predecessor sums)
 constexpr int kExThreads = 512;                     // expanding partition passes: 512 threads x 4 items
 constexpr int kExItems = 4;
-constexpr int kExChunk = kExThreads * kExItems;     // items (Gaussians in pass 1, column segments in pass 2) per block
+constexpr int kExChunk = kExThreads * kExItems;     // Gaussians per block of pass 1
+constexpr int kEx2Items = 3;                        // pass 2: 512 threads x 3 column segments = 1536-segment chunks
+constexpr int kEx2Chunk = kExThreads * kEx2Items;
+constexpr int kEx2SmallNB = 80;                     // pass 2 over at most 80 tile rows (images up to 1280 px high): small LDS
+constexpr int kEx2SmallCap = 7168;                  // image entries of that instantiation (a chunk holds ~3.3 entries per segment)
 bool binning_v2_enabled();                          // false when MVI_BINNING_LEGACY=1 or after set_binning_version(1)
 void set_dev_stamps(int pass, void* buf);            // diagnostics: shader-clock stamps of the partition kernel's phases
 int set_binning_version(int v);                     // 1 | 2 (anything else: query only); returns the previous version
@@ -231,9 +235,9 @@ inline BinningView carve_binning(void* base, int64_t D, int W, int H) {
     v.v2 = binning_v2_ok(gx, gy) ? 1 : 0;
     v.col_rel = nullptr;
     if (v.v2) {
-        // chunks of pass 2: every tile column owns at least one, so at most D / kExChunk + gx (column segments <= pairs);
+        // chunks of pass 2: every tile column owns at least one, so at most D / kEx2Chunk + gx (column segments <= pairs);
         // the launches use the exact segment count when the forward knows it
-        v.nsort = (int)((n / kExChunk + (size_t)gx + 1 + 3) / 4 * 4);
+        v.nsort = (int)((n / kEx2Chunk + (size_t)gx + 1 + 3) / 4 * 4);
         v.passes = 1;
         v.key_bytes = 2;
     }
