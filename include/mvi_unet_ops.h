@@ -361,6 +361,30 @@ int mvi_attention_kernel_kind(int32_t Sq, int32_t Sk, int32_t D, int32_t dtype);
  * self-attention of the 576 x 1024 step). mvi_attention_forward* dispatch on exactly this function. */
 int mvi_attention_kernel_variant(int32_t Sq, int32_t Sk, int32_t D, int32_t dtype);
 
+/* Differentiable attention (csrc/attn_bwd.hip): the forward and backward of softmax(q k^T * scale) v for training through the
+ * attention of the reference's CrossAttention (svd_inpaint1/sgm/modules/attention.py:250-344) — bf16 / f16 I/O, D == 64, Sk > 32: the
+ * domain where mvi_attention_kernel_kind is 1. Anything else returns MVI_EINVAL and launches nothing.
+ *
+ * mvi_attention_backward_supported: pure host function, 1 where the three functions below compute (the Python gate reads it).
+ * mvi_attention_forward_lse: mvi_attention_forward (same kernel, same instructions: `out` is bit-identical) that also writes
+ *     lse [B, H, Sq] fp32, the log-sum-exp of the scaled scores of every (batch, head, query).
+ * mvi_attention_backward: dq [B, Sq, H, D], dk, dv [B, Sk, H, D] (contiguous, the I/O type) from q, k, v, out, dout in the forward's
+ *     layout and lse. fp32 accumulation and softmax terms; P and dS are rounded to the I/O type only as MFMA operands. Deterministic:
+ *     no atomics, two runs give the same bits. dk and dv may both be NULL (the dK/dV kernel is skipped); dq may be NULL (the dQ kernel
+ *     still runs — it produces the fp32 rowsum(P dP) the dK/dV kernel takes as delta — and stores nothing else). workspace:
+ *     mvi_attention_backward_workspace_bytes(...) bytes, 4-byte aligned (delta = rowsum(dout * out) for the dQ kernel, rowsum(P dP)). */
+int mvi_attention_backward_supported(int32_t Sq, int32_t Sk, int32_t D, int32_t dtype);
+int mvi_attention_forward_lse(const void* q, const void* k, const void* v, void* out, void* lse, int32_t B, int32_t H, int32_t Sq,
+                              int32_t Sk, int32_t D, float scale, int32_t dtype, void* stream);
+size_t mvi_attention_backward_workspace_bytes(int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t D, int32_t dtype);
+int mvi_attention_backward(const void* q, const void* k, const void* v, const void* out, const void* dout, const void* lse, void* dq,
+                           void* dk, void* dv, int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t D, float scale, int32_t dtype,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* Backward of mvi_attention_temporal, same layout [(Bo*T), S, H, D] for all seven tensors, nothing regrouped: dq, dk, dv from q, k, v,
+ * dout. The softmax is recomputed in fp32 (T <= 16); fp32 / bf16 / f16 I/O, D in {16, 32, 64}. Deterministic. */
+int mvi_attention_temporal_backward(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
+                                    int32_t Bo, int32_t T, int32_t S, int32_t H, int32_t D, float scale, int32_t dtype, void* stream);
+
 const char* mvi_unet_last_error(void);
 
 /* ---- Round 6: first-stage (VAE) decoder convolutions at fp32 accuracy on the bf16 matrix pipe (split operands).

@@ -96,12 +96,14 @@ constexpr float kRescaleThreshold = 8.0f;   // log2 units: O and l are rescaled 
 // slots ~ 900 cycles per wave-tile against 512 matrix-pipe cycles. LDS holds K_{t+1} / K_{t+2} and V_t / V_{t+1}: two buffers each, one
 // barrier per tile (K_{t+2} overwrites K_t, whose last reader finished before the previous barrier;
 // V_{t+1} overwrites V_{t-1} likewise).
-template <typename T>
+// kLse (the forward under autograd, mvi_attention_forward_lse): also writes the row's log-sum-exp of the scaled scores, fp32
+// [B, H, Sq], for csrc/attn_bwd.hip; `out` is computed by the same instructions in the same order either way.
+template <typename T, bool kLse>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MVI_ATTN_WPE, MVI_ATTN_WPE))) void attn_flash_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                                    const T* __restrict__ v, T* __restrict__ out, int H,
                                                                    int Sq, int Sk, float scale_log2e, int q_blocks,
                                                                    int total_blocks, int64_t q_rs, int64_t kv_rs,
-                                                                   int64_t o_rs) {
+                                                                   int64_t o_rs, float* __restrict__ lse) {
     using M = Mma<T>;
     using frag = typename M::frag;
     __shared__ __attribute__((aligned(16))) uint16_t s_k[2][kFK * kKStride];
@@ -349,6 +351,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MVI_ATTN_WP
 #if MVI_ATTN_PIPE || !MVI_ATTN_MFMA_ROWSUM
     l += __shfl_xor(l, 32);                                  // the two lane halves hold disjoint keys of every k-step
 #endif
+    if (kLse && qrow < Sq && hh == 0) lse[(b * H + h) * Sq + qrow] = (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;   // m is in log2 units
     if (qrow < Sq) {
         const float inv = 1.0f / l;
         T* op = out + ((b * Sq + qrow) * o_rs + (int64_t)h * kFD);
@@ -366,7 +369,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MVI_ATTN_WP
 // scale_log2e: what a score is multiplied by on its way into exp2 (softmax scale * log2 e; 1 for a q that carries it already)
 template <typename T>
 int attn_flash_launch(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk,
-                      float scale_log2e, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs) {
+                      float scale_log2e, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs, float* lse) {
     const int64_t hd = (int64_t)H * kFD;
     if (q_rs == 0) q_rs = hd;
     if (kv_rs == 0) kv_rs = hd;
@@ -374,22 +377,26 @@ int attn_flash_launch(const void* q, const void* k, const void* v, void* out, in
     const int q_blocks = (Sq + kFQ - 1) / kFQ;
     const int64_t total = (int64_t)B * H * q_blocks;
     if (total > 0x7FFFFFFFll) return MVI_EINVAL;
-    hipLaunchKernelGGL((attn_flash_kernel<T>), dim3((unsigned)total), dim3(256), 0, st, (const T*)q, (const T*)k,
-                       (const T*)v, (T*)out, H, Sq, Sk, scale_log2e, q_blocks, (int)total, q_rs, kv_rs, o_rs);
+    if (lse)
+        hipLaunchKernelGGL((attn_flash_kernel<T, true>), dim3((unsigned)total), dim3(256), 0, st, (const T*)q, (const T*)k,
+                           (const T*)v, (T*)out, H, Sq, Sk, scale_log2e, q_blocks, (int)total, q_rs, kv_rs, o_rs, lse);
+    else
+        hipLaunchKernelGGL((attn_flash_kernel<T, false>), dim3((unsigned)total), dim3(256), 0, st, (const T*)q, (const T*)k,
+                           (const T*)v, (T*)out, H, Sq, Sk, scale_log2e, q_blocks, (int)total, q_rs, kv_rs, o_rs, (float*)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
-template int attn_flash_launch<__hip_bfloat16>(const void*, const void*, const void*, void*, int, int, int, int, float, hipStream_t, int64_t, int64_t, int64_t);
-template int attn_flash_launch<__half>(const void*, const void*, const void*, void*, int, int, int, int, float, hipStream_t, int64_t, int64_t, int64_t);
+template int attn_flash_launch<__hip_bfloat16>(const void*, const void*, const void*, void*, int, int, int, int, float, hipStream_t, int64_t, int64_t, int64_t, float*);
+template int attn_flash_launch<__half>(const void*, const void*, const void*, void*, int, int, int, int, float, hipStream_t, int64_t, int64_t, int64_t, float*);
 
 // 8-wave kernel for long sequences (attn_flash8.hip)
 template <typename T>
 int attn_flash8_launch(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk,
-                       float scale, bool q_log2, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs);
+                       float scale, bool q_log2, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs, float* lse);
 
 // the same kernel on v_mfma_f32_16x16x32 (attn_flash8m16.hip; MVI_ATTN_MFMA16=1)
 template <typename T>
 int attn_flash8m16_launch(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk,
-                          float scale, bool q_log2, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs);
+                          float scale, bool q_log2, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs, float* lse);
 
 // rowtile kernel (attn_rowtile.hip)
 template <typename T>
@@ -421,7 +428,7 @@ extern "C" int mvi_attention_kernel_variant(int32_t Sq, int32_t Sk, int32_t D, i
 constexpr float kLn2 = 0.6931471805599453f, kLog2e = 1.4426950408889634f;
 static int attention_forward_impl(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t H, int32_t Sq,
                                   int32_t Sk, int32_t D, float scale, int32_t dtype, int64_t q_ts, int64_t kv_ts, int64_t o_ts,
-                                  void* stream, bool q_log2 = false) {
+                                  void* stream, bool q_log2 = false, float* lse = nullptr) {
     if (q_log2) scale = kLn2;
     if (B < 0 || H <= 0 || Sq < 0 || Sk <= 0 || D <= 0) return mvi::unet_fail(MVI_EINVAL, "attention: bad shape");
     if (B == 0 || Sq == 0) return MVI_OK;
@@ -438,15 +445,15 @@ static int attention_forward_impl(const void* q, const void* k, const void* v, v
     const int variant = mvi_attention_kernel_variant(Sq, Sk, D, dtype);
     if (variant != 0) {
         if (variant == 16)
-            rc = dtype == MVI_DT_BF16 ? mvi::attn_flash8m16_launch<__hip_bfloat16>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, st, q_ts, kv_ts, o_ts)
-                                      : mvi::attn_flash8m16_launch<__half>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, st, q_ts, kv_ts, o_ts);
+            rc = dtype == MVI_DT_BF16 ? mvi::attn_flash8m16_launch<__hip_bfloat16>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, st, q_ts, kv_ts, o_ts, lse)
+                                      : mvi::attn_flash8m16_launch<__half>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, st, q_ts, kv_ts, o_ts, lse);
         else if (variant == 8)
-            rc = dtype == MVI_DT_BF16 ? mvi::attn_flash8_launch<__hip_bfloat16>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, st, q_ts, kv_ts, o_ts)
-                                      : mvi::attn_flash8_launch<__half>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, st, q_ts, kv_ts, o_ts);
+            rc = dtype == MVI_DT_BF16 ? mvi::attn_flash8_launch<__hip_bfloat16>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, st, q_ts, kv_ts, o_ts, lse)
+                                      : mvi::attn_flash8_launch<__half>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, st, q_ts, kv_ts, o_ts, lse);
         else {
             const float sl2 = q_log2 ? 1.0f : scale * kLog2e;
-            rc = dtype == MVI_DT_BF16 ? mvi::attn_flash_launch<__hip_bfloat16>(q, k, v, out, B, H, Sq, Sk, sl2, st, q_ts, kv_ts, o_ts)
-                                      : mvi::attn_flash_launch<__half>(q, k, v, out, B, H, Sq, Sk, sl2, st, q_ts, kv_ts, o_ts);
+            rc = dtype == MVI_DT_BF16 ? mvi::attn_flash_launch<__hip_bfloat16>(q, k, v, out, B, H, Sq, Sk, sl2, st, q_ts, kv_ts, o_ts, lse)
+                                      : mvi::attn_flash_launch<__half>(q, k, v, out, B, H, Sq, Sk, sl2, st, q_ts, kv_ts, o_ts, lse);
         }
     } else {
         if (D != 16 && D != 32 && D != 64) return mvi::unet_fail(MVI_EINVAL, "attention: head dim must be 16, 32 or 64");
@@ -463,6 +470,16 @@ static int attention_forward_impl(const void* q, const void* k, const void* v, v
 extern "C" int mvi_attention_forward(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t H,
                                      int32_t Sq, int32_t Sk, int32_t D, float scale, int32_t dtype, void* stream) {
     return attention_forward_impl(q, k, v, out, B, H, Sq, Sk, D, scale, dtype, 0, 0, 0, stream);
+}
+
+extern "C" int mvi_attention_forward_lse(const void* q, const void* k, const void* v, void* out, void* lse, int32_t B, int32_t H,
+                                         int32_t Sq, int32_t Sk, int32_t D, float scale, int32_t dtype, void* stream) {
+    if (B < 0 || H <= 0 || Sq < 0 || Sk <= 0 || D <= 0) return mvi::unet_fail(MVI_EINVAL, "attention (lse): bad shape");
+    if (mvi_attention_kernel_kind(Sq, Sk, D, dtype) != 1 || (dtype != MVI_DT_BF16 && dtype != MVI_DT_F16))
+        return mvi::unet_fail(MVI_EINVAL, "attention (lse): bf16 / f16, head dim 64 and more than 32 keys only");
+    if (B == 0 || Sq == 0) return MVI_OK;
+    if (!lse || (uintptr_t)lse % 4 != 0) return mvi::unet_fail(MVI_EINVAL, "attention (lse): lse must be a 4-byte aligned pointer");
+    return attention_forward_impl(q, k, v, out, B, H, Sq, Sk, D, scale, dtype, 0, 0, 0, stream, false, (float*)lse);
 }
 
 extern "C" int mvi_attention_forward_strided(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t H,

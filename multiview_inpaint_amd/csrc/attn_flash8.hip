@@ -112,11 +112,12 @@ template <int N> __device__ __forceinline__ void wait_vm_then_barrier() {
 constexpr int kWaves = 8;
 constexpr int kLoaders = 4;
 
-template <typename T, bool kExact>
+// kLse: as in attn_flash.hip — the row's log-sum-exp beside an `out` computed by the same instructions
+template <typename T, bool kExact, bool kLse = false>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void attn_flash8_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ out,
                         int H, int Sq, int Sk, float scale_log2e, int q_blocks, int total_blocks, int64_t q_rs,
-                        int64_t kv_rs, int64_t o_rs) {
+                        int64_t kv_rs, int64_t o_rs, float* __restrict__ lse) {
     using M = Mma<T>;
     using frag = typename M::frag;
     constexpr int kQB = 32 * kWaves;             // query rows per block
@@ -470,6 +471,8 @@ void attn_flash8_kernel(const T* __restrict__ q, const T* __restrict__ k, const 
         run(std::true_type{});
     }
 
+    // negm holds minus the reference exponent in the units of the accumulators (sc_mul apart from log2 units)
+    if (kLse && qrow < Sq && hh == 0) lse[(b * H + h) * Sq + qrow] = (__builtin_amdgcn_logf(l) - negm[0] * sc_mul) * 0.6931471805599453f;
     if (qrow < Sq) {
         const float inv = 1.0f / l;
         T* op = out + ((b * Sq + qrow) * o_rs + (int64_t)h * kD);
@@ -488,7 +491,7 @@ void attn_flash8_kernel(const T* __restrict__ q, const T* __restrict__ k, const 
 
 template <typename T>
 static int flash8_launch(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk, float scale, bool q_log2,
-                         hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs) {
+                         hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs, float* lse) {
     using namespace f8;
     constexpr int kQB = 32 * kWaves;
     const int q_blocks = (Sq + kQB - 1) / kQB;
@@ -506,29 +509,29 @@ static int flash8_launch(const void* q, const void* k, const void* v, void* out,
     // nothing left to fold (its prologue multiplies Q by exactly 1), for both types
     const bool fold = q_log2 || (fold_env >= 0 ? fold_env != 0 : std::is_same<T, __half>::value);
     if (!((attr_set >> dev) & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_flash8_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsBytes + 16) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_flash8_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsBytes + 16) != hipSuccess)
-            return MVI_EHIP;
+        const void* all[4] = {reinterpret_cast<const void*>(&attn_flash8_kernel<T, true>), reinterpret_cast<const void*>(&attn_flash8_kernel<T, false>),
+                              reinterpret_cast<const void*>(&attn_flash8_kernel<T, true, true>), reinterpret_cast<const void*>(&attn_flash8_kernel<T, false, true>)};
+        for (const void* f : all)
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + 16) != hipSuccess) return MVI_EHIP;
         attr_set |= 1ull << dev;
     }
-    auto kern = fold ? &attn_flash8_kernel<T, false> : &attn_flash8_kernel<T, true>;
+    auto kern = lse ? (fold ? &attn_flash8_kernel<T, false, true> : &attn_flash8_kernel<T, true, true>)
+                    : (fold ? &attn_flash8_kernel<T, false> : &attn_flash8_kernel<T, true>);
     hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(64 * kWaves), kLdsBytes + 16, st, (const T*)q, (const T*)k, (const T*)v,
-                       (T*)out, H, Sq, Sk, q_log2 ? 1.0f : scale * 1.4426950408889634f, q_blocks, (int)total, q_rs, kv_rs, o_rs);
+                       (T*)out, H, Sq, Sk, q_log2 ? 1.0f : scale * 1.4426950408889634f, q_blocks, (int)total, q_rs, kv_rs, o_rs, lse);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 
 template <typename T>
 int attn_flash8_launch(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk,
-                       float scale, bool q_log2, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs) {
+                       float scale, bool q_log2, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs, float* lse) {
     const int64_t hd = (int64_t)H * f8::kD;
     if (q_rs == 0) q_rs = hd;
     if (kv_rs == 0) kv_rs = hd;
     if (o_rs == 0) o_rs = hd;
-    return flash8_launch<T>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, st, q_rs, kv_rs, o_rs);
+    return flash8_launch<T>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, st, q_rs, kv_rs, o_rs, lse);
 }
-template int attn_flash8_launch<__hip_bfloat16>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, hipStream_t, int64_t, int64_t, int64_t);
-template int attn_flash8_launch<__half>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, hipStream_t, int64_t, int64_t, int64_t);
+template int attn_flash8_launch<__hip_bfloat16>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, hipStream_t, int64_t, int64_t, int64_t, float*);
+template int attn_flash8_launch<__half>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, hipStream_t, int64_t, int64_t, int64_t, float*);
 
 }  // namespace mvi

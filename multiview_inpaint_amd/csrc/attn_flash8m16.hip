@@ -113,11 +113,12 @@ struct Scores { f32x4 t[2][2]; };
 // kOnes: the softmax row sums come out of the matrix pipe instead of the VALU — a fifth "d tile" whose V^T fragment is a row of ones
 // (two more MFMAs per 32-key block, +1/8 of the matrix work) replaces the 32 v_add_f32 per wave and tile on the issue port that bounds
 // this kernel; the sums are then those of the ROUNDED probabilities, i.e. of exactly the numerators the P V products use.
-template <typename T, bool kExact, bool kOnes>
+// kLse: as in attn_flash.hip — the row's log-sum-exp beside an `out` computed by the same instructions
+template <typename T, bool kExact, bool kOnes, bool kLse = false>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ out,
                            int H, int Sq, int Sk, float scale_log2e, int q_blocks, int total_blocks, int64_t q_rs,
-                           int64_t kv_rs, int64_t o_rs) {
+                           int64_t kv_rs, int64_t o_rs, float* __restrict__ lse) {
     using M = Mma<T>;
     using frag = typename M::frag;
     constexpr int kQB = 32 * kWaves;             // query rows per block
@@ -220,6 +221,7 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
     const u32x4 ones = c16 == 0 ? u32x4{one2, one2, one2, one2} : u32x4{0, 0, 0, 0};     // A operand: V^T row 0 = 1 for every key
     Scores s0, s1;                           // scores of key block 0 / 1 of a tile: FIXED roles
     float l[2], rsum[2];
+    float l_exact[2] = {0.f, 0.f};           // kLse only
 
     // all of S' of one 32-key block (prologue only)
     auto qk_block = [&](int slot, int kb, Scores& sc) __attribute__((always_inline)) {
@@ -293,10 +295,10 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
                 const float x1 = kExact ? sc.t[kt][qt][2 * i + 1] * sc_mul : sc.t[kt][qt][2 * i + 1];
                 const float p0 = __builtin_amdgcn_exp2f(x0);
                 const float p1 = __builtin_amdgcn_exp2f(x1);
-                if (!kOnes) rsum[qt] += p0 + p1;
+                if (!kOnes || kLse) rsum[qt] += p0 + p1;
                 pr[2 * kt + i] = M::pack2(p0, p1);
             }
-        if (!kOnes) asm volatile("" : "+v"(rsum[qt]));   // (as in attn_flash8.hip: the sum is complete here)
+        if (!kOnes || kLse) asm volatile("" : "+v"(rsum[qt]));   // (as in attn_flash8.hip: the sum is complete here)
         return pr;
     };
     // The matrix work beside one quarter: the S' MFMAs of key tile kt of the OTHER block (into acc.t[kt][*]) and the four P V MFMAs
@@ -419,7 +421,13 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // trailing (unused) pieces must land before the ring is reused / released
 #pragma unroll
-        for (int qt = 0; qt < 2; ++qt) l[qt] = group_sum(kOnes ? lacc[qt][0] : l[qt] + rsum[qt]);   // the four lane groups hold disjoint keys (kOnes: the sum sits in group 0, zeros elsewhere)
+        for (int qt = 0; qt < 2; ++qt) {
+            // kLse with kOnes: `out` is normalised by the sum of the ROUNDED probabilities as always; the row statistic handed to the
+            // backward is the sum of the unrounded ones (the backward recomputes P in fp32), kept on the VALU beside it
+            if (kLse && kOnes) l_exact[qt] = group_sum(l[qt] + rsum[qt]);
+            l[qt] = group_sum(kOnes ? lacc[qt][0] : l[qt] + rsum[qt]);   // the four lane groups hold disjoint keys (kOnes: the sum sits in group 0, zeros elsewhere)
+            if (kLse && !kOnes) l_exact[qt] = l[qt];
+        }
     };
 
     MVI_AS3 uint32_t* const redo_flag = (MVI_AS3 uint32_t*)(lds + kLdsBytes);
@@ -442,6 +450,8 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
         const int qrow = qrow0 + 16 * qt;
+        // negm holds minus the reference exponent in the units of the accumulators (sc_mul apart from log2 units)
+        if (kLse && qrow < Sq && g == 0) lse[(b * H + h) * Sq + qrow] = (__builtin_amdgcn_logf(l_exact[qt]) - negm[qt][0] * sc_mul) * 0.6931471805599453f;
         if (qrow < Sq) {
             const float inv = 1.0f / l[qt];
             T* op = out + ((b * Sq + qrow) * o_rs + (int64_t)h * kD + 4 * g);
@@ -458,7 +468,7 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
 
 template <typename T>
 int attn_flash8m16_launch(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk,
-                          float scale, bool q_log2, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs) {
+                          float scale, bool q_log2, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs, float* lse) {
     using namespace f8m;
     const int64_t hd = (int64_t)H * kD;
     if (q_rs == 0) q_rs = hd;
@@ -477,19 +487,23 @@ int attn_flash8m16_launch(const void* q, const void* k, const void* v, void* out
     static const int mode = getenv("MVI_ATTN_MFMA16") ? atoi(getenv("MVI_ATTN_MFMA16")) : 2;          // 1: row sums on the VALU (A/B), otherwise on the matrix pipe
     const bool ones = mode != 1;
     if (!((attr_set >> dev) & 1ull)) {
-        const void* all[4] = {reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, false>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, false>),
-                              reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, true>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, true>)};
+        const void* all[8] = {reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, false>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, false>),
+                              reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, true>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, true>),
+                              reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, false, true>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, false, true>),
+                              reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, true, true>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, true, true>)};
         for (const void* f : all)
             if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + 16) != hipSuccess) return MVI_EHIP;
         attr_set |= 1ull << dev;
     }
-    auto kern = ones ? (fold ? &attn_flash8m16_kernel<T, false, true> : &attn_flash8m16_kernel<T, true, true>)
-                     : (fold ? &attn_flash8m16_kernel<T, false, false> : &attn_flash8m16_kernel<T, true, false>);
+    auto kern = lse ? (ones ? (fold ? &attn_flash8m16_kernel<T, false, true, true> : &attn_flash8m16_kernel<T, true, true, true>)
+                            : (fold ? &attn_flash8m16_kernel<T, false, false, true> : &attn_flash8m16_kernel<T, true, false, true>))
+                    : (ones ? (fold ? &attn_flash8m16_kernel<T, false, true> : &attn_flash8m16_kernel<T, true, true>)
+                            : (fold ? &attn_flash8m16_kernel<T, false, false> : &attn_flash8m16_kernel<T, true, false>));
     hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(64 * kWaves), kLdsBytes + 16, st, (const T*)q, (const T*)k, (const T*)v,
-                       (T*)out, H, Sq, Sk, q_log2 ? 1.0f : scale * 1.4426950408889634f, q_blocks, (int)total, q_rs, kv_rs, o_rs);
+                       (T*)out, H, Sq, Sk, q_log2 ? 1.0f : scale * 1.4426950408889634f, q_blocks, (int)total, q_rs, kv_rs, o_rs, lse);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
-template int attn_flash8m16_launch<__hip_bfloat16>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, hipStream_t, int64_t, int64_t, int64_t);
-template int attn_flash8m16_launch<__half>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, hipStream_t, int64_t, int64_t, int64_t);
+template int attn_flash8m16_launch<__hip_bfloat16>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, hipStream_t, int64_t, int64_t, int64_t, float*);
+template int attn_flash8m16_launch<__half>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, hipStream_t, int64_t, int64_t, int64_t, float*);
 
 }  // namespace mvi

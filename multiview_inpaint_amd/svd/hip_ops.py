@@ -304,6 +304,88 @@ def attention_temporal(q, k, v, heads, T):
     return out
 
 
+def attention_backward_supported(Sq, Sk, D, dtype):
+    """Whether attention_forward_lse / attention_backward compute this shape (mvi_attention_backward_supported, a host-only function:
+    bf16 / f16, D = 64, Sk > 32 — the domain of the MFMA forward kernels)."""
+    return dtype in _DT and bool(_lib.lib().mvi_attention_backward_supported(int(Sq), int(Sk), int(D), _DT[dtype]))
+
+
+def _check_qkv(what, q, k, v):
+    if q.dtype not in _DT or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"{what}: q/k/v must share a dtype in {list(_DT)} (got {q.dtype}, {k.dtype}, {v.dtype})")
+    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
+        raise ValueError(f"{what}: q [B,Sq,H*D], k/v [B,Sk,H*D] expected (got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)})")
+
+
+def attention_forward_lse(q, k, v, heads):
+    """attention(q, k, v, heads) — the same kernel, bit-identical output — plus the fp32 log-sum-exp of the scaled scores
+    [B, H, Sq] that attention_backward needs. Returns (out, lse)."""
+    L = _lib.lib()
+    _check_qkv("attention_forward_lse", q, k, v)
+    B, Sq, HD = q.shape
+    Sk = k.shape[1]
+    D = HD // heads
+    q, k, v = (t if t.is_contiguous() else t.contiguous() for t in (q, k, v))
+    out = torch.empty_like(q)
+    lse = torch.empty(B, heads, Sq, dtype=torch.float32, device=q.device)
+    if ATTN_VARIANTS is not None:
+        ATTN_VARIANTS.append((int(L.mvi_attention_kernel_variant(Sq, Sk, D, _DT[q.dtype])), Sq, Sk))
+    with torch.cuda.device(q.device), _Timed("attention_mfma_lse", 4.0 * B * heads * Sq * Sk * D, q.device):
+        _check(L.mvi_attention_forward_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), B, heads, Sq, Sk, D,
+                                           float(D) ** -0.5, _DT[q.dtype], _stream(q.device)), "attention_forward_lse")
+    return out, lse
+
+
+def attention_backward(q, k, v, out, dout, lse, heads, need_dq=True, need_dkv=True):
+    """(dq, dk, dv) of out = attention(q, k, v, heads) for the upstream gradient dout; out and lse from attention_forward_lse.
+    Deterministic (no atomics). need_dkv False skips the dK/dV kernel; need_dq False skips dq's stores (the dQ kernel also produces
+    the delta the dK/dV kernel uses, so dk and dv are the same bits either way). None is returned in place of what was not asked for."""
+    L = _lib.lib()
+    _check_qkv("attention_backward", q, k, v)
+    B, Sq, HD = q.shape
+    Sk = k.shape[1]
+    D = HD // heads
+    if out.shape != q.shape or dout.shape != q.shape or out.dtype != q.dtype or dout.dtype != q.dtype:
+        raise ValueError("attention_backward: out and dout must have q's shape and dtype")
+    if tuple(lse.shape) != (B, heads, Sq) or lse.dtype != torch.float32:
+        raise ValueError(f"attention_backward: lse must be fp32 [B, H, Sq] = {(B, heads, Sq)}")
+    q, k, v, out, dout, lse = (t if t.is_contiguous() else t.contiguous() for t in (q, k, v, out, dout, lse))
+    dq = torch.empty_like(q) if need_dq else None
+    dk = torch.empty_like(k) if need_dkv else None
+    dv = torch.empty_like(v) if need_dkv else None
+    if not (need_dq or need_dkv):
+        return None, None, None
+    nbytes = int(L.mvi_attention_backward_workspace_bytes(B, heads, Sq, Sk, D, _DT[q.dtype]))
+    ws = _workspace(q.device, nbytes)
+    # algorithmic FLOPs: five Sq x Sk x D products (S, dP, dV, dK, dQ); the two kernels execute seven (S and dP twice)
+    work = 2.0 * B * heads * Sq * Sk * D * (5 if need_dq and need_dkv else 3 if need_dq else 4)
+    with torch.cuda.device(q.device), _Timed("attention_mfma_bwd", work, q.device):
+        _check(L.mvi_attention_backward(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+                                        dq.data_ptr() if need_dq else None, dk.data_ptr() if need_dkv else None,
+                                        dv.data_ptr() if need_dkv else None, B, heads, Sq, Sk, D, float(D) ** -0.5, _DT[q.dtype],
+                                        ws.data_ptr(), ws.numel(), _stream(q.device)), "attention_backward")
+    return dq, dk, dv
+
+
+def attention_temporal_backward(q, k, v, dout, heads, T):
+    """(dq, dk, dv) of attention_temporal(q, k, v, heads, T): q/k/v/dout [(bo*T), S, H*D], nothing regrouped."""
+    L = _lib.lib()
+    _check_qkv("attention_temporal_backward", q, k, v)
+    if k.shape != q.shape or dout.shape != q.shape or dout.dtype != q.dtype:
+        raise ValueError("attention_temporal_backward: q, k, v and dout must share shape and dtype")
+    BT, S, HD = q.shape
+    if BT % T:
+        raise ValueError(f"attention_temporal_backward: {BT} rows are not a multiple of T = {T}")
+    D = HD // heads
+    q, k, v, dout = (t if t.is_contiguous() else t.contiguous() for t in (q, k, v, dout))
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+    with torch.cuda.device(q.device), _Timed("attention_temporal_bwd", 7.0 * BT * S * HD * q.element_size(), q.device):
+        _check(L.mvi_attention_temporal_backward(q.data_ptr(), k.data_ptr(), v.data_ptr(), dout.data_ptr(), dq.data_ptr(), dk.data_ptr(),
+                                                 dv.data_ptr(), BT // T, T, S, heads, D, float(D) ** -0.5, _DT[q.dtype],
+                                                 _stream(q.device)), "attention_temporal_backward")
+    return dq, dk, dv
+
+
 def geglu(h):
     L = _lib.lib()
     if h.dtype not in _DT:

@@ -4,8 +4,10 @@ PyTorch substitute on the GPU inference path. On a CPU tensor they are plain PyT
 BASELINE.json configs[0] ("sgm VideoUNet single denoise step ... fp32 on CPU PyTorch"), the
 reference's own CPU-runnable case, not a fallback for the GPU.
 
-The HIP kernels are forward-only. Under autograd (ControlNet training — SURVEY.md §2 row 21, out of
-scope) a GPU tensor that requires grad goes through PyTorch-ROCm's differentiable ops instead.
+Under autograd (ControlNet training — SURVEY.md §2 row 21) attention stays on the HIP path, forward and backward
+(csrc/attn_bwd.hip: `attention` for bf16 / f16 with D = 64 and more than 32 keys, `attention_temporal` for every shape its
+forward takes). Every other kernel is forward-only: a GPU tensor that requires grad goes through PyTorch-ROCm's
+differentiable ops there (GroupNorm, GEGLU, the projections and convolutions).
 
 Reference ops: GroupNorm32 + SiLU (sgm/modules/diffusionmodules/util.py:259-276,
 openaimodel.py:257-261,292-305), Normalize (sgm/modules/attention.py:125-128),
@@ -17,7 +19,8 @@ import torch
 import torch.nn.functional as F
 
 # A GPU tensor leaves the HIP path for one of two reasons, treated differently:
-#   * it requires grad (ControlNet training, out of scope): PyTorch-ROCm's differentiable ops run — the documented path;
+#   * it requires grad and the op has no HIP backward (everything but attention): PyTorch-ROCm's differentiable ops run — the
+#     documented path;
 #   * a shape / contiguity gate of a kernel fails under no_grad: that RAISES by default (STRICT_GATES; since round 3) — an
 #     inference call never silently runs PyTorch ops in place of the kernels. MVI_STRICT=0 allows the substitute again
 #     (recorded in FALLBACKS).
@@ -125,6 +128,73 @@ def group_norm_frames(x, T, num_groups, weight, bias, eps, silu=False, chan_bias
     return _stack3(y, T) if stack3 else y
 
 
+# The HIP backward of attention (csrc/attn_bwd.hip). MVI_ATTN_BWD=0 (or ops.ATTENTION_BACKWARD = False): attention under autograd
+# takes PyTorch-ROCm's scaled_dot_product_attention again, as every other op does.
+ATTENTION_BACKWARD = os.environ.get("MVI_ATTN_BWD", "1") != "0"
+
+
+def attention_backward_pays(B, Sq, Sk, heads, dtype):
+    """Whether forward + backward on the HIP kernels is at least as fast as the PyTorch-ROCm route for this shape class — the
+    routing's second question after hip_ops.attention_backward_supported (what the kernels compute correctly). Set from
+    tools/bench_attention_bwd.py (profiles/attention_bwd_bench.json; DESIGN.md 'Attention under autograd'): at B = 14 the route wins
+    at (H, S) = (5, 9216), (5, 3072), (10, 768) — 7.6 / 1.04 / 0.29 ms against 13.0 / 1.72 / 0.36 in bf16 — and loses in bf16 at
+    (20, 192) and (20, 48) — 0.230 / 0.228 ms against 0.189 / 0.184 — where the kernels take 0.08 / 0.05 ms and both routes are
+    bound by their host side. The line is drawn in score elements between the two groups (82.6 M and 10.3 M)."""
+    return B * heads * Sq * Sk >= ATTENTION_BACKWARD_MIN_SCORES
+
+
+ATTENTION_BACKWARD_MIN_SCORES = 1 << 25
+
+
+class _AttentionFn(torch.autograd.Function):
+    """softmax(q k^T D^-1/2) v on the MFMA kernels with a deterministic HIP backward. Holds q, k, v, out and the row log-sum-exp;
+    nothing is cached outside ctx, so torch.utils.checkpoint may re-run the forward."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads):
+        from . import hip_ops
+        out, lse = hip_ops.attention_forward_lse(q, k, v, heads)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        from . import hip_ops
+        q, k, v, out, lse = ctx.saved_tensors
+        need_dq = ctx.needs_input_grad[0]
+        need_dkv = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dq, dk, dv = hip_ops.attention_backward(q, k, v, out, dout.contiguous(), lse, ctx.heads, need_dq=need_dq, need_dkv=need_dkv)
+        return (dq if need_dq else None, dk if ctx.needs_input_grad[1] else None, dv if ctx.needs_input_grad[2] else None, None)
+
+
+class _AttentionTemporalFn(torch.autograd.Function):
+    """attention_temporal with its HIP backward (the softmax over T <= 16 frames is recomputed: only q, k, v are held)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, T):
+        from . import hip_ops
+        ctx.save_for_backward(q, k, v)
+        ctx.heads, ctx.T = heads, T
+        return hip_ops.attention_temporal(q, k, v, heads, T)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        from . import hip_ops
+        q, k, v = ctx.saved_tensors
+        dq, dk, dv = hip_ops.attention_temporal_backward(q, k, v, dout.contiguous(), ctx.heads, ctx.T)
+        n = ctx.needs_input_grad
+        return (dq if n[0] else None, dk if n[1] else None, dv if n[2] else None, None, None)
+
+
+def _temporal_backward_supported(q, k, v, heads, T):
+    D = q.shape[-1] // max(heads, 1)
+    return (q.dtype in (torch.float32, torch.bfloat16, torch.float16) and k.dtype == q.dtype and v.dtype == q.dtype
+            and q.shape == k.shape == v.shape and D in (16, 32, 64) and D * heads == q.shape[-1] and 0 < T <= 16 and q.shape[0] % T == 0)
+
+
 def attention(q, k, v, heads):
     """q [B,Sq,H*D], k/v [B,Sk,H*D] token-major as the Linear layers produce them -> [B,Sq,H*D]."""
     B, Sq, HD = q.shape
@@ -132,6 +202,10 @@ def attention(q, k, v, heads):
     if q.is_cuda and not _needs_autograd(q, k, v):
         from . import hip_ops
         return hip_ops.attention(q, k, v, heads)
+    if q.is_cuda and ATTENTION_BACKWARD and k.dtype == q.dtype and v.dtype == q.dtype and HD % heads == 0:
+        from . import hip_ops
+        if hip_ops.attention_backward_supported(Sq, Sk, HD // heads, q.dtype) and attention_backward_pays(B, Sq, Sk, heads, q.dtype):
+            return _AttentionFn.apply(q, k, v, heads)
     _fallback(q, "attention", _why(q, k, v))
     D = HD // heads
     qh, kh, vh = (t.reshape(B, -1, heads, D).transpose(1, 2) for t in (q, k, v))
@@ -205,6 +279,8 @@ def attention_temporal(q, k, v, heads, T):
     if q.is_cuda and not _needs_autograd(q, k, v):
         from . import hip_ops
         return hip_ops.attention_temporal(q, k, v, heads, T)
+    if q.is_cuda and ATTENTION_BACKWARD and _temporal_backward_supported(q, k, v, heads, T):
+        return _AttentionTemporalFn.apply(q, k, v, heads, T)
     _fallback(q, "attention_temporal", _why(q, k, v))
     bo = BT // T
 
