@@ -76,6 +76,39 @@ int mvi_groupnorm_silu_tokens(const void* x, void* y, const float* weight, const
                               int64_t N, int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu,
                               int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Differentiable GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip): the forward and backward of GroupNorm32 -> SiLU for training through the
+ * ResBlocks of the reference (openaimodel.py:341-353 with `h + emb_out` in front, video_model.py:71-75 with dims = 3, attention.py:125-128
+ * for Normalize without SiLU). Domain: that of mvi_groupnorm_silu_ex (fp32 / bf16 / f16; plain and temporal form; with or without
+ * chan_bias and SiLU; the 16-byte vector path and the scalar path for odd `spatial` or unaligned bases; any eps).
+ *
+ * mvi_groupnorm_backward_supported: pure host function, 1 where the entries below compute (the Python gate reads it). It cannot see
+ *     pointers: the token-major layout also needs x, dy and dx 16-byte aligned (MVI_EINVAL otherwise; the caller checks); the other
+ *     layouts take the scalar path for unaligned bases.
+ * mvi_groupnorm_forward_stats: the forward — mvi_groupnorm_silu_ex2 for out_layout MVI_GN_DY_PLANES / MVI_GN_DY_STACK3,
+ *     mvi_groupnorm_silu_tokens for MVI_GN_DY_TOKENS (sync may be NULL there): the same kernels, same instructions, `y` bit-identical —
+ *     that also writes stats [videos * groups, 2] fp32 = (mean, rstd) of every (video, group).
+ * mvi_groupnorm_backward: from x, chan_bias, weight, bias as the forward took them, stats, and dy in the layout the forward wrote y in
+ *     (planes [rows, C, spatial]; stack3 [rows, 3 C, spatial] — the gradient of frame t is block 1 of row t + block 0 of row t + 1 +
+ *     block 2 of row t - 1, missing neighbours at the ends of a video being zero; token-major [rows, spatial, C], which needs T == 1 and
+ *     C, spatial multiples of the 16-byte vector), read in place: dx [rows, C, spatial] in the I/O type, dweight, dbias [C] and
+ *     dchan_bias [rows, C] in fp32. Every output is nullable; dweight / dbias cost one small launch, dchan_bias none, dx one pass over x
+ *     and dy. All math in fp32, one rounding on the way out. Deterministic: no atomics, two runs give the same bits.
+ *     workspace: mvi_groupnorm_backward_workspace_bytes(...) bytes, 4-byte aligned. */
+#define MVI_GN_DY_PLANES 0
+#define MVI_GN_DY_STACK3 1
+#define MVI_GN_DY_TOKENS 2
+int mvi_groupnorm_backward_supported(int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, int32_t dy_layout,
+                                     int32_t dtype);
+int mvi_groupnorm_forward_stats(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias, float* stats,
+                                int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu,
+                                int32_t out_layout, int32_t dtype, void* workspace, size_t workspace_bytes, void* sync,
+                                size_t sync_bytes, void* stream);
+size_t mvi_groupnorm_backward_workspace_bytes(int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups);
+int mvi_groupnorm_backward(const void* x, const void* dy, const float* stats, const float* weight, const float* bias,
+                           const float* chan_bias, void* dx, float* dweight, float* dbias, float* dchan_bias, int64_t videos, int32_t T,
+                           int32_t C, int64_t spatial, int32_t groups, int32_t fuse_silu, int32_t dy_layout, int32_t dtype,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* GroupNorm(+SiLU) with TOKEN-MAJOR input and output: x, y [N, spatial, C] (C contiguous = NHWC). The norm between the two
  * 3x3 convolutions of a ResBlock (openaimodel.py:292-305, :341-352) when the convolutions run on channels-last tensors —
  * MIOpen's kernels are NHWC and wrap NCHW tensors in transposes (csrc/groupnorm_tokens.hip). chan_bias: optional fp32 [N, C]

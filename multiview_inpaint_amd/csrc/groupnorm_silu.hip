@@ -58,6 +58,7 @@ struct GnGeom {
     int stack3;               // temporal form only: write y three times into [(videos T), 3C, S] — at channel
                               // offset C of its own frame, offset 0 of the next frame and offset 2C of the previous
                               // one (zeros at the sequence ends): the input of the (3,1,1) convolution as a 1x1
+    float* stats;             // kStats instantiations only: (mean, rstd) per (video, group) [N * G, 2], what the backward takes
 };
 __device__ __forceinline__ int64_t gn_slice_base(const GnGeom& q, int64_t g, int slice) {
     const int64_t n = g / q.G, gi = g % q.G;
@@ -156,7 +157,9 @@ __global__ __launch_bounds__(kGnBlock) void gn_stats_kernel(const T* __restrict_
     }
 }
 
-template <typename T, bool VEC>
+// kStats (here and in the kernels below): the forward under autograd — the same instructions, plus one store of (mean, rstd) per
+// group to q.stats; inference launches the kStats = false instantiations
+template <typename T, bool VEC, bool kStats = false>
 __global__ __launch_bounds__(kGnBlock) void gn_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                             const float* __restrict__ weight,
                                                             const float* __restrict__ bias,
@@ -190,7 +193,10 @@ __global__ __launch_bounds__(kGnBlock) void gn_apply_kernel(const T* __restrict_
             }
             n = nt;
         }
-        if (threadIdx.x == 0) { s_stat[0] = mean; s_stat[1] = rsqrtf(m2 / n + eps); }
+        if (threadIdx.x == 0) {
+            s_stat[0] = mean; s_stat[1] = rsqrtf(m2 / n + eps);
+            if (kStats && blockIdx.x == 0) { q.stats[2 * g] = s_stat[0]; q.stats[2 * g + 1] = s_stat[1]; }
+        }
     }
     __syncthreads();
     const float mean = s_stat[0], rstd = s_stat[1];
@@ -286,7 +292,7 @@ constexpr int kGnTokS = 128;                              // positions per tile
 // The tile sits in LDS in the OUTPUT type (the rounding of the final store, done before the transpose instead of after it:
 // same values) — 17 KB for bf16 / f16 instead of 33 KB of floats, so the 8 blocks a CU's wave slots allow are resident and a
 // thread has four 16-byte loads in flight instead of two (the 64 x 64 float tile ran at 4.2 TB/s of read + write).
-template <typename T>
+template <typename T, bool kStats = false>
 __global__ __launch_bounds__(256) void gn_apply_tokens_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                               const float* __restrict__ weight,
                                                               const float* __restrict__ bias,
@@ -330,6 +336,7 @@ __global__ __launch_bounds__(256) void gn_apply_tokens_kernel(const T* __restric
                 }
             }
             const float rstd = rsqrtf(m2 / cnt + eps);
+            if (kStats && stile == 0 && c % q.Cg == 0) { q.stats[2 * g] = mean; q.stats[2 * g + 1] = rstd; }   // every channel of a group merges the same values
             const float add = q.chan_bias ? q.chan_bias[n * C + c] : 0.f;
             const float w = weight[c] * rstd;
             s_sc[threadIdx.x] = w;
@@ -379,12 +386,12 @@ __global__ __launch_bounds__(256) void gn_apply_tokens_kernel(const T* __restric
 // through it) and reached 0.39 of the HBM peak in the 14 x 576x1024 step; a group of that step is 11 KB ... 368 KB,
 // against 512 KB of vector registers per CU. Groups that do not fit (more than 256 KB in bf16 / f16, 192 KB in fp32), the temporal form and the token-major /
 // stacked outputs keep the two-launch kernels.
-template <typename T, int NV, int kGnResBlock>
+template <typename T, int NV, int kGnResBlock, bool kStats = false>
 __global__ __launch_bounds__(kGnResBlock) void gn_resident_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                                   const float* __restrict__ weight,
                                                                   const float* __restrict__ bias,
                                                                   const float* __restrict__ chan_bias, int Cg, int G,
-                                                                  int64_t S, float eps, int silu) {
+                                                                  int64_t S, float eps, int silu, float* __restrict__ stats) {
     constexpr int KV = Io<T>::kVec;
     __shared__ float s_red[kGnResBlock / 64];
     const int64_t g = blockIdx.x;
@@ -448,6 +455,7 @@ __global__ __launch_bounds__(kGnResBlock) void gn_resident_kernel(const T* __res
         m2 += vi < nvec ? part : 0.f;
     }
     const float rstd = rsqrtf(block_total(m2) / (float)E + eps);
+    if (kStats && threadIdx.x == 0) { stats[2 * g] = mean; stats[2 * g + 1] = rstd; }
 #pragma unroll
     for (int i = 0; i < NV; ++i) asm volatile("" : "+v"(r[i].x), "+v"(r[i].y), "+v"(r[i].z), "+v"(r[i].w));
 #pragma unroll
@@ -474,13 +482,17 @@ __global__ __launch_bounds__(kGnResBlock) void gn_resident_kernel(const T* __res
 // against 115 for the two-launch form)
 template <typename T, int BS>
 static int gn_resident_launch_bs(const void* x, void* y, const float* w, const float* b, const float* chan_bias, int64_t N, int C,
-                                 int64_t S, int G, float eps, int silu, hipStream_t st, int nv) {
+                                 int64_t S, int G, float eps, int silu, hipStream_t st, int nv, float* stats) {
     const int Cg = C / G;
     const int64_t blocks = N * G;
 #define MVI_GN_RES(NVV)                                                                                                          \
     case NVV:                                                                                                                    \
-        hipLaunchKernelGGL((gn_resident_kernel<T, NVV, BS>), dim3((unsigned)blocks), dim3(BS), 0, st, (const T*)x, (T*)y, w, b, chan_bias, \
-                           Cg, G, S, eps, silu);                                                                                  \
+        if (stats)                                                                                                               \
+            hipLaunchKernelGGL((gn_resident_kernel<T, NVV, BS, true>), dim3((unsigned)blocks), dim3(BS), 0, st, (const T*)x, (T*)y, w, b, \
+                               chan_bias, Cg, G, S, eps, silu, stats);                                                            \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((gn_resident_kernel<T, NVV, BS>), dim3((unsigned)blocks), dim3(BS), 0, st, (const T*)x, (T*)y, w, b, \
+                               chan_bias, Cg, G, S, eps, silu, stats);                                                            \
         break;
     switch (nv) {
         MVI_GN_RES(2) MVI_GN_RES(4) MVI_GN_RES(8) MVI_GN_RES(12)
@@ -491,7 +503,7 @@ static int gn_resident_launch_bs(const void* x, void* y, const float* w, const f
 }
 template <typename T>
 static int gn_resident_launch(const void* x, void* y, const float* w, const float* b, const float* chan_bias, int64_t N, int C,
-                              int64_t S, int G, float eps, int silu, hipStream_t st) {
+                              int64_t S, int G, float eps, int silu, hipStream_t st, float* stats) {
     constexpr int KV = Io<T>::kVec;
     const int64_t nvec = (int64_t)(C / G) * S / KV;
     if (N * G > 0x7FFFFFFFll || nvec >= (1 << 21)) return 1;      // caller falls back to the two-launch form
@@ -500,8 +512,8 @@ static int gn_resident_launch(const void* x, void* y, const float* w, const floa
         const int64_t need = (nvec + bs - 1) / bs;
         for (int o : opts)
             if (need <= o)
-                return bs == 512 ? gn_resident_launch_bs<T, 512>(x, y, w, b, chan_bias, N, C, S, G, eps, silu, st, o)
-                                 : gn_resident_launch_bs<T, 1024>(x, y, w, b, chan_bias, N, C, S, G, eps, silu, st, o);
+                return bs == 512 ? gn_resident_launch_bs<T, 512>(x, y, w, b, chan_bias, N, C, S, G, eps, silu, st, o, stats)
+                                 : gn_resident_launch_bs<T, 1024>(x, y, w, b, chan_bias, N, C, S, G, eps, silu, st, o, stats);
     }
     return 1;                                                      // more than 12 vectors per thread of a 1024-thread block
 }
@@ -531,7 +543,7 @@ constexpr int kGnClusterBlock = 512;
 constexpr int kGnSyncGroups = 65536;
 constexpr uint32_t kGnSpinLimit = 1u << 22;
 
-template <typename T, int NV>
+template <typename T, int NV, bool kStats = false>
 __global__ __launch_bounds__(kGnClusterBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void gn_cluster_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                                      const float* __restrict__ weight,
                                                                      const float* __restrict__ bias, GnGeom q, int kps, int vpb,
@@ -639,7 +651,10 @@ __global__ __launch_bounds__(kGnClusterBlock) __attribute__((amdgpu_waves_per_eu
             M2 += qb + d * d * (n * nb / nt);
             n = nt;
         }
-        if (threadIdx.x == 0) { s_stat[0] = mean; s_stat[1] = rsqrtf(M2 / n + eps); }
+        if (threadIdx.x == 0) {
+            s_stat[0] = mean; s_stat[1] = rsqrtf(M2 / n + eps);
+            if (kStats && j == 0) { q.stats[2 * g] = s_stat[0]; q.stats[2 * g + 1] = s_stat[1]; }
+        }
     }
     __syncthreads();
     const float mean = s_stat[0], rstd = s_stat[1];
@@ -724,8 +739,14 @@ static int gn_cluster_launch(const void* x, void* y, const float* w, const float
     const int need = (vpb + BS - 1) / BS;
     const unsigned blocks = (unsigned)(groups * K);                       // exactly the tickets 0 .. groups * K - 1
 #define MVI_GN_CL(NVV)                                                                                                        \
-    hipLaunchKernelGGL((gn_cluster_kernel<T, NVV>), dim3(blocks), dim3(BS), 0, st, (const T*)x, (T*)y, w, b, q, kps, vpb, eps, silu, \
-                       part, sync, groups)
+    do {                                                                                                                      \
+        if (q.stats)                                                                                                          \
+            hipLaunchKernelGGL((gn_cluster_kernel<T, NVV, true>), dim3(blocks), dim3(BS), 0, st, (const T*)x, (T*)y, w, b, q, kps, vpb, \
+                               eps, silu, part, sync, groups);                                                                \
+        else                                                                                                                  \
+            hipLaunchKernelGGL((gn_cluster_kernel<T, NVV>), dim3(blocks), dim3(BS), 0, st, (const T*)x, (T*)y, w, b, q, kps, vpb, eps,  \
+                               silu, part, sync, groups);                                                                     \
+    } while (0)
     if (need <= 2) MVI_GN_CL(2);
     else if (need <= 4) MVI_GN_CL(4);
     else if (need <= 8) MVI_GN_CL(8);
@@ -737,7 +758,7 @@ static int gn_cluster_launch(const void* x, void* y, const float* w, const float
 template <typename T>
 static int gn_launch(const void* x, void* y, const float* w, const float* b, const float* chan_bias, int stack3, int64_t N,
                      int slices, int C, int64_t S, int G, float eps, int silu, float* part, hipStream_t st, int tokens = 0,
-                     uint32_t* sync = nullptr) {
+                     uint32_t* sync = nullptr, float* stats = nullptr) {
     constexpr int KV = Io<T>::kVec;
     constexpr int CH = kGnBlock * kGnVecPerThread * KV;
     GnGeom q;
@@ -745,7 +766,7 @@ static int gn_launch(const void* x, void* y, const float* w, const float* b, con
     q.E = (int64_t)q.Cg * S;
     q.slice_stride = (int64_t)C * S;
     q.cps = (int)((q.E + CH - 1) / CH);
-    q.chan_bias = chan_bias; q.stack3 = stack3;
+    q.chan_bias = chan_bias; q.stack3 = stack3; q.stats = stats;
     const bool vec = (S % KV == 0) && (((uintptr_t)x | (uintptr_t)y) % 16 == 0);
     dim3 grid((unsigned)(q.cps * slices), (unsigned)(N * G));
     if (tokens) {
@@ -754,8 +775,12 @@ static int gn_launch(const void* x, void* y, const float* w, const float* b, con
         const int64_t blocks = N * s_tiles * c_tiles;
         if (blocks > 0x7FFFFFFFll) return MVI_EINVAL;
         hipLaunchKernelGGL((gn_stats_kernel<T, true>), grid, dim3(kGnBlock), 0, st, (const T*)x, part, q);
-        hipLaunchKernelGGL((gn_apply_tokens_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, (T*)y, w, b, part,
-                           q, eps, silu, s_tiles, c_tiles);
+        if (stats)
+            hipLaunchKernelGGL((gn_apply_tokens_kernel<T, true>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, (T*)y, w, b,
+                               part, q, eps, silu, s_tiles, c_tiles);
+        else
+            hipLaunchKernelGGL((gn_apply_tokens_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, (T*)y, w, b, part,
+                               q, eps, silu, s_tiles, c_tiles);
         return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
     }
     // measured (tools/bench_groupnorm.py, bf16, MI355X, two launches -> resident): 11 KB groups 21.7 -> 17.8 us, 46 KB
@@ -764,7 +789,7 @@ static int gn_launch(const void* x, void* y, const float* w, const float* b, con
     static const int resident_kb = getenv("MVI_GN_RESIDENT_KB") ? atoi(getenv("MVI_GN_RESIDENT_KB")) : 192;
     // (the resident kernel indexes channels with 24-bit arithmetic: groups of up to 256 KB are far below that)
     if (vec && slices == 1 && !stack3 && (int64_t)q.Cg * S * (int64_t)sizeof(T) <= (int64_t)resident_kb * 1024) {
-        const int rc = gn_resident_launch<T>(x, y, w, b, chan_bias, N, C, S, G, eps, silu, st);
+        const int rc = gn_resident_launch<T>(x, y, w, b, chan_bias, N, C, S, G, eps, silu, st, stats);
         if (rc != 1) return rc;
     }
     // groups from cluster_kb up (and every temporal / stacked call) take the cluster form when the caller gave a sync buffer
@@ -778,10 +803,12 @@ static int gn_launch(const void* x, void* y, const float* w, const float* b, con
     // (28, 320, 72, 128) bf16; smaller bands worse: the shorter grids cost more than the cached re-read saves.)
     if (vec) {
         hipLaunchKernelGGL((gn_stats_kernel<T, true>), grid, dim3(kGnBlock), 0, st, (const T*)x, part, q);
-        hipLaunchKernelGGL((gn_apply_kernel<T, true>), grid, dim3(kGnBlock), 0, st, (const T*)x, (T*)y, w, b, part, q, eps, silu);
+        if (stats) hipLaunchKernelGGL((gn_apply_kernel<T, true, true>), grid, dim3(kGnBlock), 0, st, (const T*)x, (T*)y, w, b, part, q, eps, silu);
+        else hipLaunchKernelGGL((gn_apply_kernel<T, true>), grid, dim3(kGnBlock), 0, st, (const T*)x, (T*)y, w, b, part, q, eps, silu);
     } else {
         hipLaunchKernelGGL((gn_stats_kernel<T, false>), grid, dim3(kGnBlock), 0, st, (const T*)x, part, q);
-        hipLaunchKernelGGL((gn_apply_kernel<T, false>), grid, dim3(kGnBlock), 0, st, (const T*)x, (T*)y, w, b, part, q, eps, silu);
+        if (stats) hipLaunchKernelGGL((gn_apply_kernel<T, false, true>), grid, dim3(kGnBlock), 0, st, (const T*)x, (T*)y, w, b, part, q, eps, silu);
+        else hipLaunchKernelGGL((gn_apply_kernel<T, false>), grid, dim3(kGnBlock), 0, st, (const T*)x, (T*)y, w, b, part, q, eps, silu);
     }
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
@@ -811,7 +838,7 @@ extern "C" size_t mvi_groupnorm_workspace_bytes(int64_t N, int32_t C, int64_t sp
 static int gn_dispatch(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias, int stack3,
                        int64_t Nv, int32_t T, int32_t C,
                        int64_t spatial, int32_t groups, float eps, int32_t fuse_silu, int32_t dtype, void* workspace,
-                       size_t workspace_bytes, void* stream, int tokens = 0, uint32_t* sync = nullptr) {
+                       size_t workspace_bytes, void* stream, int tokens = 0, uint32_t* sync = nullptr, float* stats = nullptr) {
     if (Nv < 0 || T <= 0 || C <= 0 || groups <= 0 || spatial < 0 || C % groups != 0)
         return mvi::unet_fail(MVI_EINVAL, "groupnorm: C must be a positive multiple of groups");
     if (Nv == 0 || spatial == 0) return MVI_OK;
@@ -823,9 +850,9 @@ static int gn_dispatch(const void* x, void* y, const float* weight, const float*
     float* part = (float*)workspace;
     int rc;
     switch (dtype) {
-        case MVI_DT_F32: rc = mvi::gn_launch<float>(x, y, weight, bias, chan_bias, stack3, Nv, T, C, spatial, groups, eps, fuse_silu, part, st, tokens, sync); break;
-        case MVI_DT_BF16: rc = mvi::gn_launch<__hip_bfloat16>(x, y, weight, bias, chan_bias, stack3, Nv, T, C, spatial, groups, eps, fuse_silu, part, st, tokens, sync); break;
-        case MVI_DT_F16: rc = mvi::gn_launch<__half>(x, y, weight, bias, chan_bias, stack3, Nv, T, C, spatial, groups, eps, fuse_silu, part, st, tokens, sync); break;
+        case MVI_DT_F32: rc = mvi::gn_launch<float>(x, y, weight, bias, chan_bias, stack3, Nv, T, C, spatial, groups, eps, fuse_silu, part, st, tokens, sync, stats); break;
+        case MVI_DT_BF16: rc = mvi::gn_launch<__hip_bfloat16>(x, y, weight, bias, chan_bias, stack3, Nv, T, C, spatial, groups, eps, fuse_silu, part, st, tokens, sync, stats); break;
+        case MVI_DT_F16: rc = mvi::gn_launch<__half>(x, y, weight, bias, chan_bias, stack3, Nv, T, C, spatial, groups, eps, fuse_silu, part, st, tokens, sync, stats); break;
         default: return mvi::unet_fail(MVI_EINVAL, "groupnorm: unknown dtype");
     }
     if (rc == MVI_EINVAL)
@@ -864,6 +891,24 @@ extern "C" int mvi_groupnorm_silu_ex2(const void* x, void* y, const float* weigh
     if (sync && sync_bytes < mvi_groupnorm_sync_bytes()) return mvi::unet_fail(MVI_ENOMEM, "groupnorm: sync buffer too small");
     return gn_dispatch(x, y, weight, bias, chan_bias, stack3 ? 1 : 0, videos, T, C, spatial, groups, eps, fuse_silu, dtype, workspace,
                        workspace_bytes, stream, 0, (uint32_t*)sync);
+}
+
+// The forward under autograd: the dispatch of mvi_groupnorm_silu_ex2 / mvi_groupnorm_silu_tokens with the kStats instantiations
+extern "C" int mvi_groupnorm_forward_stats(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
+                                           float* stats, int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, float eps,
+                                           int32_t fuse_silu, int32_t out_layout, int32_t dtype, void* workspace, size_t workspace_bytes,
+                                           void* sync, size_t sync_bytes, void* stream) {
+    if (!stats) return mvi::unet_fail(MVI_EINVAL, "groupnorm: stats is NULL");
+    if (out_layout < MVI_GN_DY_PLANES || out_layout > MVI_GN_DY_TOKENS) return mvi::unet_fail(MVI_EINVAL, "groupnorm: unknown output layout");
+    if (out_layout != MVI_GN_DY_PLANES && x == y) return mvi::unet_fail(MVI_EINVAL, "groupnorm: this output layout cannot alias the input");
+    if (out_layout == MVI_GN_DY_TOKENS) {
+        if (T != 1) return mvi::unet_fail(MVI_EINVAL, "groupnorm (token-major output): T must be 1");
+        return gn_dispatch(x, y, weight, bias, chan_bias, 0, videos, 1, C, spatial, groups, eps, fuse_silu, dtype, workspace, workspace_bytes,
+                           stream, 1, nullptr, stats);
+    }
+    if (sync && sync_bytes < mvi_groupnorm_sync_bytes()) return mvi::unet_fail(MVI_ENOMEM, "groupnorm: sync buffer too small");
+    return gn_dispatch(x, y, weight, bias, chan_bias, out_layout == MVI_GN_DY_STACK3 ? 1 : 0, videos, T, C, spatial, groups, eps, fuse_silu,
+                       dtype, workspace, workspace_bytes, stream, 0, (uint32_t*)sync, stats);
 }
 
 extern "C" int mvi_groupnorm_silu_tokens(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,

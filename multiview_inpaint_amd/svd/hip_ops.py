@@ -12,7 +12,8 @@ _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 _ws = {}
 
 # Optional per-op timing for bench.py: when PROFILE is a list, every op appends
-# (kind, start_event, end_event, work) with events recorded on the stream the kernel runs on.
+# (kind, start_event, end_event, work) with events recorded on the stream the kernel runs on. GroupNorm under autograd shows as
+# "groupnorm_stats_fwd" and "groupnorm_bwd" ("groupnorm_bwd_params" when the call also launched the dweight / dbias kernel).
 PROFILE = None
 # When a list: every attention call appends (kernel variant, Sq, Sk) — 0 rowtile, 4 / 8 = the 4- / 8-wave MFMA kernel
 # (mvi_attention_kernel_variant, the function the C dispatch itself uses). The parity tests assert from it WHICH kernel ran
@@ -124,18 +125,9 @@ def _f32(p):
 
 def _gn(x, T, num_groups, weight, bias, eps, silu, chan_bias, stack3):
     L = _lib.lib()
-    if x.dtype not in _DT:
-        raise TypeError(f"group_norm: unsupported dtype {x.dtype}")
-    xc = x if x.is_contiguous() else x.contiguous()
-    N, Cc = xc.shape[0], xc.shape[1]
-    S = xc.numel() // max(N * Cc, 1)
+    xc, N, Cc, S, cb = _gn_args("group_norm", x, chan_bias)
     y = torch.empty((N, 3 * Cc, *xc.shape[2:]) if stack3 else xc.shape, dtype=x.dtype, device=x.device)
     w, b = _f32(weight), _f32(bias)
-    cb = None
-    if chan_bias is not None:
-        cb = chan_bias.detach().float().contiguous()
-        if cb.shape != (N, Cc):
-            raise ValueError(f"group_norm: chan_bias must be [{N}, {Cc}], got {tuple(cb.shape)}")
     ws = _workspace(xc.device, L.mvi_groupnorm_workspace_bytes(N, Cc, S, num_groups))
     sync = _groupnorm_sync(xc.device)
     with torch.cuda.device(xc.device), _Timed("groupnorm", (2.0 + 2.0 * bool(stack3)) * xc.numel() * xc.element_size(), xc.device):
@@ -153,17 +145,8 @@ def group_norm_silu(x, num_groups, weight, bias, eps, silu, chan_bias=None):
 def group_norm_silu_tokens(x, num_groups, weight, bias, eps, silu, chan_bias=None):
     """GroupNorm(+SiLU) of x [N, C, *spatial] returned token-major [N, prod(spatial), C]."""
     L = _lib.lib()
-    if x.dtype not in _DT:
-        raise TypeError(f"group_norm: unsupported dtype {x.dtype}")
-    xc = x if x.is_contiguous() else x.contiguous()
-    N, Cc = xc.shape[0], xc.shape[1]
-    S = xc.numel() // max(N * Cc, 1)
+    xc, N, Cc, S, cb = _gn_args("group_norm", x, chan_bias)
     y = torch.empty((N, S, Cc), dtype=x.dtype, device=x.device)
-    cb = None
-    if chan_bias is not None:
-        cb = chan_bias.detach().float().contiguous()
-        if cb.shape != (N, Cc):
-            raise ValueError(f"group_norm: chan_bias must be [{N}, {Cc}], got {tuple(cb.shape)}")
     ws = _workspace(xc.device, L.mvi_groupnorm_workspace_bytes(N, Cc, S, num_groups))
     with torch.cuda.device(xc.device), _Timed("groupnorm_tokens", 2.0 * xc.numel() * xc.element_size(), xc.device):
         _check(L.mvi_groupnorm_silu_tokens(xc.data_ptr(), y.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(),
@@ -176,6 +159,85 @@ def group_norm_silu_tokens(x, num_groups, weight, bias, eps, silu, chan_bias=Non
 def group_norm_silu_frames(x, T, num_groups, weight, bias, eps, silu, chan_bias=None, stack3=False):
     """x [(b T), C, *spatial] contiguous; statistics per (video, group) over all T frames."""
     return _gn(x, int(T), num_groups, weight, bias, eps, silu, chan_bias, stack3)
+
+
+GN_PLANES, GN_STACK3, GN_TOKENS = 0, 1, 2      # MVI_GN_DY_*: the layout the forward writes y in = the layout dy arrives in
+
+
+def group_norm_backward_supported(N, C, S, num_groups, T, dtype, layout=GN_PLANES):
+    """Whether group_norm_forward_stats / group_norm_backward compute x [N = videos * T, C, S] (mvi_groupnorm_backward_supported, a
+    host-only function)."""
+    if dtype not in _DT or T <= 0 or N % T != 0 or num_groups <= 0 or C % num_groups != 0:
+        return False
+    return bool(_lib.lib().mvi_groupnorm_backward_supported(int(N // T), int(T), int(C), int(S), int(num_groups), int(layout), _DT[dtype]))
+
+
+def _gn_args(what, x, chan_bias):
+    if x.dtype not in _DT:
+        raise TypeError(f"{what}: unsupported dtype {x.dtype}")
+    xc = x if x.is_contiguous() else x.contiguous()
+    N, Cc = xc.shape[0], xc.shape[1]
+    S = xc.numel() // max(N * Cc, 1)
+    cb = None
+    if chan_bias is not None:
+        cb = chan_bias.detach().float().contiguous()
+        if cb.shape != (N, Cc):
+            raise ValueError(f"{what}: chan_bias must be [{N}, {Cc}], got {tuple(cb.shape)}")
+    return xc, N, Cc, S, cb
+
+
+def group_norm_forward_stats(x, T, num_groups, weight, bias, eps, silu, chan_bias=None, layout=GN_PLANES):
+    """The forward of group_norm_silu / _frames (layout GN_PLANES, GN_STACK3) or group_norm_silu_tokens (GN_TOKENS) — same kernels, y
+    bit-identical — that also returns the fp32 (mean, rstd) of every (video, group) [N / T * groups, 2] for group_norm_backward."""
+    L = _lib.lib()
+    xc, N, Cc, S, cb = _gn_args("group_norm_forward_stats", x, chan_bias)
+    if layout == GN_TOKENS:
+        y = torch.empty((N, S, Cc), dtype=x.dtype, device=x.device)
+    else:
+        y = torch.empty((N, 3 * Cc, *xc.shape[2:]) if layout == GN_STACK3 else xc.shape, dtype=x.dtype, device=x.device)
+    stats = torch.empty((N // T * num_groups, 2), dtype=torch.float32, device=x.device)
+    ws = _workspace(xc.device, L.mvi_groupnorm_workspace_bytes(N, Cc, S, num_groups))
+    sync = None if layout == GN_TOKENS else _groupnorm_sync(xc.device)
+    work = (2.0 + 2.0 * (layout == GN_STACK3)) * xc.numel() * xc.element_size()
+    with torch.cuda.device(xc.device), _Timed("groupnorm_stats_fwd", work, xc.device):
+        _check(L.mvi_groupnorm_forward_stats(xc.data_ptr(), y.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(),
+                                             None if cb is None else cb.data_ptr(), stats.data_ptr(), N // T, int(T), Cc, S, num_groups,
+                                             float(eps), int(bool(silu)), int(layout), _DT[x.dtype], ws.data_ptr(), ws.numel(),
+                                             None if sync is None else sync.data_ptr(), 0 if sync is None else sync.numel(),
+                                             _stream(xc.device)), "group_norm_forward_stats")
+    return y, stats
+
+
+def group_norm_backward(dy, x, stats, T, num_groups, weight, bias, silu, chan_bias=None, layout=GN_PLANES, need_dx=True,
+                        need_dparams=False, need_dchan_bias=False):
+    """(dx, dweight, dbias, dchan_bias) of the GroupNorm(+SiLU) whose forward returned `stats` (csrc/groupnorm_bwd.hip): dx in x's dtype
+    and shape, the others fp32; outputs not asked for are None and cost nothing (need_dparams adds one small launch; the PROFILE kind
+    is then "groupnorm_bwd_params" instead of "groupnorm_bwd"). dy: contiguous, x's dtype, in the layout the forward wrote y in.
+    Deterministic."""
+    L = _lib.lib()
+    xc, N, Cc, S, cb = _gn_args("group_norm_backward", x, chan_bias)
+    want = (N, S, Cc) if layout == GN_TOKENS else (N, (3 if layout == GN_STACK3 else 1) * Cc, *xc.shape[2:])
+    if dy.dtype != x.dtype or tuple(dy.shape) != want or not dy.is_contiguous():
+        raise ValueError(f"group_norm_backward: dy must be contiguous {x.dtype} {want}, got {dy.dtype} {tuple(dy.shape)}")
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (N // T * num_groups, 2) or not stats.is_contiguous():
+        raise ValueError("group_norm_backward: stats must be the fp32 [videos * groups, 2] table of group_norm_forward_stats")
+    if need_dchan_bias and cb is None:
+        raise ValueError("group_norm_backward: dchan_bias asked for without chan_bias")
+    f32 = dict(dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(xc) if need_dx else None
+    dw = torch.empty(Cc, **f32) if need_dparams else None
+    db = torch.empty(Cc, **f32) if need_dparams else None
+    dcb = torch.empty((N, Cc), **f32) if need_dchan_bias else None
+    nbytes = int(L.mvi_groupnorm_backward_workspace_bytes(N // T, int(T), Cc, S, num_groups))
+    ws = _workspace(x.device, nbytes)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    nd = 3 if layout == GN_STACK3 else 1                 # dy blocks read per element
+    work = ((1.0 + nd) + (2.0 + nd) * bool(need_dx)) * xc.numel() * xc.element_size()     # reduce pass (+ apply pass) bytes
+    with torch.cuda.device(x.device), _Timed("groupnorm_bwd_params" if need_dparams else "groupnorm_bwd", work, x.device):
+        _check(L.mvi_groupnorm_backward(xc.data_ptr(), dy.data_ptr(), stats.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(),
+                                        ptr(cb), ptr(dx), ptr(dw), ptr(db), ptr(dcb), N // T, int(T), Cc, S, num_groups, int(bool(silu)),
+                                        int(layout), _DT[x.dtype], ws.data_ptr(), ws.numel(), _stream(x.device)), "group_norm_backward")
+    return dx, dw, db, dcb
 
 
 def attention(q, k, v, heads):

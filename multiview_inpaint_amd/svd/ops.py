@@ -6,8 +6,9 @@ reference's own CPU-runnable case, not a fallback for the GPU.
 
 Under autograd (ControlNet training — SURVEY.md §2 row 21) attention stays on the HIP path, forward and backward
 (csrc/attn_bwd.hip: `attention` for bf16 / f16 with D = 64 and more than 32 keys, `attention_temporal` for every shape its
-forward takes). Every other kernel is forward-only: a GPU tensor that requires grad goes through PyTorch-ROCm's
-differentiable ops there (GroupNorm, GEGLU, the projections and convolutions).
+forward takes), and so does GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip: `group_norm`, `group_norm_frames`, `group_norm_tokens`).
+Every other kernel is forward-only: a GPU tensor that requires grad goes through PyTorch-ROCm's differentiable ops there
+(GEGLU, the projections and convolutions, the token-major `group_norm_tok2tok`).
 
 Reference ops: GroupNorm32 + SiLU (sgm/modules/diffusionmodules/util.py:259-276,
 openaimodel.py:257-261,292-305), Normalize (sgm/modules/attention.py:125-128),
@@ -19,7 +20,7 @@ import torch
 import torch.nn.functional as F
 
 # A GPU tensor leaves the HIP path for one of two reasons, treated differently:
-#   * it requires grad and the op has no HIP backward (everything but attention): PyTorch-ROCm's differentiable ops run — the
+#   * it requires grad and the op has no HIP backward (everything but attention and GroupNorm): PyTorch-ROCm's differentiable ops run — the
 #     documented path;
 #   * a shape / contiguity gate of a kernel fails under no_grad: that RAISES by default (STRICT_GATES; since round 3) — an
 #     inference call never silently runs PyTorch ops in place of the kernels. MVI_STRICT=0 allows the substitute again
@@ -64,12 +65,71 @@ def _stack3(y, T):
     return out.reshape(bt, 3 * c, *y.shape[2:])
 
 
+# The HIP backward of GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip). MVI_GN_BWD=0 (or ops.GROUPNORM_BACKWARD = False): the three norms
+# below take PyTorch-ROCm's differentiable ops under autograd again.
+GROUPNORM_BACKWARD = os.environ.get("MVI_GN_BWD", "1") != "0"
+GROUPNORM_BACKWARD_MIN_ELEMENTS = (1 << 24, 0, 1 << 23)      # per dy layout: planes, stack3, token-major
+
+
+def group_norm_backward_pays(N, C, S, T, dtype, layout=0):
+    """Whether forward + backward on the HIP kernels is faster than the PyTorch-ROCm route for this shape class — the routing's second
+    question after hip_ops.group_norm_backward_supported. Set from tools/bench_groupnorm_bwd.py (profiles/groupnorm_bwd_bench.json;
+    DESIGN.md 'GroupNorm under autograd'): a class goes to HIP where the HIP route's median beat the PyTorch route's by more than that
+    route's spread. The HIP route costs 0.22 - 0.27 ms of host time per forward + backward whatever the size (its kernels: 0.06 - 0.29 ms),
+    the PyTorch route 0.21 ms at its smallest. stack3 (the temporal ResBlock: 0.26 - 0.41 against 0.43 - 2.7 ms) wins at every shape;
+    planes win from 20.6 M elements up (14 x 1920 x 24x32: 0.24 against 0.39 ms) and tie or lose at 13.8 M and below (14 x 320 x 48x64:
+    0.247 against 0.244); token-major wins at 13.8 M (0.23 against 0.32) and loses at 3.4 M and below. The lines sit between."""
+    return N * C * S >= GROUPNORM_BACKWARD_MIN_ELEMENTS[layout]
+
+
+class _GroupNormFn(torch.autograd.Function):
+    """GroupNorm(+SiLU) on the HIP kernels with a deterministic HIP backward, behind group_norm, group_norm_tokens and
+    group_norm_frames. Holds x, weight, bias, chan_bias and the (mean, rstd) table — not y, nothing tensor-sized in fp32; nothing is
+    cached outside ctx, so torch.utils.checkpoint may re-run the forward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, chan_bias, num_groups, eps, silu, T, layout):
+        from . import hip_ops
+        xc = x if x.is_contiguous() else x.contiguous()
+        y, stats = hip_ops.group_norm_forward_stats(xc, T, num_groups, weight, bias, eps, silu, chan_bias=chan_bias, layout=layout)
+        ctx.save_for_backward(xc, weight, bias, chan_bias, stats)
+        ctx.cfg = (num_groups, bool(silu), T, layout)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        x, weight, bias, chan_bias, stats = ctx.saved_tensors
+        num_groups, silu, T, layout = ctx.cfg
+        n = ctx.needs_input_grad
+        dx, dw, db, dcb = hip_ops.group_norm_backward(dy.contiguous(), x, stats, T, num_groups, weight, bias, silu, chan_bias=chan_bias,
+                                                      layout=layout, need_dx=n[0], need_dparams=n[1] or n[2], need_dchan_bias=n[3])
+        return (dx, dw.to(weight.dtype) if n[1] else None, db.to(bias.dtype) if n[2] else None,
+                dcb.to(chan_bias.dtype).reshape(chan_bias.shape) if n[3] else None, None, None, None, None, None)
+
+
+def _gn_hip_autograd(x, T, num_groups, weight, bias, chan_bias, layout):
+    """Under autograd: does this norm run _GroupNormFn? (switch on, kernels compute the shape, and it pays)"""
+    if not (x.is_cuda and GROUPNORM_BACKWARD and x.dim() >= 2 and x.numel() > 0):
+        return False
+    from . import hip_ops
+    N, C = x.shape[0], x.shape[1]
+    S = x.numel() // (N * C)
+    if chan_bias is not None and tuple(chan_bias.shape) != (N, C):
+        return False
+    return (hip_ops.group_norm_backward_supported(N, C, S, num_groups, T, x.dtype, layout)
+            and group_norm_backward_pays(N, C, S, T, x.dtype, layout))
+
+
 def group_norm(x, num_groups, weight, bias, eps, silu=False, chan_bias=None):
     """GroupNorm over (C/G, *spatial) with fp32 statistics, optional fused SiLU; output dtype = x.dtype.
     chan_bias [N, C] (optional) is added to x first (the ResBlock's timestep-embedding bias)."""
     if x.is_cuda and not _needs_autograd(x, weight, bias, chan_bias):
         from . import hip_ops
         return hip_ops.group_norm_silu(x, num_groups, weight, bias, eps, silu, chan_bias=chan_bias)
+    if _gn_hip_autograd(x, 1, num_groups, weight, bias, chan_bias, 0):
+        return _GroupNormFn.apply(x, weight, bias, chan_bias, num_groups, eps, silu, 1, 0)
     _fallback(x, "group_norm", _why(x, weight, bias, chan_bias))
     xf = x.float()
     if chan_bias is not None:
@@ -88,6 +148,11 @@ def group_norm_tokens(x, num_groups, weight, bias, eps, silu=False, chan_bias=No
             return hip_ops.group_norm_silu_tokens(x, num_groups, weight, bias, eps, silu, chan_bias=chan_bias)
         # odd channel / token counts: the plain HIP GroupNorm, then PyTorch's transpose copy (small tensors only)
         return hip_ops.group_norm_silu(x, num_groups, weight, bias, eps, silu, chan_bias=chan_bias).flatten(2).transpose(1, 2).contiguous()
+    if x.shape[1] % 8 == 0 and S % 8 == 0 and x.data_ptr() % 16 == 0 and _gn_hip_autograd(x, 1, num_groups, weight, bias, chan_bias, 2):
+        return _GroupNormFn.apply(x, weight, bias, chan_bias, num_groups, eps, silu, 1, 2)
+    if _gn_hip_autograd(x, 1, num_groups, weight, bias, chan_bias, 0):
+        # odd channel / token counts: the planes form, then PyTorch's transpose copy (autograd provides its backward)
+        return _GroupNormFn.apply(x, weight, bias, chan_bias, num_groups, eps, silu, 1, 0).flatten(2).transpose(1, 2).contiguous()
     _fallback(x, "group_norm_tokens", _why(x, weight, bias, chan_bias))
     return group_norm(x, num_groups, weight, bias, eps, silu=silu, chan_bias=chan_bias).flatten(2).transpose(1, 2).contiguous()
 
@@ -115,6 +180,8 @@ def group_norm_frames(x, T, num_groups, weight, bias, eps, silu=False, chan_bias
     if x.is_cuda and not _needs_autograd(x, weight, bias, chan_bias):
         from . import hip_ops
         return hip_ops.group_norm_silu_frames(x, T, num_groups, weight, bias, eps, silu, chan_bias=chan_bias, stack3=stack3)
+    if x.shape[0] % T == 0 and _gn_hip_autograd(x, int(T), num_groups, weight, bias, chan_bias, 1 if stack3 else 0):
+        return _GroupNormFn.apply(x, weight, bias, chan_bias, num_groups, eps, silu, int(T), 1 if stack3 else 0)
     _fallback(x, "group_norm_frames", _why(x, weight, bias, chan_bias))
     bt, c = x.shape[:2]
     xf = x.float()
