@@ -20,38 +20,26 @@
 //        A = two transposed 4-row x 16-d LDS reads (rows 4 g .. 4 g + 3 of streamed tile 0, then of tile 1): the same permutation
 //        C/D: lane (c, g) register i holds out[resident 16 rt + c][d = 16 dt + 4 g + i]: one 8-byte store per d tile
 // The softmax scale: the forward either multiplies the fp32 scores by scale log2 e (bf16) or rounds scale log2 e into Q (f16 default,
-// attn_flash8.hip `kExact`). L was computed from those scores, so the recomputation here takes the same form (kFold) — P then sums to
-// one over a row; dK uses the unscaled Q (a second LDS image), dQ and dK get `scale` in the epilogue. (Measured: exact scores against
-// a folded forward's L are WORSE — f16, S = 1300 with a peaked row: dk rms 2.7 x the reference's own error against 1.8 x, dv 2.0 x
-// against 0.4 x.)
+// attn_flash8m16.hip `kExact`; attention_folds_scale in attn_api.hip decides for both directions). L was computed from those scores,
+// so the recomputation here takes the same form (kFold) — P then sums to one over a row; dK uses the unscaled Q (a second LDS
+// image), dQ and dK get `scale` in the epilogue. (Measured: exact scores against a folded forward's L are WORSE — f16, S = 1300
+// with a peaked row: dk rms 2.7 x the reference's own error against 1.8 x, dv 2.0 x against 0.4 x.)
 // Rows past the end of a ragged last tile: resident rows are loaded as zeros and not stored; streamed rows are loaded as zeros and
 // their P and dS are set to zero. No lane is ever masked around a transposed LDS read (it needs EXEC all ones).
 //
 // Temporal backward (softmax over the T <= 16 frames of each (video, token, head), [(Bo T), S, H, D], nothing regrouped): HBM-bound
 // (seven tensors against T x T scores), so one 64-thread block per problem recomputes the softmax in fp32 from an LDS copy.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <type_traits>
 
 #include "../../include/mvi_raster.h"
 #include "../../include/mvi_unet_ops.h"
+#include "attn_launch.h"
+#include "mfma_common.h"
 
 namespace mvi {
-int unet_fail(int code, const char* msg);
 namespace bwd {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-#define MVI_AS3 __attribute__((address_space(3)))
 
 constexpr int kD = 64;
 constexpr int kST = 64;                 // streamed rows per tile
@@ -62,29 +50,12 @@ constexpr int kImg = kST * kStride * 2; // bytes of one tile image
 constexpr float kLog2e = 1.4426950408889634f;
 
 template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> {
-    using frag = bf16x8;
+template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
     __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        bf16x2 r = __builtin_convertvector(f, bf16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
-    __device__ static float lo(uint32_t w) { return __uint_as_float(w << 16); }
-    __device__ static float hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
 };
-template <> struct Mma<__half> {
-    using frag = f16x8;
+template <> struct Mma<__half> : MmaType<__half> {
     __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        f16x2 r = __builtin_convertvector(f, f16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
-    __device__ static float lo(uint32_t w) { f16x2 h = *reinterpret_cast<f16x2*>(&w); return (float)h[0]; }
-    __device__ static float hi(uint32_t w) { f16x2 h = *reinterpret_cast<f16x2*>(&w); return (float)h[1]; }
 };
-template <typename F> __device__ __forceinline__ F as_frag(u32x4 v) { return *reinterpret_cast<F*>(&v); }
 
 // delta[b, h, i] = sum_d dout[b, i, h, d] out[b, i, h, d]: 8 lanes per row, 16 bytes per lane and tensor
 template <typename T>
@@ -430,14 +401,6 @@ static int temporal_bwd_launch(const void* q, const void* k, const void* v, cons
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 
-// the forward's choice between the exact and the folded scale (attn_flash8.hip, attn_flash8m16.hip); the 4-wave kernel is always exact
-static bool forward_folds(int Sq, int Sk, int dtype) {
-    const int variant = mvi_attention_kernel_variant(Sq, Sk, kD, dtype);
-    if (variant != 8 && variant != 16) return false;
-    static const int fold_env = getenv("MVI_ATTN_FOLD_SCALE") ? atoi(getenv("MVI_ATTN_FOLD_SCALE")) : -1;
-    return fold_env >= 0 ? fold_env != 0 : dtype == MVI_DT_F16;
-}
-
 template <typename T>
 static int bwd_launch(const void* q, const void* k, const void* v, const void* out, const void* dout, const float* lse, void* dq, void* dk,
                       void* dv, int B, int H, int Sq, int Sk, float scale, bool fold, float* delta, hipStream_t st) {
@@ -491,7 +454,7 @@ extern "C" int mvi_attention_backward(const void* q, const void* k, const void* 
         return mvi::unet_fail(MVI_EINVAL, "attention backward: tensors must be 16-byte aligned");
     if (!workspace || workspace_bytes < mvi_attention_backward_workspace_bytes(B, H, Sq, Sk, D, dtype))
         return mvi::unet_fail(MVI_EINVAL, "attention backward: workspace too small");
-    const bool fold = mvi::bwd::forward_folds(Sq, Sk, dtype);
+    const bool fold = mvi::attention_folds_scale(mvi_attention_kernel_variant(Sq, Sk, D, dtype), dtype);   // as the forward that wrote lse
     hipStream_t st = (hipStream_t)stream;
     const int rc = dtype == MVI_DT_BF16
         ? mvi::bwd::bwd_launch<__hip_bfloat16>(q, k, v, out, dout, (const float*)lse, dq, dk, dv, B, H, Sq, Sk, scale, fold, (float*)workspace, st)

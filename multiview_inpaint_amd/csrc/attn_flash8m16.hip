@@ -1,19 +1,34 @@
-// The 8-wave flash attention kernel of attn_flash8.hip on v_mfma_f32_16x16x32 instead of v_mfma_f32_32x32x16 (round 6, VERDICT r5
-// item 1): the same 256-query block, K/V LDS-DMA ring, barriers, fixed-exponent fast form and online-softmax safe form — only the
-// matrix instruction and with it every lane layout differ. Why it exists: every linear_n320 form ran 9 - 11 % faster on the 16x16x32
-// shape at equal cycles (the chip holds a higher clock under it: profiles/round5_n320_mfma16_ab.txt, MI355X_MICROARCH.md 'DVFS
-// give-back' item 7), and attention was the one matrix kernel never built on it. Whether it pays HERE is a measurement
-// (profiles/round6_attention_mfma16_ab.txt): this kernel is bound by vector issue, and an MFMA of either shape holds the issue port
-// for 8 cycles — the 16x16x32 form issues twice as many of them per FLOP.
-// Measured (profiles/round6_attention_mfma16_ab.txt, same box, alternating, q carrying the scale as the SVD modules run it): per 64-key
-// tile and block 1638 shader cycles on 32x32x16, 1841 here, 1868 with the row sums as a fifth d tile (kOnes) — and an in-kernel clock of
-// 1.83, 2.07 and 2.11 GHz: the chip is power-bound under this kernel and pays the cheaper instruction back as clock, 12 % more cycles
-// become 2.7 - 3.0 % LESS time (S = 9216: 2.742 -> 2.668 ms, 0.443 -> 0.455 of 2.5 PF on that box; S = 2304: 0.402 -> 0.390 ms). On
-// all-zero operands (2.39 GHz for all three) the order is the cycle order. So this kernel is the default since round 6
-// (MVI_ATTN_MFMA16: 0 = attn_flash8.hip, 1 = row sums on the VALU, 2 = default); mvi_attention_kernel_variant reports 16.
-// Replaces xformers.ops.memory_efficient_attention / SDPA (svd_inpaint1/sgm/modules/attention.py:427-439, :332-336).
+// bf16/f16 MFMA flash attention (forward), head dim 64, 8-wave workgroups, on v_mfma_f32_16x16x32 — the kernel behind the large
+// spatial self-attentions of the SVD denoise step: (B*H, S) = (140, 9216) and (280, 2304) at 14 x 576x1024, 99.7 % of the attention
+// FLOPs. Replaces xformers.ops.memory_efficient_attention / SDPA (svd_inpaint1/sgm/modules/attention.py:427-439,
+// :332-336). attn_flash.hip keeps the 4-wave kernel for short sequences; mvi_attention_kernel_variant reports 16 where this one runs.
 //
-// Layout: q/out [B, Sq, H, 64], k/v [B, Sk, H, 64] token-major with element strides between tokens, as in attn_flash8.hip.
+// Why a second kernel: at D = 64 the 4-wave kernel is bound by the SIMD's ISSUE port, not by the matrix pipe
+// (profiles/r01u_pmc_attention.txt: 13.8 VALU per MFMA, pipe 39.7 % busy). This one removes issue slots:
+//   * the running reference exponent m never touches the VALU: -m enters the scores as the C operand of the first MFMA of every
+//     QK^T chain (a register block holding -m). The softmax SCALE has two forms (template kExact, below): applied to the fp32
+//     scores (one v_mul per score; the form a caller's own q gets in bf16), or absent from the loop because Q carries
+//     scale * log2(e) — either rounded into Q in the prologue (f16's default: a second rounding of q) or already inside q from its
+//     projection's weights (mvi_attention_forward_strided_qlog2: no second rounding, both types; what the self-attentions of the
+//     SVD modules run) — so P = exp2(S') directly. Which form a call gets is decided in attn_api.hip (attention_folds_scale);
+//   * the softmax row sums come out of the matrix pipe: a fifth "d tile" whose V^T fragment is a row of ones (two more MFMAs per
+//     32-key block, +1/8 of the matrix work) replaces 32 v_add_f32 per wave and tile; the sums are then those of the ROUNDED
+//     probabilities, i.e. of exactly the numerators the P V products use;
+//   * K and V tiles go HBM/L2 -> LDS by LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave-instruction) instead of through VGPRs
+//     (8 loads + 12 LDS stores + 16 pack ops per wave and tile in the 4-wave kernel);
+//   * V stays row-major in LDS and is read transposed by ds_read_b64_tr_b16 (no hand transposition);
+//   * the loop is unrolled over a 4-deep ring with two score accumulators in FIXED roles, so neither ring offsets nor an
+//     accumulator hand-over cost instructions (16 v_mov_b64 per tile in the 4-wave kernel);
+//   * 256 query rows share one K/V tile (8 waves x 32 rows): half the LDS fill traffic per row.
+// Measured and not kept (profiles/round6_attention_mfma16_ab.txt, same box, alternating; commit 7903115 is the last that holds them):
+// the same kernel on v_mfma_f32_32x32x16 (a file of its own there) and this one with the row sums on the VALU. Per 64-key tile and
+// block 1638 shader cycles on 32x32x16, 1841 here with VALU row sums, 1868 as shipped — at in-kernel clocks of 1.83, 2.07 and
+// 2.11 GHz: the chip is power-bound under this kernel and pays the cheaper instruction back as clock, 12 % more cycles become
+// 2.7 - 3.0 % LESS time (S = 9216: 2.742 -> 2.668 ms; S = 2304: 0.402 -> 0.390 ms). On all-zero operands (2.39 GHz for all three) the
+// order is the cycle order.
+//
+// Layout: q/out [B, Sq, H, 64], k/v [B, Sk, H, 64] token-major with element strides q_rs / kv_rs / o_rs between tokens (H*64 when
+// contiguous, 3*H*64 inside a packed projection).
 // A wave owns 32 queries = two 16-query tiles (qt). Lane = (c = lane & 15, g = lane >> 4).
 // Per wave and 32-key block (two 16-key tiles kt), v_mfma_f32_16x16x32, fp32 accumulate:
 //   S'^T[key][query] (16 x 16) = K (16 keys x 32 d) Q'^T (32 d x 16 queries) - m : 2 kt x 2 qt x 2 d-steps = 8 MFMA
@@ -24,72 +39,44 @@
 //   O^T[d][query] (16 x 16) += V^T (16 d x 32 keys) P^T (32 keys x 16 queries): 4 d tiles x 2 qt = 8 MFMA
 //        B = P from the S' accumulators: element j of lane (c, g) is k-index 8 g + j  <->  key (j < 4 ? 4 g + j : 16 + 4 g + j - 4)
 //        A = V^T by two ds_read_b64_tr_b16 per d tile (keys 4 g .. 4 g + 3 of key tile 0, then of key tile 1): the same permutation
-// LDS images (128-byte rows, 16-byte chunks XOR-swizzled on the DMA's SOURCE side): K chunk c of row r in slot c ^ ((r >> 1) & 7)
-// (ds_read_b128 of 16 rows x one chunk: conflict-free); V chunk c of row r in slot c ^ (((r >> 1) & 3) << 1) (a transposed read
-// touches 8 rows x 32 bytes per half wave: conflict-free).
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
+// LDS images (128-byte rows, 16-byte chunks XOR-swizzled; the DMA's destination is lane-linear, so the swizzle is applied to the
+// SOURCE address): K chunk c of row r in slot c ^ ((r >> 1) & 7) (ds_read_b128 of 16 rows x one chunk: conflict-free); V chunk c of
+// row r in slot c ^ (((r >> 1) & 3) << 1) (a transposed read touches 8 rows x 32 bytes per half wave: conflict-free).
+// Ring: 4 slots each for K and V; tile t (between two barriers) issues K_{t+3}, V_{t+3}; before the closing barrier every wave waits
+// for its own pieces of tile t + 2 with a COUNTED vmcnt (the pieces of tile t + 3 stay in flight across the barrier).
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
 #include "../../include/mvi_raster.h"
 #include "../../include/mvi_unet_ops.h"
+#include "attn_launch.h"
+#include "mfma_common.h"
 
 namespace mvi {
 namespace f8m {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-#define MVI_AS3 __attribute__((address_space(3)))
 
 constexpr int kD = 64;            // head dim
 constexpr int kKT = 64;           // keys per tile
 constexpr int kRing = 4;
 constexpr int kTileBytes = kKT * kD * 2;          // 8 KiB
 constexpr int kLdsBytes = 2 * kRing * kTileBytes; // K ring | V ring = 64 KiB (+ 16 bytes: the block's "repeat safely" flag)
-constexpr float kRescaleThreshold = 8.0f;         // log2 units
+constexpr float kRescaleThreshold = 8.0f;         // log2 units: O, l rescaled only when the row max grows by > 2^8
+// kWaves = 8: one 512-thread block per CU (2 waves per SIMD, 256 query rows share a K/V tile). kLoaders = 4: waves 0 .. 3 move the
+// LDS-DMA pieces, at the END of a tile (see issue_tile). The timing ablations, in-kernel stamps and block timeline that led here (other
+// kWaves / kLoaders, static wave priority, DMA pieces spread over the quarters — all measured and not kept) are in profiles/HISTORY.md
+// rounds 2 - 5; the diagnostic build that exists today is generated from this file (tools/attn_dev/build_stamped.sh), not kept beside it.
 constexpr int kWaves = 8;
 constexpr int kLoaders = 4;
 
 template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> {
-    using frag = bf16x8;
+template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
     __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        bf16x2 r = __builtin_convertvector(f, bf16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
-    __device__ static float lo(uint32_t w) { return __uint_as_float(w << 16); }
-    __device__ static float hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
 };
-template <> struct Mma<__half> {
-    using frag = f16x8;
+template <> struct Mma<__half> : MmaType<__half> {
     __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        f16x2 r = __builtin_convertvector(f, f16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
-    __device__ static float lo(uint32_t w) { f16x2 h = *reinterpret_cast<f16x2*>(&w); return (float)h[0]; }
-    __device__ static float hi(uint32_t w) { f16x2 h = *reinterpret_cast<f16x2*>(&w); return (float)h[1]; }
 };
 
-template <typename F> __device__ __forceinline__ F as_frag(u32x4 v) { return *reinterpret_cast<F*>(&v); }
-
-// (as in attn_flash8.hip: the kernel counts its own vmcnt for the LDS-DMA pieces)
-__device__ __forceinline__ void dma_piece(const void* sbase, uint32_t voff, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(sbase), "v"(voff), "s"(lds_addr) : "memory");
-}
 template <int N> __device__ __forceinline__ void wait_vm_then_barrier() {
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
 }
@@ -110,11 +97,12 @@ __device__ __forceinline__ float group_max(float x) {
 // scores of one 32-key block: [key tile kt][query tile qt], each the C/D tile of one accumulation chain
 struct Scores { f32x4 t[2][2]; };
 
-// kOnes: the softmax row sums come out of the matrix pipe instead of the VALU — a fifth "d tile" whose V^T fragment is a row of ones
-// (two more MFMAs per 32-key block, +1/8 of the matrix work) replaces the 32 v_add_f32 per wave and tile on the issue port that bounds
-// this kernel; the sums are then those of the ROUNDED probabilities, i.e. of exactly the numerators the P V products use.
+// kExact: the softmax scale is applied to the fp32 scores (one v_mul per score) instead of being rounded into Q. Folding
+// scale * log2(e) into Q saves those 32 multiplies per wave and tile but rounds Q a second time to bf16: an error of
+// |logit| * 2^-9 in the exponent, i.e. a few per cent on P where two keys with logits of ~60 compete (2.7e-2 of the
+// output scale on the adversarial rows of tests/test_unet_ops_gpu.py, against 5e-3 with the exact form).
 // kLse: as in attn_flash.hip — the row's log-sum-exp beside an `out` computed by the same instructions
-template <typename T, bool kExact, bool kOnes, bool kLse = false>
+template <typename T, bool kExact, bool kLse = false>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ out,
                            int H, int Sq, int Sk, float scale_log2e, int q_blocks, int total_blocks, int64_t q_rs,
@@ -155,7 +143,11 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
         }
     }
 
-    // ---- LDS-DMA source addressing (attn_flash8.hip; only V's swizzle differs)
+    // ---- LDS-DMA source addressing. A tile is 16 pieces of 1 KiB: pieces 0..7 = K rows 8 p .. 8 p + 7, pieces 8..15 = the same for
+    // V. Lane i of piece p fills LDS slot (row 8 (p & 7) + (i >> 3), 16-byte slot i & 7) with the chunk the image's swizzle assigns
+    // to that slot. Only waves 0 .. kLoaders - 1 move pieces (wave w: pieces w, w + kLoaders, ...), and they do it at the END of a
+    // tile: issuing a piece costs its wave ~150 cycles, and the first-dispatched half of the workgroup wins the SIMD's arbitration
+    // and waits ~500 cycles per tile at the barrier for the other half: that wait is where the loaders issue.
     const char* const kbase = reinterpret_cast<const char*>(k + (b * Sk * kv_rs + (int64_t)h * kD));
     const char* const vbase = reinterpret_cast<const char*>(v + (b * Sk * kv_rs + (int64_t)h * kD));
     constexpr int kMaxPieces = (16 + kLoaders - 1) / kLoaders;
@@ -175,7 +167,9 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
         p_dst[i] = lds0 + (p_is_v[i] ? kRing * kTileBytes : 0) + 1024u * (pc & 7);
     }
     const int n_tiles = (Sk + kKT - 1) / kKT;
-    const int n_full = Sk / kKT;
+    const int n_full = Sk / kKT;                 // tiles whose 64 rows all exist
+    // tiles past the end are still "loaded" (rows clamped to Sk - 1) so that every iteration issues the same number of pieces and
+    // the counted vmcnt stays valid; their ring slots are never read
     auto issue_tile = [&](int tt) __attribute__((always_inline)) {
         const uint32_t ring_off = (uint32_t)((tt & (kRing - 1)) * kTileBytes);
         const bool full = tt < n_full;
@@ -193,6 +187,7 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
             }
         }
     };
+    // counted waits: "at most `tiles_c` tiles' worth of this wave's own pieces still outstanding", then the barrier
     auto wait_tiles_then_barrier = [&](auto tiles_c) __attribute__((always_inline)) {
         constexpr int kT = decltype(tiles_c)::value;
         static_assert(16 % kLoaders == 0, "every loader moves 16 / kLoaders pieces");
@@ -216,11 +211,11 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
     }
 
     f32x4 o[4][2], negm[2];                  // o[d tile][query tile]
-    f32x4 lacc[2];                           // kOnes: row 0 of the "ones" tile = the row sums (lanes g == 0, register 0; zeros elsewhere)
+    f32x4 lacc[2];                           // row 0 of the "ones" tile = the row sums (lanes g == 0, register 0; zeros elsewhere)
     const uint32_t one2 = std::is_same<T, __half>::value ? 0x3C003C00u : 0x3F803F80u;
     const u32x4 ones = c16 == 0 ? u32x4{one2, one2, one2, one2} : u32x4{0, 0, 0, 0};     // A operand: V^T row 0 = 1 for every key
     Scores s0, s1;                           // scores of key block 0 / 1 of a tile: FIXED roles
-    float l[2], rsum[2];
+    float l[2], rsum[2];                     // l: row sum up to the last rescale; rsum (kLse only): what the VALU added since
     float l_exact[2] = {0.f, 0.f};           // kLse only
 
     // all of S' of one 32-key block (prologue only)
@@ -249,6 +244,8 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
         const float rb = __builtin_fmaxf(__builtin_fmaxf(bb[0], bb[1]), __builtin_fmaxf(bb[2], bb[3]));
         return group_max(__builtin_fmaxf(ra, rb));
     };
+    // Moves the reference exponent of the lanes in `grow` up by their block's excess over it: O, l, the block's scores and the -m
+    // operand all follow (first: O = l = 0, nothing to scale — and 0 * 2^big would be NaN)
     auto rescale = [&](Scores& sc, const bool (&grow)[2], const float (&rmax)[2], bool first) __attribute__((always_inline)) {
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
@@ -256,7 +253,7 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
             const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta * sc_mul);
             l[qt] = (l[qt] + rsum[qt]) * alpha;
             rsum[qt] = 0.f;
-            if (kOnes) lacc[qt] *= alpha;
+            lacc[qt] *= alpha;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha;
             sc.t[0][qt] -= delta;
@@ -295,10 +292,12 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
                 const float x1 = kExact ? sc.t[kt][qt][2 * i + 1] * sc_mul : sc.t[kt][qt][2 * i + 1];
                 const float p0 = __builtin_amdgcn_exp2f(x0);
                 const float p1 = __builtin_amdgcn_exp2f(x1);
-                if (!kOnes || kLse) rsum[qt] += p0 + p1;
+                if (kLse) rsum[qt] += p0 + p1;
                 pr[2 * kt + i] = M::pack2(p0, p1);
             }
-        if (!kOnes || kLse) asm volatile("" : "+v"(rsum[qt]));   // (as in attn_flash8.hip: the sum is complete here)
+        // the sum is complete HERE: without this, the fast form (which reads rsum only after the loop) sinks four tiles' adds — and
+        // 128 live P values — to the loop's end
+        if (kLse) asm volatile("" : "+v"(rsum[qt]));
         return pr;
     };
     // The matrix work beside one quarter: the S' MFMAs of key tile kt of the OTHER block (into acc.t[kt][*]) and the four P V MFMAs
@@ -313,11 +312,18 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
         if (with_k) acc.t[kt][1] = M::mfma(as_frag<frag>(f.k[1]), qf[1][1], acc.t[kt][1]);
         if (with_pv) o[2][pqt] = M::mfma(as_frag<frag>(vs[2]), pf, o[2][pqt]);
         if (with_pv) o[3][pqt] = M::mfma(as_frag<frag>(vs[3]), pf, o[3][pqt]);
-        if (kOnes && with_pv) lacc[pqt] = M::mfma(as_frag<frag>(ones), pf, lacc[pqt]);
+        if (with_pv) lacc[pqt] = M::mfma(as_frag<frag>(ones), pf, lacc[pqt]);
     };
 
-    // The whole key loop for this block's 256 queries; kSafe as in attn_flash8.hip (false: the reference exponent is the row max of
-    // the first 32 keys and never moves; true: online softmax, run only when the fast form's row sum left its range).
+    // The whole key loop for this block's 256 queries. Two forms of the SAME arithmetic:
+    //   kSafe = false (tried first): the reference exponent m is the row max of the FIRST 32 keys and never moves. Nothing about
+    //     softmax needs the true maximum: P = 2^(s - m) / sum is exact for any m as long as nothing over- or underflows, fp32 / bf16
+    //     keep their relative precision at any magnitude, and keys far below m are as negligible against the first block's own
+    //     maximum (P = 1) as against the true one. Dropping the per-block max takes the v_max3 chain, the lane swaps and a
+    //     compare-and-branch per tile off the issue port that bounds this kernel.
+    //   kSafe = true: the usual online softmax (max per 32-key block, rescale when it grows by more than 2^8). Run only if the fast
+    //     form's row sum left [0, 2^100] ([0, 2^15] in f16, where P must fit the type; or became NaN) for any query of the block —
+    //     i.e. some score exceeded the first block's maximum by ~100 / log2(e) = 69 — everything is then recomputed from scratch.
     auto run = [&](auto safe_c) __attribute__((always_inline)) {
         constexpr bool kSafe = decltype(safe_c)::value;
 #pragma unroll
@@ -353,6 +359,13 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
             const bool gr[2] = {rm[0] * sc_mul > kRescaleThreshold, rm[1] * sc_mul > kRescaleThreshold};
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(gr[0] || gr[1]) != 0ull, 0)) rescale(sc, gr, rm, false);   // wave-uniform, rare
         };
+        // Fragments are requested TWO quarters before their use (measured: an MFMA that waits on its K fragment costs 19 % of the
+        // kernel), also across the tile boundary: while tile t runs, tiles t and t + 1 are complete in LDS (the closing wait of tile
+        // t - 1 covered tile t + 1), so its last two quarters request the first two of tile t + 1. The scheduling fences keep the
+        // quarters apart (left alone, the scheduler hoists every LDS read of a tile and the allocator runs out of registers).
+        // Fast form, software-pipelined: the MFMAs of a quarter are the S' MFMAs and the P V MFMAs of the PREVIOUS quarter (`pend`),
+        // the VALU work is the P of THIS quarter — independent of each other, so an in-order wave never waits for its own pack
+        // before a matrix instruction. Safe form: a quarter multiplies its own P (a rescale must find nothing pending).
         u32x4 pend = u32x4{0, 0, 0, 0};                              // fast form: the P fragment whose P V is still to be issued
         // One 64-key tile = four quarters; a quarter = one query tile of one 32-key block on the VALU (8 exp, 8 adds, 4 packs)
         // beside 8 MFMAs: the S' of one key tile of the other block and the P V of the PREVIOUS quarter's P (fast form) or of its
@@ -422,19 +435,20 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // trailing (unused) pieces must land before the ring is reused / released
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
-            // kLse with kOnes: `out` is normalised by the sum of the ROUNDED probabilities as always; the row statistic handed to the
+            // kLse: `out` is normalised by the sum of the ROUNDED probabilities as always; the row statistic handed to the
             // backward is the sum of the unrounded ones (the backward recomputes P in fp32), kept on the VALU beside it
-            if (kLse && kOnes) l_exact[qt] = group_sum(l[qt] + rsum[qt]);
-            l[qt] = group_sum(kOnes ? lacc[qt][0] : l[qt] + rsum[qt]);   // the four lane groups hold disjoint keys (kOnes: the sum sits in group 0, zeros elsewhere)
-            if (kLse && !kOnes) l_exact[qt] = l[qt];
+            if (kLse) l_exact[qt] = group_sum(l[qt] + rsum[qt]);     // the four lane groups hold disjoint keys
+            l[qt] = group_sum(lacc[qt][0]);                          // (the sum sits in group 0, zeros elsewhere)
         }
     };
 
     MVI_AS3 uint32_t* const redo_flag = (MVI_AS3 uint32_t*)(lds + kLdsBytes);
     if (tid == 0) *redo_flag = 0u;                               // ordered before any read by the barriers of run()
     run(std::false_type{});
+    // block-wide vote (the waves share the K / V ring and its barriers, so they repeat together or not at all)
+    // (f16: P itself is packed to f16, which ends at 65504 — a row sum of at most 2^15 proves that no P of the row was larger)
     const float l_limit = std::is_same<T, __half>::value ? 0x1p15f : 0x1p100f;
-    // Compared as BIT PATTERNS: with the row sums from the matrix pipe (kOnes) a probability that overflowed the type (f16: > 65504)
+    // Compared as BIT PATTERNS: with the row sums from the matrix pipe a probability that overflowed the type (f16: > 65504)
     // gives 0 x inf = NaN in the rows of the ones tile that hold zeros, i.e. a NaN sum — and this file is compiled with
     // -fno-honor-nans, under which `!(l <= limit)` may be folded to `l > limit` (false for NaN). Sums are >= 0: |bits| orders them,
     // and every inf / NaN pattern is above every finite limit.
@@ -466,9 +480,11 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
 
 }  // namespace f8m
 
+// fold: the kernel without the per-score multiply (!kExact) — q carries scale * log2(e) already (q_log2: the prologue then multiplies
+// Q by exactly 1) or gets it rounded in; the caller decides (attention_folds_scale, attn_api.hip) and the backward is told the same
 template <typename T>
 int attn_flash8m16_launch(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk,
-                          float scale, bool q_log2, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs, float* lse) {
+                          float scale, bool q_log2, bool fold, hipStream_t st, int64_t q_rs, int64_t kv_rs, int64_t o_rs, float* lse) {
     using namespace f8m;
     const int64_t hd = (int64_t)H * kD;
     if (q_rs == 0) q_rs = hd;
@@ -479,31 +495,24 @@ int attn_flash8m16_launch(const void* q, const void* k, const void* v, void* out
     const int64_t total = (int64_t)B * H * q_blocks;
     if (total > 0x7FFFFFFFll) return MVI_EINVAL;
     if ((int64_t)Sk * kv_rs * 2 > 0xFFFFFFFFll) return MVI_EINVAL;       // 32-bit byte offsets inside one batch entry
+    // more than 64 KiB of dynamic LDS needs the opt-in attribute, once per device and instantiation
     static unsigned long long attr_set = 0ull;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MVI_EHIP;
-    static const int fold_env = getenv("MVI_ATTN_FOLD_SCALE") ? atoi(getenv("MVI_ATTN_FOLD_SCALE")) : -1;
-    const bool fold = q_log2 || (fold_env >= 0 ? fold_env != 0 : std::is_same<T, __half>::value);     // (attn_flash8.hip)
-    static const int mode = getenv("MVI_ATTN_MFMA16") ? atoi(getenv("MVI_ATTN_MFMA16")) : 2;          // 1: row sums on the VALU (A/B), otherwise on the matrix pipe
-    const bool ones = mode != 1;
     if (!((attr_set >> dev) & 1ull)) {
-        const void* all[8] = {reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, false>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, false>),
-                              reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, true>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, true>),
-                              reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, false, true>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, false, true>),
-                              reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, true, true>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, true, true>)};
+        const void* all[4] = {reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false>),
+                              reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, true>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, true>)};
         for (const void* f : all)
             if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + 16) != hipSuccess) return MVI_EHIP;
         attr_set |= 1ull << dev;
     }
-    auto kern = lse ? (ones ? (fold ? &attn_flash8m16_kernel<T, false, true, true> : &attn_flash8m16_kernel<T, true, true, true>)
-                            : (fold ? &attn_flash8m16_kernel<T, false, false, true> : &attn_flash8m16_kernel<T, true, false, true>))
-                    : (ones ? (fold ? &attn_flash8m16_kernel<T, false, true> : &attn_flash8m16_kernel<T, true, true>)
-                            : (fold ? &attn_flash8m16_kernel<T, false, false> : &attn_flash8m16_kernel<T, true, false>));
+    auto kern = lse ? (fold ? &attn_flash8m16_kernel<T, false, true> : &attn_flash8m16_kernel<T, true, true>)
+                    : (fold ? &attn_flash8m16_kernel<T, false> : &attn_flash8m16_kernel<T, true>);
     hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(64 * kWaves), kLdsBytes + 16, st, (const T*)q, (const T*)k, (const T*)v,
                        (T*)out, H, Sq, Sk, q_log2 ? 1.0f : scale * 1.4426950408889634f, q_blocks, (int)total, q_rs, kv_rs, o_rs, lse);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
-template int attn_flash8m16_launch<__hip_bfloat16>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, hipStream_t, int64_t, int64_t, int64_t, float*);
-template int attn_flash8m16_launch<__half>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, hipStream_t, int64_t, int64_t, int64_t, float*);
+template int attn_flash8m16_launch<__hip_bfloat16>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, bool, hipStream_t, int64_t, int64_t, int64_t, float*);
+template int attn_flash8m16_launch<__half>(const void*, const void*, const void*, void*, int, int, int, int, float, bool, bool, hipStream_t, int64_t, int64_t, int64_t, float*);
 
 }  // namespace mvi

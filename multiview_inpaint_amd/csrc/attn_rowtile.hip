@@ -17,10 +17,9 @@
 
 #include "../../include/mvi_raster.h"
 #include "../../include/mvi_unet_ops.h"
+#include "attn_launch.h"
 
 namespace mvi {
-
-int unet_fail(int code, const char* msg);
 
 template <typename T> __device__ __forceinline__ float to_f(T v);
 template <> __device__ __forceinline__ float to_f<float>(float v) { return v; }

@@ -17,25 +17,16 @@
 //                                C layout: lane (query l & 15, g) holds channels 16 tile + 4 g + r: one 8-byte store per tile.
 // A wave walks problems grid-stride (neighbouring waves work on neighbouring 128-byte segments of every frame) and loads the next
 // problem's fragments before it computes the current one.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "../../include/mvi_raster.h"
 #include "../../include/mvi_unet_ops.h"
+#include "attn_launch.h"
+#include "mfma_common.h"
 
 namespace mvi {
 namespace at16 {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 constexpr int kD = 64;
 constexpr int kWaves = 4;                            // waves per block, one problem each at a time
@@ -43,25 +34,12 @@ constexpr int kVRow = 136;                           // bytes per V row in LDS (
 constexpr int kVTile = 16 * kVRow;
 
 template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> {
-    using frag = bf16x8;
+template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
     __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        bf16x2 r = __builtin_convertvector(f, bf16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
 };
-template <> struct Mma<__half> {
-    using frag = f16x8;
+template <> struct Mma<__half> : MmaType<__half> {
     __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        f16x2 r = __builtin_convertvector(f, f16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
 };
-template <typename F> __device__ __forceinline__ F as_frag(u32x4 v) { return *reinterpret_cast<F*>(&v); }
 
 struct Operands {                                    // one problem's global loads, in flight while the previous problem computes
     u32x4 kq[4];                                     // K step 0, 1, Q step 0, 1 (frame T - 1 again for the rows >= T)

@@ -6,7 +6,7 @@
 // 0.60 ms = 0.70 PFLOP/s) which geglu_kernel then reads back (0.35 ms): 0.95 ms per call, 20 ms per step. Here the value and the
 // gate of an output never leave the accumulators.
 //
-// Structure (the QK^T half of attn_flash8.hip with x in the role of Q and W in the role of K):
+// Structure (the QK^T half of attn_flash8m16.hip with x in the role of Q and W in the role of K):
 //   * block = 8 waves x 32 rows of x; a wave's 32 rows live in registers as the B operand for the whole block (20 k-steps of 16:
 //     80 registers), so x is read from HBM exactly once and never passes through LDS;
 //   * W streams through a 3-slot LDS ring by LDS-DMA in tiles of 64 rows x 640 bytes = the 32 value rows and the 32 gate rows of
@@ -19,9 +19,6 @@
 //     END of a step, behind that step's stores, and wait with a COUNTED vmcnt for everything older than the pieces just issued.
 // GELU: erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, below half an ulp of the bf16 / f16 output by four orders of magnitude)
 // with v_rcp_f32 / v_exp_f32: 14 instructions per output, branch-free.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -29,20 +26,12 @@
 
 #include "../../include/mvi_raster.h"
 #include "../../include/mvi_unet_ops.h"
+#include "mfma_common.h"
 
 namespace mvi {
 int unet_fail(int code, const char* msg);
 namespace ffg {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-#define MVI_AS3 __attribute__((address_space(3)))
 
 constexpr int kK = 320;                              // contraction length
 constexpr int kKS = kK / 32;                         // MFMA k-steps (v_mfma_f32_16x16x32)
@@ -59,26 +48,12 @@ constexpr int kPiecesPerLoader = kPieces / kLoaders; // 10
 template <typename T> struct Mma;
 // c += A B on v_mfma_f32_16x16x32, IN PLACE and in program order (tied inline assembly: csrc/linear_n320.hip, Mma, says why). The compiler
 // does not know these are matrix instructions: the wait states around ordinary reads / writes of an accumulator are written out below.
-template <> struct Mma<__hip_bfloat16> {
+template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
     __device__ static void mfma(f32x4& c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        bf16x2 r = __builtin_convertvector(f, bf16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
 };
-template <> struct Mma<__half> {
+template <> struct Mma<__half> : MmaType<__half> {
     __device__ static void mfma(f32x4& c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        f16x2 r = __builtin_convertvector(f, f16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
 };
-
-__device__ __forceinline__ void dma_piece(const void* sbase, uint32_t voff, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(sbase), "v"(voff), "s"(lds_addr) : "memory");
-}
 
 // v * gelu(g), gelu(g) = g/2 (1 + erf(g / sqrt 2)); erf(z) = sign(z) (1 - (a1 t + ... + a5 t^5) e^(-z^2)), t = 1 / (1 + p |z|), z = g / sqrt 2
 __device__ __forceinline__ float geglu1(float v, float g) {

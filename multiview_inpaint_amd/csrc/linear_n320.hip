@@ -14,16 +14,13 @@
 //     clock on this shape under load (MI355X_MICROARCH.md, DVFS item 7): every form of this kernel 9 - 11 % faster on the same box
 //     (profiles/round5_n320_mfma16_ab.txt). The MFMAs are tied inline assembly (see Mma);
 //   * W chunk [320 rows][64 k] = 40 KiB streams through a 3-slot LDS ring by LDS-DMA (128-byte rows, 16-byte chunk c of row r at
-//     slot c ^ ((r >> 1) & 7), swizzled on the source side: the K image of attn_flash8.hip, conflict-free ds_read_b128); all 8 waves
+//     slot c ^ ((r >> 1) & 7), swizzled on the source side: the K image of attn_flash8m16.hip, conflict-free ds_read_b128); all 8 waves
 //     read the same chunk; 4 loader waves issue the chunk two ahead at the END of a chunk and wait with a counted vmcnt;
 //   * a wave's own x rows go HBM -> registers directly (4 x global_load_dwordx4 per chunk — 2 row tiles x 2 k-steps, a lane holds
 //     rows n16 and 16 + n16 — one chunk ahead, double-buffered; the 4 loads of a chunk touch the same 32 lines). They are inline assembly like the DMA: a load the compiler knows about
 //     makes it wait for vmcnt(0) at the first use — the DMA pieces just issued included;
 //   * the bias is the accumulators' initial value; outputs leave through a wave-private 4 KiB LDS tile as 16-byte stores
 //     (four column tiles = one 128-byte line per row per flush) into a buffer padded to whole 256-row blocks.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -31,20 +28,12 @@
 
 #include "../../include/mvi_raster.h"
 #include "../../include/mvi_unet_ops.h"
+#include "mfma_common.h"
 
 namespace mvi {
 int unet_fail(int code, const char* msg);
 namespace ln3 {
 
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-#define MVI_AS3 __attribute__((address_space(3)))
 
 constexpr int kN = 320;                              // outputs
 constexpr int kNT = kN / 16;                         // column tiles (16 wide) per wave
@@ -59,31 +48,15 @@ constexpr int kPiecesPerLoader = kPieces / kLoaders; // 10
 constexpr int kLdsBytes = kRing * kChunkBytes + kWaves * 4096;
 
 template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> {
-    using frag = bf16x8;
+template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
     // c += A B, IN PLACE and in program order: through the builtin the register allocator took the untied form for two MFMAs in three,
     // rotated the forty 4-register accumulators through the W fragments' registers (write-after-read stalls on the next ds_read) and
     // spilled; as volatile assembly the loop below is issued as written. The compiler does not know these are matrix instructions:
     // the wait states between the last of them and the first ordinary read of an accumulator are in the kernel (mfma_settle).
     __device__ static void mfma(f32x4& c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        bf16x2 r = __builtin_convertvector(f, bf16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
-    __device__ static float lo(uint32_t w) { return __uint_as_float(w << 16); }
-    __device__ static float hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
 };
-template <> struct Mma<__half> {
-    using frag = f16x8;
+template <> struct Mma<__half> : MmaType<__half> {
     __device__ static void mfma(f32x4& c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        f16x2 r = __builtin_convertvector(f, f16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
-    __device__ static float lo(uint32_t w) { f16x2 h = *reinterpret_cast<f16x2*>(&w); return (float)h[0]; }
-    __device__ static float hi(uint32_t w) { f16x2 h = *reinterpret_cast<f16x2*>(&w); return (float)h[1]; }
 };
 
 // a pointer every lane of the wave holds the same value of, said to the compiler (the asynchronous loads take their base in scalar registers)
@@ -93,7 +66,7 @@ __device__ __forceinline__ const char* wave_uniform(const char* p) {
     return (const char*)(uintptr_t)(((uint64_t)hi << 32) | lo);
 }
 __device__ __forceinline__ void dma_piece(const void* sbase, uint32_t voff, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(wave_uniform((const char*)sbase)), "v"(voff), "s"(lds_addr) : "memory");
+    mvi::dma_piece(wave_uniform((const char*)sbase), voff, lds_addr);
 }
 // 16 bytes per lane, invisible to the compiler's wait-count bookkeeping (see the header): whoever reads the result waits first
 __device__ __forceinline__ u32x4 load16_async(const void* sbase, uint32_t voff) {

@@ -11,50 +11,27 @@
 //     A fragment of a k-step is ONE ds_read_b128 per lane: 8 consecutive channels of pixel (p + dx, row + dy);
 //   * the weights are the B operand, built once per wave in registers (20 or 12 registers);
 //   * the accumulator starts from the bias; a lane ends with 4 consecutive pixels of one output channel: SiLU, pack, one 8-byte store.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "../../include/mvi_raster.h"
 #include "../../include/mvi_unet_ops.h"
+#include "mfma_common.h"
 
 namespace mvi {
 int unet_fail(int code, const char* msg);
 namespace sc {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 constexpr int kTW = 64;                // tile width in pixels
 constexpr int kTHMax = 8;              // tile rows = waves: 8 for the 16-output forms, 4 for the 32-output form (registers, LDS)
 
 template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> {
-    using frag = bf16x8;
+template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
     __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        bf16x2 r = __builtin_convertvector(f, bf16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
 };
-template <> struct Mma<__half> {
-    using frag = f16x8;
+template <> struct Mma<__half> : MmaType<__half> {
     __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    __device__ static uint32_t pack2(float lo, float hi) {
-        f32x2 f = {lo, hi};
-        f16x2 r = __builtin_convertvector(f, f16x2);
-        return *reinterpret_cast<uint32_t*>(&r);
-    }
 };
-template <typename F> __device__ __forceinline__ F as_frag(u32x4 v) { return *reinterpret_cast<F*>(&v); }
 
 template <typename T, int CINP, int COUT, int kTH, int STRIDE>
 __global__ __launch_bounds__(64 * kTH) void stem_conv3x3_kernel(const T* __restrict__ x, const T* __restrict__ wp, const float* __restrict__ bias,

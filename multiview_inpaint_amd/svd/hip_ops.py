@@ -15,7 +15,7 @@ _ws = {}
 # (kind, start_event, end_event, work) with events recorded on the stream the kernel runs on. GroupNorm under autograd shows as
 # "groupnorm_stats_fwd" and "groupnorm_bwd" ("groupnorm_bwd_params" when the call also launched the dweight / dbias kernel).
 PROFILE = None
-# When a list: every attention call appends (kernel variant, Sq, Sk) — 0 rowtile, 4 / 8 = the 4- / 8-wave MFMA kernel
+# When a list: every attention call appends (kernel variant, Sq, Sk) — 0 rowtile, 4 / 16 = the 4- / 8-wave MFMA kernel
 # (mvi_attention_kernel_variant, the function the C dispatch itself uses). The parity tests assert from it WHICH kernel ran
 # inside a module graph.
 ATTN_VARIANTS = None
@@ -1027,7 +1027,7 @@ def group_norm_silu_tok2tok(t, num_groups, weight, bias, eps, silu, chan_bias=No
 
 
 def attention_kernel_variant(Sq, Sk, D, dtype):
-    """0 = fp32-math rowtile kernel, 4 / 8 = the 4- / 8-wave MFMA kernel (the function the C dispatch itself uses)."""
+    """0 = fp32-math rowtile kernel, 4 / 16 = the 4- / 8-wave MFMA kernel (the function the C dispatch itself uses)."""
     return int(_lib.lib().mvi_attention_kernel_variant(int(Sq), int(Sk), int(D), _DT[dtype]))
 
 

@@ -286,7 +286,7 @@ def packed_ok(x, heads, dim_head):
 
 
 def attention_scale_fold_pays(x, dim_head):
-    """Whether the self-attention of x [B, S, C] runs the 8-wave MFMA kernel (csrc/attn_flash8.hip), whose softmax is bound by
+    """Whether the self-attention of x [B, S, C] runs the 8-wave MFMA kernel (csrc/attn_flash8m16.hip), whose softmax is bound by
     vector issue: the only kernel for which a q that carries the softmax scale (CrossAttention._packed_qkv_weight(fold=True))
     is faster."""
     if not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and x.dim() == 3):

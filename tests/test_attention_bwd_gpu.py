@@ -100,7 +100,7 @@ def test_training_and_ragged_shapes_against_the_fp64_formula(case, tag):
     runs are bit-identical.
     Observed on the MI355X (rms / max multiples): training shapes 0.34 - 1.00 / 0.13 - 1.00, ragged shapes with their peaked row
     0.33 - 1.41 / 0.10 - 1.50; the largest are f16 (1, 2, 1300, 1300), dk rms 1.41 x and dq max 1.50 x — the 8-wave f16 forward rounds
-    scale * log2 e into q a second time (attn_flash8.hip `kExact`), and the backward recomputes P from the same rounded q.
+    scale * log2 e into q a second time (attn_flash8m16.hip `kExact`), and the backward recomputes P from the same rounded q.
     """
     _, hip_ops = _ops()
     B, Hh, Sq, Sk = case

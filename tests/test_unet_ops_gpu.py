@@ -144,7 +144,7 @@ def test_attention_8wave_kernel_ragged_shapes(ops, dtype, tol, B, Hh, Sq, Sk):
 
 
 def test_attention_8wave_kernel_f16_folded_scale_on_peaked_rows(ops):
-    """f16 inputs take the 8-wave kernel with softmax scale x log2(e) folded into Q (csrc/attn_flash8.hip, kExact = false: Q is
+    """f16 inputs take the 8-wave kernel with softmax scale x log2(e) folded into Q (csrc/attn_flash8m16.hip, kExact = false: Q is
     rounded a second time, to f16's 11 bits). Peaked rows are where that shows: logits of +-20 nats with the top keys competing.
     The bar is the one the exact bf16 form is held to on the same construction (attn_check 'peaky': 5e-3) — not the random-data bar."""
     B, Hh, S, D = 1, 2, 1536, 64
@@ -1179,7 +1179,7 @@ def test_hd64_nets_in_bf16_run_the_mfma_kernel_within_the_reference_autocast_bud
 @pytest.mark.parametrize("dtype,tag", [(torch.bfloat16, "bf16ac"), (torch.float16, "f16ac")])
 def test_hd64_nets_on_a_32x32_latent_run_the_8_wave_kernel_within_the_reference_autocast_budget(golden_dir, strict, dtype, tag):
     """The PRODUCTION attention kernel under the reference pin: num_head_channels = 64 on a 32x32 latent, so the level-0
-    spatial self-attention has S_q = S_k = 1024 and runs attn_flash8_kernel (8 waves, LDS-DMA ring — the kernel of every large
+    spatial self-attention has S_q = S_k = 1024 and runs attn_flash8m16_kernel (8 waves, LDS-DMA ring — the kernel of every large
     attention of the 576 x 1024 step) INSIDE the module graph; level 1 (S = 256) runs the 4-wave kernel. Which kernel ran is
     read from mvi_attention_kernel_variant, the function the C dispatch itself uses. Reference semantics:
     sgm/modules/attention.py:281-344 (softmax(q k^T d^-1/2) v, no mask); precision recipe models/csvd.py:27-31.

@@ -1,5 +1,5 @@
 // Standalone check + timing of the attention kernels through the C-ABI (no Python): used while developing
-// csrc/attn_flash8.hip. Build:  hipcc -O2 --offload-arch=gfx950 tools/attn_dev/attn_check.cpp -Iinclude
+// csrc/attn_flash8m16.hip. Build:  hipcc -O2 --offload-arch=gfx950 tools/attn_dev/attn_check.cpp -Iinclude
 //                                     -Lmultiview_inpaint_amd/csrc -lmvi_hip -Wl,-rpath,'$ORIGIN/../../multiview_inpaint_amd/csrc' -o tools/attn_dev/attn_check
 // Run:    MVI_ATTN_VARIANT=8 tools/attn_dev/attn_check            (4 = the 4-wave kernel, 8 = the 8-wave kernel)
 #include <hip/hip_runtime.h>
@@ -206,7 +206,7 @@ static void clock_mode(int B, int H, int S, int iters) {
 
 int main(int argc, char** argv) {
     const char* var = getenv("MVI_ATTN_VARIANT");
-    printf("MVI_ATTN_VARIANT=%s MVI_ATTN_MFMA16=%s\n", var ? var : "(default)", getenv("MVI_ATTN_MFMA16") ? getenv("MVI_ATTN_MFMA16") : "(default)");
+    printf("MVI_ATTN_VARIANT=%s\n", var ? var : "(default)");
     int fails = 0;
     if (argc >= 2 && !strcmp(argv[1], "bench0")) {
         g_zero_data = true;

@@ -32,7 +32,7 @@ def duration(d):
             if "attn_flash8" in r["Name"]:
                 return float(r["AverageNs"]) / 1e3, int(r["Calls"])
     return None, 0
-print("shipped attn_flash8_kernel<bf16, exact scale>, rocprofv3 --pmc (two passes) + --kernel-trace per shape; mean per dispatch")
+print("shipped attn_flash8m16_kernel<bf16, exact scale>, rocprofv3 --pmc (two passes) + --kernel-trace per shape; mean per dispatch")
 for shape, (B, H, S) in (("bench1", (28, 5, 9216)), ("bench2", (28, 10, 2304))):
     c = counters(os.path.join(out, shape + "_a")); c.update({k: v for k, v in counters(os.path.join(out, shape + "_b")).items() if k not in c})
     us, calls = duration(os.path.join(out, shape + "_t"))
