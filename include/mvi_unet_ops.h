@@ -161,6 +161,22 @@ int64_t mvi_ff_geglu_out_rows(int64_t rows);
 int mvi_ff_geglu(const void* x, const void* weight, const float* bias, void* out, int64_t rows, int64_t out_rows_capacity, int32_t K,
                  int32_t inner, int64_t x_row_stride, int64_t out_row_stride, int32_t dtype, void* stream);
 
+/* Backward of the two GEGLU forms above (training: csrc/ff_geglu_bwd.hip, csrc/geglu.hip). With h = x weight^T + bias, a = h[:, :inner],
+ * g = h[:, inner:], Phi / phi the normal cdf / pdf: da = dy g Phi(g), dg = dy a (Phi(g) + g phi(g)), dh = [da | dg], dx = dh weight.
+ *   mvi_geglu_backward: dh [rows, 2 inner] from h [rows, 2 inner] and dy [rows, inner], all contiguous, fp32 / bf16 / f16 (fp32 math);
+ *     inner a multiple of the 16-byte vector as for mvi_geglu.
+ *   mvi_ff_geglu_backward: dx [rows, K] from x, weight, bias and dy [rows, inner] for the shapes mvi_ff_geglu_backward_supported()
+ *     accepts (those of mvi_ff_geglu_supported): h is recomputed tile by tile and never stored; every dx element is written once, in
+ *     a fixed order (no atomics). dx NULL (with dh given): the contraction is skipped, dh alone is written. dh NULL: nothing
+ *     but dx is written. dh non-NULL: also receives dh [rows, 2 inner] in the I/O type (the
+ *     operand of the caller's dweight = dh^T x and dbias = column sums of dh). Row strides in elements; rows of x and weight 16-byte
+ *     aligned, rows of dy, dx and dh 8-byte aligned; bias fp32 [2 inner] or NULL. Exactly `rows` rows are stored (no padding). */
+int mvi_geglu_backward(const void* h, const void* dy, void* dh, int64_t rows, int32_t inner, int32_t dtype, void* stream);
+int mvi_ff_geglu_backward_supported(int32_t K, int32_t inner, int32_t dtype);
+int mvi_ff_geglu_backward(const void* x, const void* weight, const float* bias, const void* dy, void* dx, void* dh, int64_t rows, int32_t K,
+                          int32_t inner, int64_t x_row_stride, int64_t dy_row_stride, int64_t dx_row_stride, int64_t dh_row_stride,
+                          int32_t dtype, void* stream);
+
 /* The same kernel with a plain epilogue: out[r, j] = x[r, :] . weight[j, :] + bias[j] — nn.Linear for K = 320 (bf16 / f16,
  * out_features a multiple of 64): the bias-only projections of the level-0 transformer blocks (packed q/k/v, to_out, proj_in,
  * proj_out; sgm/modules/attention.py:281-344, :690-712), which are short-K, output-bound GEMMs the library runs at 2 TB/s. Same

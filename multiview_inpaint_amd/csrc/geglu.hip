@@ -8,6 +8,7 @@
 
 #include "../../include/mvi_raster.h"
 #include "../../include/mvi_unet_ops.h"
+#include "geglu_math.h"
 
 namespace mvi {
 int unet_fail(int code, const char* msg);
@@ -71,6 +72,37 @@ __global__ __launch_bounds__(256) void geglu_kernel(const T* __restrict__ h, T* 
     }
 }
 
+// dh[r, j] = dy[r, j] gelu(g), dh[r, inner + j] = dy[r, j] a gelu'(g) with a = h[r, j], g = h[r, inner + j]: fp32 math (geglu_math.h),
+// reads 3 inner, writes 2 inner per row
+template <typename T>
+__global__ __launch_bounds__(256) void geglu_bwd_kernel(const T* __restrict__ h, const T* __restrict__ dy, T* __restrict__ dh, int64_t rows,
+                                                        int inner) {
+    constexpr int N = GVec<T>::N;
+    const int vec_per_row = inner / N;
+    const int64_t total = rows * vec_per_row;
+    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < total; v += (int64_t)gridDim.x * 256) {
+        const int64_t r = v / vec_per_row;
+        const int j = (int)(v % vec_per_row) * N;
+        float a[N], g[N], d[N];
+        GVec<T>::load(h + r * 2 * inner + j, a);
+        GVec<T>::load(h + r * 2 * inner + inner + j, g);
+        GVec<T>::load(dy + r * inner + j, d);
+#pragma unroll
+        for (int k = 0; k < N; ++k) geglu_grad(a[k], g[k], d[k], a[k], g[k]);
+        GVec<T>::store(dh + r * 2 * inner + j, a);
+        GVec<T>::store(dh + r * 2 * inner + inner + j, g);
+    }
+}
+
+template <typename T>
+static int geglu_bwd_launch(const void* h, const void* dy, void* dh, int64_t rows, int inner, hipStream_t st) {
+    const int64_t total = rows * (inner / GVec<T>::N);
+    int64_t blocks = (total + 255) / 256;
+    if (blocks > 256 * 64) blocks = 256 * 64;             // grid-stride the rest
+    hipLaunchKernelGGL((geglu_bwd_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)h, (const T*)dy, (T*)dh, rows, inner);
+    return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
+}
+
 template <typename T>
 static int geglu_launch(const void* h, void* out, int64_t rows, int inner, hipStream_t st) {
     const int64_t total = rows * (inner / GVec<T>::N);
@@ -97,4 +129,22 @@ extern "C" int mvi_geglu(const void* h, void* out, int64_t rows, int32_t inner, 
         default: return mvi::unet_fail(MVI_EINVAL, "geglu: unknown dtype");
     }
     return rc ? mvi::unet_fail(MVI_EHIP, "geglu: kernel launch failed") : MVI_OK;
+}
+
+extern "C" int mvi_geglu_backward(const void* h, const void* dy, void* dh, int64_t rows, int32_t inner, int32_t dtype, void* stream) {
+    if (rows < 0 || inner <= 0) return mvi::unet_fail(MVI_EINVAL, "geglu backward: bad shape");
+    if (rows == 0) return MVI_OK;
+    if (!h || !dy || !dh) return mvi::unet_fail(MVI_EINVAL, "geglu backward: NULL pointer");
+    const int n = dtype == MVI_DT_F32 ? 4 : 8;
+    if (inner % n != 0 || ((uintptr_t)h | (uintptr_t)dy | (uintptr_t)dh) % 16 != 0)
+        return mvi::unet_fail(MVI_EINVAL, "geglu backward: inner must be a multiple of the 16-byte vector and pointers 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    switch (dtype) {
+        case MVI_DT_F32: rc = mvi::geglu_bwd_launch<float>(h, dy, dh, rows, inner, st); break;
+        case MVI_DT_BF16: rc = mvi::geglu_bwd_launch<__hip_bfloat16>(h, dy, dh, rows, inner, st); break;
+        case MVI_DT_F16: rc = mvi::geglu_bwd_launch<__half>(h, dy, dh, rows, inner, st); break;
+        default: return mvi::unet_fail(MVI_EINVAL, "geglu backward: unknown dtype");
+    }
+    return rc ? mvi::unet_fail(MVI_EHIP, "geglu backward: kernel launch failed") : MVI_OK;
 }

@@ -13,7 +13,9 @@ _ws = {}
 
 # Optional per-op timing for bench.py: when PROFILE is a list, every op appends
 # (kind, start_event, end_event, work) with events recorded on the stream the kernel runs on. GroupNorm under autograd shows as
-# "groupnorm_stats_fwd" and "groupnorm_bwd" ("groupnorm_bwd_params" when the call also launched the dweight / dbias kernel).
+# "groupnorm_stats_fwd" and "groupnorm_bwd" ("groupnorm_bwd_params" when the call also launched the dweight / dbias kernel),
+# GEGLU under autograd as "ff_geglu" + "ff_geglu_bwd" (the kernel alone) + "ff_geglu_dparams" (for trainable parameters: the library's
+# dweight GEMM and the dbias sum on the kernel's dh), or "geglu" + "geglu_bwd".
 PROFILE = None
 # When a list: every attention call appends (kernel variant, Sq, Sk) — 0 rowtile, 4 / 16 = the 4- / 8-wave MFMA kernel
 # (mvi_attention_kernel_variant, the function the C dispatch itself uses). The parity tests assert from it WHICH kernel ran
@@ -483,6 +485,80 @@ def ff_geglu(x, weight, bias):
         _check(L.mvi_ff_geglu(xc.data_ptr(), wc.data_ptr(), None if b is None else b.data_ptr(), full.data_ptr(), rows, cap, K, inner,
                               xc.stride(0), full.stride(0), _DT[x.dtype], _stream(x.device)), "ff_geglu")
     return out.reshape(*x.shape[:-1], inner)
+
+
+def geglu_backward(h, dy):
+    """dh [..., 2 inner] of y = geglu(h) for the upstream gradient dy [..., inner] (csrc/geglu.hip, mvi_geglu_backward): fp32 math,
+    one pass, deterministic."""
+    L = _lib.lib()
+    if h.dtype not in _DT or dy.dtype != h.dtype:
+        raise TypeError(f"geglu_backward: h and dy must share a dtype in {list(_DT)} (got {h.dtype}, {dy.dtype})")
+    inner = h.shape[-1] // 2
+    if tuple(dy.shape) != (*h.shape[:-1], inner):
+        raise ValueError(f"geglu_backward: dy must be {(*h.shape[:-1], inner)} (got {tuple(dy.shape)})")
+    hc = h if h.is_contiguous() else h.contiguous()
+    dyc = dy if dy.is_contiguous() else dy.contiguous()
+    rows = hc.numel() // max(2 * inner, 1)
+    dh = torch.empty_like(hc)
+    with torch.cuda.device(h.device), _Timed("geglu_bwd", 5.0 * rows * inner * h.element_size(), h.device):
+        _check(L.mvi_geglu_backward(hc.data_ptr(), dyc.data_ptr(), dh.data_ptr(), rows, inner, _DT[h.dtype], _stream(h.device)),
+               "geglu_backward")
+    return dh
+
+
+def ff_geglu_backward_supported(K, inner, dtype):
+    """Whether ff_geglu_backward computes this shape (mvi_ff_geglu_backward_supported, host-only: the shapes of ff_geglu_supported)."""
+    return dtype in (torch.bfloat16, torch.float16) and bool(_lib.lib().mvi_ff_geglu_backward_supported(int(K), int(inner), _DT[dtype]))
+
+
+def _ff_geglu_backward(x, weight, bias, dy, need_dx, need_dweight, need_dbias):
+    """ff_geglu_backward's body: (dx, dweight, dbias, dh), dh being the transient [rows, 2 inner] buffer the kernel stored (None where
+    no parameter gradient was asked for). The public wrapper drops dh; tests/test_geglu_bwd_gpu.py reads it for bit identity."""
+    L = _lib.lib()
+    K, inner = x.shape[-1], weight.shape[0] // 2
+    if dy.dtype != x.dtype or weight.dtype != x.dtype or tuple(dy.shape) != (*x.shape[:-1], inner):
+        raise ValueError(f"ff_geglu_backward: dy must be {(*x.shape[:-1], inner)} in x's dtype, weight in x's dtype")
+    need_dbias = need_dbias and bias is not None
+    need_dh = need_dweight or need_dbias
+    if not (need_dx or need_dh):
+        return None, None, None, None
+    xc = x.reshape(-1, K)
+    if xc.stride(1) != 1 or xc.stride(0) % 8 or xc.data_ptr() % 16:
+        xc = xc.contiguous()
+    dyc = dy.reshape(-1, inner)
+    if dyc.stride(1) != 1 or dyc.stride(0) % 4 or dyc.data_ptr() % 8:
+        dyc = dyc.contiguous()
+    wc = weight if weight.is_contiguous() and weight.data_ptr() % 16 == 0 else weight.contiguous().clone()
+    rows = xc.shape[0]
+    b = None if bias is None else _f32(bias)
+    dx = torch.empty(rows, K, dtype=x.dtype, device=x.device) if need_dx else None      # NULL: the kernel skips the contraction
+    dh = torch.empty(rows, 2 * inner, dtype=x.dtype, device=x.device) if need_dh else None
+    # the products the kernel executes (recomputation, and the contraction where dx is asked for), 2 rows K 2 inner each
+    with torch.cuda.device(x.device), _Timed("ff_geglu_bwd", (8.0 if need_dx else 4.0) * rows * K * inner, x.device):
+        _check(L.mvi_ff_geglu_backward(xc.data_ptr(), wc.data_ptr(), None if b is None else b.data_ptr(), dyc.data_ptr(),
+                                       None if dx is None else dx.data_ptr(), None if dh is None else dh.data_ptr(), rows, K, inner,
+                                       xc.stride(0), dyc.stride(0), K, 2 * inner, _DT[x.dtype], _stream(x.device)), "ff_geglu_backward")
+    dw = db = None
+    if need_dh:                                                  # the library's share, timed as a kind of its own
+        with torch.cuda.device(x.device), _Timed("ff_geglu_dparams", (4.0 * rows * K * inner) if need_dweight else 0.0, x.device):
+            if need_dweight:
+                dw = dh.t() @ xc
+            if need_dbias:
+                db = dh.sum(0, dtype=torch.float32)
+    return (None if dx is None else dx.reshape(x.shape)), dw, db, dh
+
+
+def ff_geglu_backward(x, weight, bias, dy, need_dx=True, need_dparams=True, need_dweight=None, need_dbias=None):
+    """(dx, dweight, dbias) of y = ff_geglu(x, weight, bias) for the upstream gradient dy [..., inner] (csrc/ff_geglu_bwd.hip): the
+    projection is recomputed tile by tile, gated in registers and contracted into dx — no [rows, 2 inner] tensor unless a parameter
+    gradient is asked for, which has the kernel store dh in the I/O type for dweight = dh^T x (one library GEMM, fp32 accumulation,
+    rounded to x.dtype) and dbias = the fp32 column sums of dh (bias given). need_dparams asks for both; need_dweight / need_dbias
+    override it one by one (only the bias trainable: no GEMM). Without need_dx the kernel skips the contraction and writes dh only.
+    dh is freed on return. dx and dbias are run-to-run identical; dweight is the library GEMM's. None is returned in place of what
+    was not asked for. PROFILE kinds: ff_geglu_bwd (the kernel), ff_geglu_dparams (the GEMM and the column sum)."""
+    need_dweight = need_dparams if need_dweight is None else need_dweight
+    need_dbias = need_dparams if need_dbias is None else need_dbias
+    return _ff_geglu_backward(x, weight, bias, dy, bool(need_dx), bool(need_dweight), bool(need_dbias))[:3]
 
 
 def ff_geglu_n320_supported(K, inner, dtype):

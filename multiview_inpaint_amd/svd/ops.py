@@ -6,9 +6,11 @@ reference's own CPU-runnable case, not a fallback for the GPU.
 
 Under autograd (ControlNet training — SURVEY.md §2 row 21) attention stays on the HIP path, forward and backward
 (csrc/attn_bwd.hip: `attention` for bf16 / f16 with D = 64 and more than 32 keys, `attention_temporal` for every shape its
-forward takes), and so does GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip: `group_norm`, `group_norm_frames`, `group_norm_tokens`).
+forward takes), and so do GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip: `group_norm`, `group_norm_frames`, `group_norm_tokens`) and GEGLU
+(csrc/ff_geglu_bwd.hip: `linear_geglu` at K = 320 in bf16 / f16, the projection recomputed, never stored; csrc/geglu.hip: `geglu`;
+from the sizes at which they were measured faster, `linear_geglu_backward_pays` / `geglu_backward_pays`).
 Every other kernel is forward-only: a GPU tensor that requires grad goes through PyTorch-ROCm's differentiable ops there
-(GEGLU, the projections and convolutions, the token-major `group_norm_tok2tok`).
+(the projections and convolutions, the LayerNorm fusions, the token-major `group_norm_tok2tok`).
 
 Reference ops: GroupNorm32 + SiLU (sgm/modules/diffusionmodules/util.py:259-276,
 openaimodel.py:257-261,292-305), Normalize (sgm/modules/attention.py:125-128),
@@ -20,7 +22,7 @@ import torch
 import torch.nn.functional as F
 
 # A GPU tensor leaves the HIP path for one of two reasons, treated differently:
-#   * it requires grad and the op has no HIP backward (everything but attention and GroupNorm): PyTorch-ROCm's differentiable ops run — the
+#   * it requires grad and the op has no HIP backward (everything but attention, GroupNorm and GEGLU): PyTorch-ROCm's differentiable ops run — the
 #     documented path;
 #   * a shape / contiguity gate of a kernel fails under no_grad: that RAISES by default (STRICT_GATES; since round 3) — an
 #     inference call never silently runs PyTorch ops in place of the kernels. MVI_STRICT=0 allows the substitute again
@@ -357,12 +359,105 @@ def attention_temporal(q, k, v, heads, T):
     return o.reshape(bo, S, T, HD).transpose(1, 2).reshape(BT, S, HD)
 
 
+# The HIP backward of GEGLU (csrc/ff_geglu_bwd.hip, csrc/geglu.hip). MVI_FF_GEGLU_BWD=0 (or ops.FF_GEGLU_BACKWARD = False): GEGLU under
+# autograd takes PyTorch-ROCm's differentiable ops again (F.linear, chunk, gelu, mul), as every op without a HIP backward does.
+FF_GEGLU_BACKWARD = os.environ.get("MVI_FF_GEGLU_BWD", "1") != "0"
+# The smallest measured size of each class at which the HIP route won in BOTH bench runs (profiles/geglu_bwd_bench.json, bf16 measured
+# first, and profiles/geglu_bwd_bench_f16_first.json); a dtype without an entry was not measured and is not routed.
+FF_GEGLU_BACKWARD_MIN_ROWS = {torch.float16: 14 * 3072, torch.bfloat16: 28 * 3072}
+GEGLU_BACKWARD_MIN_ELEMENTS = {torch.float16: 10752 * 2560, torch.bfloat16: 10752 * 2560}      # rows * inner
+
+
+def linear_geglu_backward_pays(rows, K, inner, dtype, need_dparams):
+    """Whether ff_geglu forward + the fused backward is faster than the PyTorch-ROCm route (F.linear, chunk, gelu, mul and their
+    backward) for this shape class — the routing's second question after hip_ops.ff_geglu_backward_supported. Measured by
+    tools/bench_geglu_bwd.py (profiles/geglu_bwd_bench.json; DESIGN.md 'GEGLU under autograd'): forward + backward by device events,
+    the two routes alternating in one process, 9 pairs, medians; a class goes to HIP only where its median beats the PyTorch route's
+    by more than that route's spread. K = 320, inner = 1280, ms HIP / PyTorch (spread), dx only | all gradients:
+      f16   14 x 3072 rows  0.498 / 0.800 (0.116) | 0.773 / 1.096 (0.019)    wins
+      f16   28 x 3072       0.741 / 1.561 (0.027) | 1.295 / 2.087 (0.137)    wins
+      f16   14 x 9216       0.925 / 2.227 (0.044) | 1.711 / 3.055 (0.412)    wins
+      bf16  14 x 3072       0.490 / 0.790 (0.806) | 0.966 / 1.151 (0.491)    ahead by the median, inside the spread: a tie, PyTorch
+      bf16  28 x 3072       0.729 / 1.552 (0.103) | 1.239 / 2.079 (0.011)    wins
+      bf16  14 x 9216       0.913 / 2.218 (0.031) | 1.663 / 2.994 (0.115)    wins
+    A second run on another machine with f16 measured first (profiles/geglu_bwd_bench_f16_first.json) won in every class, bf16 at
+    14 x 3072 rows included (0.507 / 0.786 (0.044) | 0.795 / 1.096 (0.066)): the tie above was one slow PyTorch pair in what that process
+    measured first, not a property of the kernel (same arithmetic, same bytes in both types). A class is routed where it won in BOTH
+    runs, so bf16 at 14 x 3072 rows stays on PyTorch. The dx-only and the all-gradient class have the same verdict at every measured
+    size, so need_dparams does not move the line. Nothing below 14 x 3072 rows, nothing between the measured sizes and no other
+    inner was measured: the line is the smallest size of the dtype that won twice, and everything below it stays on PyTorch."""
+    return rows >= FF_GEGLU_BACKWARD_MIN_ROWS.get(dtype, float("inf"))
+
+
+def geglu_backward_pays(rows, inner, dtype):
+    """The same question for the elementwise pair geglu / geglu_backward (one pass each) against chunk + gelu + mul and their
+    backward (three passes each and a cat of the two gradient halves), same bench, same rule. (rows, inner) of levels 1 - 3, ms HIP /
+    PyTorch (spread), f16 | bf16:
+      32256 x 2560 (82.6 M gated elements)  0.277 / 0.844 (0.021) | 0.266 / 0.840 (0.015)    wins | wins
+       8064 x 5120 (41.3 M)                 0.139 / 0.408 (0.004) | 0.177 / 0.424 (0.047)    wins | wins
+      10752 x 2560 (27.5 M)                 0.094 / 0.256 (0.005) | 0.139 / 0.272 (0.014)    wins | wins
+       2688 x 5120 (13.8 M)                 0.076 / 0.125 (0.004) | 0.133 / 0.137 (0.008)    wins | tie
+       2016 x 5120 (10.3 M)                 0.072 / 0.101 (0.007) | 0.149 / 0.124 (0.024)    wins | loses
+        672 x 5120 (3.4 M)                  0.072 / 0.065 (0.004) | 0.124 / 0.098 (0.136)    loses | loses
+    Small shapes are bound by the Function's host side, and that differs by run, not by type: in the second run (f16 first, another
+    machine) the HIP route took 0.15 ms at every small size in BOTH types and lost at 13.8 M (0.153 / 0.132 f16, 0.162 / 0.138 bf16),
+    10.3 M and 3.4 M, while 27.5 M and above won again in both (0.154 / 0.259 f16, 0.181 / 0.267 bf16 at 27.5 M). A class is routed
+    where it won in BOTH runs: from 27.5 M gated elements in either type. fp32 I/O was not measured and is not routed (its kernel
+    is parity-tested and reachable through hip_ops.geglu_backward)."""
+    return rows * inner >= GEGLU_BACKWARD_MIN_ELEMENTS.get(dtype, float("inf"))
+
+
+class _GegluFn(torch.autograd.Function):
+    """geglu on the HIP kernel with its one-pass HIP backward. Holds h only; nothing is cached outside ctx."""
+
+    @staticmethod
+    def forward(ctx, h):
+        from . import hip_ops
+        hc = h if h.is_contiguous() else h.contiguous()
+        ctx.save_for_backward(hc)
+        return hip_ops.geglu(hc)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        (h,) = ctx.saved_tensors
+        return hip_ops.geglu_backward(h, dy)
+
+
+class _LinearGegluFn(torch.autograd.Function):
+    """linear_geglu on the fused kernel (csrc/ff_geglu.hip) with the fused HIP backward (csrc/ff_geglu_bwd.hip). Holds x, weight and
+    bias only — the [rows, 2 inner] projection exists neither between forward and backward nor, for frozen weights, during the
+    backward; nothing is cached outside ctx, so torch.utils.checkpoint may re-run the forward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        from . import hip_ops
+        ctx.save_for_backward(x, weight, bias)
+        return hip_ops.ff_geglu(x, weight, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        x, weight, bias = ctx.saved_tensors
+        n = ctx.needs_input_grad
+        need_db = bias is not None and n[2]
+        dx, dw, db = hip_ops.ff_geglu_backward(x, weight, bias, dy.contiguous(), need_dx=n[0], need_dparams=n[1] or need_db,
+                                               need_dweight=n[1], need_dbias=need_db)
+        return (dx if n[0] else None, dw.to(weight.dtype) if n[1] else None, db.to(bias.dtype) if need_db else None)
+
+
 def geglu(h):
     """h [..., 2*inner] -> h[..., :inner] * gelu(h[..., inner:]) (sgm/modules/attention.py:93-95)."""
     inner = h.shape[-1] // 2
     if h.is_cuda and not _needs_autograd(h) and inner % 8 == 0:
         from . import hip_ops
         return hip_ops.geglu(h)
+    if h.is_cuda and FF_GEGLU_BACKWARD and _needs_autograd(h) and h.dtype in (torch.float32, torch.bfloat16, torch.float16) \
+            and inner > 0 and h.shape[-1] == 2 * inner and inner % (4 if h.dtype == torch.float32 else 8) == 0 \
+            and geglu_backward_pays(h.numel() // (2 * inner), inner, h.dtype):
+        return _GegluFn.apply(h)
     _fallback(h, "geglu", _why(h))
     a, gate = h.chunk(2, dim=-1)
     return a * F.gelu(gate)
@@ -392,6 +487,14 @@ def linear_geglu(x, weight, bias=None):
         if FF_GEGLU_N320 and x.shape[-1] in FF_GEGLU_N320_K and rows >= FF_GEGLU_N320_MIN_ROWS \
                 and hip_ops.ff_geglu_n320_supported(x.shape[-1], weight.shape[0] // 2, x.dtype):
             return hip_ops.ff_geglu_n320(x, weight, bias)
+    if K320_KERNELS and FF_GEGLU_BACKWARD and x.is_cuda and _needs_autograd(x, weight, bias) and x.dtype == weight.dtype \
+            and (bias is None or bias.is_cuda) and weight.dim() == 2 and weight.shape[1] == x.shape[-1]:
+        from . import hip_ops
+        rows = x.numel() // max(x.shape[-1], 1)
+        inner = weight.shape[0] // 2
+        if hip_ops.ff_geglu_backward_supported(x.shape[-1], inner, x.dtype) \
+                and linear_geglu_backward_pays(rows, x.shape[-1], inner, x.dtype, weight.requires_grad or (bias is not None and bias.requires_grad)):
+            return _LinearGegluFn.apply(x, weight, bias)
     return geglu(F.linear(x, weight, bias))
 
 
