@@ -289,6 +289,25 @@ int mvi_add_layernorm(const void* x, const void* h, const void* row, int64_t row
                       void* stream);
 int mvi_layernorm_supported(int32_t C, int32_t dtype);
 
+/* Backward of mvi_add_layernorm (training: csrc/layernorm_bwd.hip), deterministic, one pass over the tensors, fp32 math:
+ *     xh = (s - mean) rstd with mean, rstd recomputed from s in the forward's order of operations;  t = gy weight
+ *     gS = rstd (t - mean_c(t) - xh mean_c(t xh)) + gs         g_out = gS + gs_pre  (= dx = dh: one tensor, rounded once)
+ *     drow[g] = sum of the unrounded gS over the row_div rows of run g;  dweight = sum_r gy xh;  dbias = sum_r gy
+ * s [R, C]: the forward's s output (x itself for the plain LayerNorm). gy, gs, gs_pre [R, C] in s's dtype are the gradients of the
+ * forward's y, s, s_pre; NULL = absent (zero). Outputs: g_out [R, C] in s's dtype; dweight, dbias fp32 [C]; drow fp32 [R / row_div, C]
+ * (row_div must divide R; it is read only when drow is asked for); NULL = not computed. All tensors contiguous and 16-byte aligned.
+ * workspace: mvi_add_layernorm_backward_workspace_bytes(R, C, row_div, flags) bytes, flags = the MVI_LNB_* of the non-NULL outputs
+ * (0 bytes for g_out alone, and for drow at row_div == 1), 16-byte aligned, caller-owned.
+ * mvi_add_layernorm_backward_supported: host-only; the gate of mvi_layernorm_supported, not narrowed. */
+#define MVI_LNB_GRAD 1
+#define MVI_LNB_PARAMS 2
+#define MVI_LNB_DROW 4
+int mvi_add_layernorm_backward_supported(int32_t C, int32_t dtype);
+size_t mvi_add_layernorm_backward_workspace_bytes(int64_t R, int32_t C, int64_t row_div, int32_t flags);
+int mvi_add_layernorm_backward(const void* gy, const void* s, const void* gs, const void* gs_pre, const float* weight, int64_t row_div,
+                               float eps, void* g_out, float* dweight, float* dbias, float* drow, void* workspace,
+                               size_t workspace_bytes, int64_t R, int32_t C, int32_t dtype, void* stream);
+
 /* out = lerp(x + h, base, alpha[r / row_div]) = alpha * base + (1 - alpha) * (x + h): the temporal block's last residual
  * add fused with AlphaBlender (svd_inpaint1/sgm/modules/diffusionmodules/util.py:312-372; video_attention.py:290-294).
  * alpha: fp32 [ceil(R / row_div)]; h optional. PyTorch's two-sided lerp formula. */

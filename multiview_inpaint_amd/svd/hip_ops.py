@@ -962,6 +962,65 @@ def add_layer_norm(x, weight, bias, eps, h=None, row=None, ret_pre=False):
     return y, s, s_pre
 
 
+LNB_GRAD, LNB_PARAMS, LNB_DROW = 1, 2, 4       # MVI_LNB_* of include/mvi_unet_ops.h
+
+
+def add_layer_norm_backward_supported(C_, dtype):
+    """Whether add_layer_norm_backward computes this width (mvi_add_layernorm_backward_supported, host-only: layernorm_supported's gate)."""
+    return dtype in _DT and bool(_lib.lib().mvi_add_layernorm_backward_supported(int(C_), _DT[dtype]))
+
+
+def add_layer_norm_backward_workspace_bytes(R, C_, row_div, need_dparams, need_drow):
+    """Bytes of the fp32 partial rows add_layer_norm_backward needs for these outputs (0 without column sums)."""
+    flags = LNB_GRAD | (LNB_PARAMS if need_dparams else 0) | (LNB_DROW if need_drow else 0)
+    return int(_lib.lib().mvi_add_layernorm_backward_workspace_bytes(int(R), int(C_), int(row_div), flags))
+
+
+def add_layer_norm_backward(s, weight, eps, gy=None, gs=None, gs_pre=None, row_groups=None, need_dx=True, need_dparams=True):
+    """(g, dweight, dbias, drow) of (y, s, s_pre) = add_layer_norm(x, weight, bias, eps, h, row) for the upstream gradients gy, gs,
+    gs_pre of its three outputs, each optional (csrc/layernorm_bwd.hip). s [..., C]: the forward's s (x for the plain norm). g, in
+    s's dtype and shape, is the gradient of x AND of h (one tensor); dweight, dbias fp32 [C]; drow fp32 [row_groups, C], asked for by
+    giving row_groups (the G of the forward's row). Outputs not asked for are None and cost nothing. Deterministic."""
+    L = _lib.lib()
+    if s.dtype not in _DT:
+        raise TypeError(f"add_layer_norm_backward: unsupported dtype {s.dtype}")
+    Cc = s.shape[-1]
+    sc = s if s.is_contiguous() else s.contiguous()
+    R = sc.numel() // Cc
+    grads = []
+    for name, g in (("gy", gy), ("gs", gs), ("gs_pre", gs_pre)):
+        if g is not None:
+            if g.shape != s.shape or g.dtype != s.dtype:
+                raise ValueError(f"add_layer_norm_backward: {name} must match s in shape and dtype")
+            g = g if g.is_contiguous() else g.contiguous()
+        grads.append(g)
+    row_div = 1
+    if row_groups is not None:
+        if row_groups <= 0 or R % row_groups:
+            raise ValueError(f"add_layer_norm_backward: {R} rows do not split into {row_groups} equal runs")
+        row_div = R // row_groups
+    f32 = dict(dtype=torch.float32, device=s.device)
+    g_out = torch.empty_like(sc) if need_dx else None
+    dw = torch.empty(Cc, **f32) if need_dparams else None
+    db = torch.empty(Cc, **f32) if need_dparams else None
+    drow = torch.empty((row_groups, Cc), **f32) if row_groups is not None else None
+    if R == 0 or not (need_dx or need_dparams or drow is not None):
+        for t in (dw, db, drow):
+            if t is not None:
+                t.zero_()
+        return g_out, dw, db, drow
+    flags = (LNB_GRAD if need_dx else 0) | (LNB_PARAMS if need_dparams else 0) | (LNB_DROW if drow is not None else 0)
+    nbytes = int(L.mvi_add_layernorm_backward_workspace_bytes(R, Cc, row_div, flags))
+    ws = _workspace(s.device, nbytes) if nbytes else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    n_io = 1 + sum(g is not None for g in grads) + bool(need_dx)
+    with torch.cuda.device(s.device), _Timed("add_layernorm_bwd", float(n_io) * sc.numel() * sc.element_size(), s.device):
+        _check(L.mvi_add_layernorm_backward(ptr(grads[0]), sc.data_ptr(), ptr(grads[1]), ptr(grads[2]), _f32(weight).data_ptr(), row_div,
+                                            float(eps), ptr(g_out), ptr(dw), ptr(db), ptr(drow), ptr(ws), 0 if ws is None else ws.numel(),
+                                            R, Cc, _DT[s.dtype], _stream(s.device)), "add_layer_norm_backward")
+    return g_out, dw, db, drow
+
+
 def add_lerp(x, h, base, alpha):
     """lerp(x + h, base, alpha) with alpha [G] fp32 broadcast over equal runs of the rows of x [..., C]."""
     L = _lib.lib()

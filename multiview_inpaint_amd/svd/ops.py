@@ -8,9 +8,12 @@ Under autograd (ControlNet training — SURVEY.md §2 row 21) attention stays on
 (csrc/attn_bwd.hip: `attention` for bf16 / f16 with D = 64 and more than 32 keys, `attention_temporal` for every shape its
 forward takes), and so do GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip: `group_norm`, `group_norm_frames`, `group_norm_tokens`) and GEGLU
 (csrc/ff_geglu_bwd.hip: `linear_geglu` at K = 320 in bf16 / f16, the projection recomputed, never stored; csrc/geglu.hip: `geglu`;
-from the sizes at which they were measured faster, `linear_geglu_backward_pays` / `geglu_backward_pays`).
+from the sizes at which they were measured faster, `linear_geglu_backward_pays` / `geglu_backward_pays`), and the residual add(s) +
+LayerNorm of the transformer blocks (csrc/layernorm_bwd.hip: `add_layer_norm` for every width its forward takes, where
+`add_layer_norm_backward_pays` says so).
 Every other kernel is forward-only: a GPU tensor that requires grad goes through PyTorch-ROCm's differentiable ops there
-(the projections and convolutions, the LayerNorm fusions, the token-major `group_norm_tok2tok`).
+(the projections and convolutions — `linear_add_layer_norm` under grad is `linear_module` + `add_layer_norm` —, `add_lerp`, the
+token-major `group_norm_tok2tok`).
 
 Reference ops: GroupNorm32 + SiLU (sgm/modules/diffusionmodules/util.py:259-276,
 openaimodel.py:257-261,292-305), Normalize (sgm/modules/attention.py:125-128),
@@ -22,8 +25,8 @@ import torch
 import torch.nn.functional as F
 
 # A GPU tensor leaves the HIP path for one of two reasons, treated differently:
-#   * it requires grad and the op has no HIP backward (everything but attention, GroupNorm and GEGLU): PyTorch-ROCm's differentiable ops run — the
-#     documented path;
+#   * it requires grad and the op has no HIP backward (everything but attention, GroupNorm, GEGLU and add_layer_norm): PyTorch-ROCm's
+#     differentiable ops run — the documented path;
 #   * a shape / contiguity gate of a kernel fails under no_grad: that RAISES by default (STRICT_GATES; since round 3) — an
 #     inference call never silently runs PyTorch ops in place of the kernels. MVI_STRICT=0 allows the substitute again
 #     (recorded in FALLBACKS).
@@ -592,17 +595,111 @@ def bias_silu(h, bias):
     return F.silu(h)
 
 
+# The HIP backward of add_layer_norm (csrc/layernorm_bwd.hip). MVI_LN_BWD=0 (or ops.LAYERNORM_BACKWARD = False): add_layer_norm under
+# autograd takes PyTorch-ROCm's differentiable ops again (two adds and F.layer_norm), as every op without a HIP backward does.
+LAYERNORM_BACKWARD = os.environ.get("MVI_LN_BWD", "1") != "0"
+# Smallest rows * C of each (dtype, variant) class from which every measured size won, with all gradients and with the norm frozen
+# (profiles/layernorm_bwd_bench.json); a class without an entry was not measured or did not win, and is not routed. Variants: "plain"
+# (no h, no row), "add" (h only), "row" (anything with a row).
+LAYERNORM_BACKWARD_MIN_ELEMENTS = {(torch.bfloat16, "plain"): 28 * 2304 * 640, (torch.bfloat16, "add"): 28 * 2304 * 640,
+                                   (torch.bfloat16, "row"): 28 * 2304 * 640, (torch.float16, "plain"): 28 * 2304 * 640,
+                                   (torch.float16, "row"): 28 * 2304 * 640}
+
+
+def add_layer_norm_backward_pays(rows, C, dtype, variant):
+    """Whether add_layer_norm forward + the fused HIP backward is faster than the PyTorch-ROCm route (two adds, F.layer_norm and their
+    backward) for this shape class — the routing's second question after hip_ops.add_layer_norm_backward_supported. Measured by
+    tools/bench_layernorm_bwd.py (profiles/layernorm_bwd_bench.json; DESIGN.md 'Add+LayerNorm under autograd'): forward + backward by
+    device events, the two routes alternating in one process, 9 pairs, medians; a class goes to HIP only where its median beats the
+    PyTorch route's by more than that route's spread, with all gradients AND with the norm frozen. ms HIP / PyTorch (spread), all
+    gradients | frozen norm, bf16 then f16:
+      28 x 9216 x 320 (82.6 M elements)  plain 0.321 / 1.057 (0.013) | 0.213 / 0.764 (0.009)    0.410 / 1.063 (0.011) | 0.339 / 0.753 (0.009)    wins, wins
+                                         add   0.480 / 1.284 (0.037) | 0.356 / 0.990 (0.009)    0.678 / 1.288 (0.763) | 0.468 / 0.982 (0.011)    wins, TIE (one slow PyTorch pair)
+                                         row   0.699 / 1.560 (0.016) | 0.482 / 1.256 (0.010)    0.876 / 1.571 (0.233) | 0.483 / 1.241 (0.010)    wins, wins
+      28 x 2304 x 640 (41.3 M)           plain 0.205 / 0.339 (0.010) | 0.133 / 0.275 (0.003)    0.201 / 0.336 (0.008) | 0.133 / 0.269 (0.003)    wins, wins
+                                         add   0.373 / 0.477 (0.029) | 0.255 / 0.393 (0.008)    0.282 / 0.455 (0.028) | 0.197 / 0.379 (0.006)    wins, wins
+                                         row   0.459 / 0.613 (0.012) | 0.320 / 0.530 (0.003)    0.391 / 0.591 (0.007) | 0.272 / 0.511 (0.009)    wins, wins
+      28 x 576 x 1280 (20.6 M)           every variant loses or ties in both types (row, all gradients: 0.351 / 0.307 bf16, 0.273 / 0.267 f16)
+      14 x 3072 x 320 (13.8 M)           bf16 add 0.177 / 0.221 and row 0.223 / 0.296 win, plain loses (0.246 / 0.193); f16 loses or ties everywhere
+      14 x 768 x 640, 14 x 192 x 1280    lose everywhere (0.08 - 0.29 against 0.05 - 0.22)
+    Below 41.3 M the route is bound by the Function's host side (0.07 - 0.28 ms per forward + backward, varying within the process, against
+    0.04 - 0.24 for the PyTorch route) and the verdict is not monotone in the size, so the line is the smallest size from which every
+    measured size won: 41.3 M elements; f16 "add" tied at 82.6 M and is not routed at all. The training latent's shapes stay on PyTorch."""
+    return rows * C >= LAYERNORM_BACKWARD_MIN_ELEMENTS.get((dtype, variant), float("inf"))
+
+
+def _ln_variant(h, row):
+    return "row" if row is not None else ("add" if h is not None else "plain")
+
+
+class _AddLayerNormFn(torch.autograd.Function):
+    """add_layer_norm on its inference kernel with the fused deterministic HIP backward (csrc/layernorm_bwd.hip). Outputs: y, then s
+    when there is an h or a row, then s_pre when it is a tensor of its own (ret_pre with both h and row); an input is never returned.
+    Holds s (x for the plain norm) and the norm's weight — no statistics, nothing tensor-sized in fp32; nothing is cached outside ctx,
+    so torch.utils.checkpoint may re-run the forward. The gradients of x and h are ONE tensor."""
+
+    @staticmethod
+    def forward(ctx, x, h, row, weight, bias, eps, ret_pre):
+        from . import hip_ops
+        y, s, s_pre = hip_ops.add_layer_norm(x, weight, bias, eps, h=h, row=row, ret_pre=ret_pre)
+        own_pre = ret_pre and h is not None and row is not None
+        ctx.save_for_backward(x if s is None else s, weight)
+        ctx.set_materialize_grads(False)
+        ctx.cfg = (float(eps), None if row is None else (tuple(row.shape), row.dtype, row.numel() // x.shape[-1]), tuple(x.shape), bias.dtype)
+        if s is None:
+            return y
+        return (y, s, s_pre) if own_pre else (y, s)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy, gs=None, gs_pre=None):
+        from . import hip_ops
+        s, weight = ctx.saved_tensors
+        eps, row_info, x_shape, bias_dtype = ctx.cfg
+        n = ctx.needs_input_grad
+        need_g, need_par, need_drow = n[0] or n[1], n[3] or n[4], row_info is not None and n[2]
+        if (gy is None and gs is None and gs_pre is None) or not (need_g or need_par or need_drow):
+            return (None,) * 7
+        g, dw, db, drow = hip_ops.add_layer_norm_backward(s, weight, eps, gy=gy, gs=gs, gs_pre=gs_pre,
+                                                          row_groups=row_info[2] if need_drow else None, need_dx=need_g,
+                                                          need_dparams=need_par)
+        if g is not None:
+            g = g.reshape(x_shape)
+        return (g if n[0] else None, g if n[1] else None, drow.to(row_info[1]).reshape(row_info[0]) if need_drow else None,
+                dw.to(weight.dtype) if n[3] else None, db.to(bias_dtype) if n[4] else None, None, None)
+
+
+def _ln_hip_autograd(x, norm, h, row):
+    """Under autograd: does this add_layer_norm run _AddLayerNormFn? (switch on, affine norm, the kernels compute the width, and it pays)"""
+    if not (x.is_cuda and LAYERNORM_BACKWARD and norm.elementwise_affine and x.numel() > 0):
+        return False
+    from . import hip_ops
+    C_ = x.shape[-1]
+    if tuple(norm.normalized_shape) != (C_,) or (h is not None and (h.shape != x.shape or h.dtype != x.dtype)) \
+            or (row is not None and (row.dtype != x.dtype or row.shape[-1] != C_ or (x.numel() // C_) % max(row.numel() // C_, 1))):
+        return False
+    return (hip_ops.layernorm_supported(C_, x.dtype) and hip_ops.add_layer_norm_backward_supported(C_, x.dtype)
+            and add_layer_norm_backward_pays(x.numel() // C_, C_, x.dtype, _ln_variant(h, row)))
+
+
 def add_layer_norm(x, norm, h=None, row=None, ret_pre=False):
     """Residual add(s) fused with the next LayerNorm: s_pre = x + h, s = s_pre + row, y = norm(s) for token-major
     x [B, S, C]; `row` [G, 1, C] (G divides B*S) is broadcast over equal runs of rows — the single-token
     cross-attention row or the frame-index embedding. Returns (y, s, s_pre); s is x when h and row are None,
-    s_pre is returned only with ret_pre (and is s when row is None). `norm` is the nn.LayerNorm."""
+    s_pre is returned only with ret_pre (and is s when row is None). `norm` is the nn.LayerNorm. Under autograd the same kernel
+    runs inside _AddLayerNormFn where the HIP backward is supported and pays (add_layer_norm_backward_pays)."""
     C_ = x.shape[-1]
     if x.is_cuda and not _needs_autograd(x, h, row, norm.weight, norm.bias):
         from . import hip_ops
         if norm.elementwise_affine and hip_ops.layernorm_supported(C_, x.dtype):
             y, s, s_pre = hip_ops.add_layer_norm(x, norm.weight, norm.bias, norm.eps, h=h, row=row, ret_pre=ret_pre)
             return y, (x if s is None else s), s_pre
+    elif _ln_hip_autograd(x, norm, h, row):
+        out = _AddLayerNormFn.apply(x, h, row, norm.weight, norm.bias, norm.eps, bool(ret_pre))
+        if h is None and row is None:
+            return out, x, (x if ret_pre else None)
+        y, s = out[0], out[1]
+        return y, s, ((out[2] if len(out) == 3 else (x if h is None else s)) if ret_pre else None)
     _fallback(x, "add_layer_norm", _why(x, h, row, norm.weight, norm.bias))
     s_pre = x if h is None else x + h
     s = s_pre
