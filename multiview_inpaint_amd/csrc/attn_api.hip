@@ -6,8 +6,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
 #include "attn_launch.h"
 
 extern "C" int mvi_attention_kernel_kind(int32_t Sq, int32_t Sk, int32_t D, int32_t dtype) {
@@ -51,29 +49,25 @@ static int attention_forward_impl(const void* q, const void* k, const void* v, v
         (q_ts * esz) % 16 || (kv_ts * esz) % 16 || (o_ts * esz) % 16)
         return mvi::unet_fail(MVI_EINVAL, "attention: token strides must be 0 or >= H*D elements and 16-byte multiples");
     hipStream_t st = (hipStream_t)stream;
-    int rc;
+    const auto launched = [](int rc) { return rc ? mvi::unet_fail(rc, "attention: kernel launch failed") : MVI_OK; };
     const int variant = mvi_attention_kernel_variant(Sq, Sk, D, dtype);
-    if (variant != 0) {
-        if (variant == 16) {
-            // a q that carries scale * log2(e) runs the folded kernel with nothing left to fold, in both types
-            const bool fold = q_log2 || mvi::attention_folds_scale(variant, dtype);
-            rc = dtype == MVI_DT_BF16 ? mvi::attn_flash8m16_launch<__hip_bfloat16>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, fold, st, q_ts, kv_ts, o_ts, lse)
-                                      : mvi::attn_flash8m16_launch<__half>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, fold, st, q_ts, kv_ts, o_ts, lse);
-        } else {
-            const float sl2 = q_log2 ? 1.0f : scale * kLog2e;
-            rc = dtype == MVI_DT_BF16 ? mvi::attn_flash_launch<__hip_bfloat16>(q, k, v, out, B, H, Sq, Sk, sl2, st, q_ts, kv_ts, o_ts, lse)
-                                      : mvi::attn_flash_launch<__half>(q, k, v, out, B, H, Sq, Sk, sl2, st, q_ts, kv_ts, o_ts, lse);
-        }
-    } else {
-        if (D != 16 && D != 32 && D != 64) return mvi::unet_fail(MVI_EINVAL, "attention: head dim must be 16, 32 or 64");
-        switch (dtype) {
-            case MVI_DT_F32: rc = mvi::attn_rowtile_launch<float>(q, k, v, out, B, H, Sq, Sk, D, scale, st, 0, q_ts, kv_ts, o_ts); break;
-            case MVI_DT_BF16: rc = mvi::attn_rowtile_launch<__hip_bfloat16>(q, k, v, out, B, H, Sq, Sk, D, scale, st, 0, q_ts, kv_ts, o_ts); break;
-            case MVI_DT_F16: rc = mvi::attn_rowtile_launch<__half>(q, k, v, out, B, H, Sq, Sk, D, scale, st, 0, q_ts, kv_ts, o_ts); break;
-            default: return mvi::unet_fail(MVI_EINVAL, "attention: unknown dtype");
-        }
+    if (variant == 16) {
+        // a q that carries scale * log2(e) runs the folded kernel with nothing left to fold, in both types
+        const bool fold = q_log2 || mvi::attention_folds_scale(variant, dtype);
+        return mvi::dispatch_dtype16(dtype, "attention: unknown dtype", [&](auto t) {
+            return launched(mvi::attn_flash8m16_launch<typename decltype(t)::type>(q, k, v, out, B, H, Sq, Sk, scale, q_log2, fold, st, q_ts, kv_ts, o_ts, lse));
+        });
     }
-    return rc ? mvi::unet_fail(rc, "attention: kernel launch failed") : MVI_OK;
+    if (variant != 0) {
+        const float sl2 = q_log2 ? 1.0f : scale * kLog2e;
+        return mvi::dispatch_dtype16(dtype, "attention: unknown dtype", [&](auto t) {
+            return launched(mvi::attn_flash_launch<typename decltype(t)::type>(q, k, v, out, B, H, Sq, Sk, sl2, st, q_ts, kv_ts, o_ts, lse));
+        });
+    }
+    if (D != 16 && D != 32 && D != 64) return mvi::unet_fail(MVI_EINVAL, "attention: head dim must be 16, 32 or 64");
+    return mvi::dispatch_dtype(dtype, "attention: unknown dtype", [&](auto t) {
+        return launched(mvi::attn_rowtile_launch<typename decltype(t)::type>(q, k, v, out, B, H, Sq, Sk, D, scale, st, 0, q_ts, kv_ts, o_ts));
+    });
 }
 
 extern "C" int mvi_attention_forward(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t H,
@@ -124,19 +118,14 @@ static int attention_temporal_impl(const void* q, const void* k, const void* v, 
         return mvi::unet_fail(MVI_EINVAL, "temporal attention: token strides must be 0 or >= H*D elements");
     hipStream_t st = (hipStream_t)stream;
     const int B = Bo * S;
-    int rc;
-    if (mvi_attention_temporal_kernel_variant(T, H, D, dtype, qkv_ts, o_ts) && mvi::attn_temporal16_ok(T, D, dtype, hd, qkv_ts, o_ts, q, k, v, out)) {
-        rc = dtype == MVI_DT_BF16 ? mvi::attn_temporal16_launch<__hip_bfloat16>(q, k, v, out, Bo, T, S, H, scale, st, qkv_ts, o_ts)
-                                  : mvi::attn_temporal16_launch<__half>(q, k, v, out, Bo, T, S, H, scale, st, qkv_ts, o_ts);
-        return rc ? mvi::unet_fail(rc, "temporal attention: kernel launch failed") : MVI_OK;
-    }
-    switch (dtype) {
-        case MVI_DT_F32: rc = mvi::attn_rowtile_launch<float>(q, k, v, out, B, H, T, T, D, scale, st, S, qkv_ts, qkv_ts, o_ts); break;
-        case MVI_DT_BF16: rc = mvi::attn_rowtile_launch<__hip_bfloat16>(q, k, v, out, B, H, T, T, D, scale, st, S, qkv_ts, qkv_ts, o_ts); break;
-        case MVI_DT_F16: rc = mvi::attn_rowtile_launch<__half>(q, k, v, out, B, H, T, T, D, scale, st, S, qkv_ts, qkv_ts, o_ts); break;
-        default: return mvi::unet_fail(MVI_EINVAL, "temporal attention: unknown dtype");
-    }
-    return rc ? mvi::unet_fail(rc, "temporal attention: kernel launch failed") : MVI_OK;
+    const auto launched = [](int rc) { return rc ? mvi::unet_fail(rc, "temporal attention: kernel launch failed") : MVI_OK; };
+    if (mvi_attention_temporal_kernel_variant(T, H, D, dtype, qkv_ts, o_ts) && mvi::attn_temporal16_ok(T, D, dtype, hd, qkv_ts, o_ts, q, k, v, out))
+        return mvi::dispatch_dtype16(dtype, "temporal attention: unknown dtype", [&](auto t) {
+            return launched(mvi::attn_temporal16_launch<typename decltype(t)::type>(q, k, v, out, Bo, T, S, H, scale, st, qkv_ts, o_ts));
+        });
+    return mvi::dispatch_dtype(dtype, "temporal attention: unknown dtype", [&](auto t) {
+        return launched(mvi::attn_rowtile_launch<typename decltype(t)::type>(q, k, v, out, B, H, T, T, D, scale, st, S, qkv_ts, qkv_ts, o_ts));
+    });
 }
 
 extern "C" int mvi_attention_temporal(const void* q, const void* k, const void* v, void* out, int32_t Bo, int32_t T,

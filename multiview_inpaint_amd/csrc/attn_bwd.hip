@@ -32,8 +32,6 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
 #include "attn_launch.h"
 #include "mfma_common.h"
 
@@ -49,13 +47,7 @@ constexpr int kStride = 72;             // LDS row stride in elements (144 bytes
 constexpr int kImg = kST * kStride * 2; // bytes of one tile image
 constexpr float kLog2e = 1.4426950408889634f;
 
-template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
-    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma<__half> : MmaType<__half> {
-    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
+template <typename T> using Mma = MmaBuiltin16<T>;
 
 // delta[b, h, i] = sum_d dout[b, i, h, d] out[b, i, h, d]: 8 lanes per row, 16 bytes per lane and tensor
 template <typename T>
@@ -456,10 +448,10 @@ extern "C" int mvi_attention_backward(const void* q, const void* k, const void* 
         return mvi::unet_fail(MVI_EINVAL, "attention backward: workspace too small");
     const bool fold = mvi::attention_folds_scale(mvi_attention_kernel_variant(Sq, Sk, D, dtype), dtype);   // as the forward that wrote lse
     hipStream_t st = (hipStream_t)stream;
-    const int rc = dtype == MVI_DT_BF16
-        ? mvi::bwd::bwd_launch<__hip_bfloat16>(q, k, v, out, dout, (const float*)lse, dq, dk, dv, B, H, Sq, Sk, scale, fold, (float*)workspace, st)
-        : mvi::bwd::bwd_launch<__half>(q, k, v, out, dout, (const float*)lse, dq, dk, dv, B, H, Sq, Sk, scale, fold, (float*)workspace, st);
-    return rc ? mvi::unet_fail(rc, "attention backward: kernel launch failed") : MVI_OK;
+    return mvi::dispatch_dtype16(dtype, "attention backward: unknown dtype", [&](auto t) {
+        const int rc = mvi::bwd::bwd_launch<typename decltype(t)::type>(q, k, v, out, dout, (const float*)lse, dq, dk, dv, B, H, Sq, Sk, scale, fold, (float*)workspace, st);
+        return rc ? mvi::unet_fail(rc, "attention backward: kernel launch failed") : MVI_OK;
+    });
 }
 
 extern "C" int mvi_attention_temporal_backward(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
@@ -471,12 +463,8 @@ extern "C" int mvi_attention_temporal_backward(const void* q, const void* k, con
     if (!q || !k || !v || !dout || !dq || !dk || !dv) return mvi::unet_fail(MVI_EINVAL, "temporal attention backward: NULL pointer");
     if ((int64_t)Bo * S * H > 0x7FFFFFFFll) return mvi::unet_fail(MVI_EINVAL, "temporal attention backward: too many problems");
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = mvi::bwd::temporal_bwd_launch<float>(q, k, v, dout, dq, dk, dv, Bo, T, S, H, D, scale, st); break;
-        case MVI_DT_BF16: rc = mvi::bwd::temporal_bwd_launch<__hip_bfloat16>(q, k, v, dout, dq, dk, dv, Bo, T, S, H, D, scale, st); break;
-        case MVI_DT_F16: rc = mvi::bwd::temporal_bwd_launch<__half>(q, k, v, dout, dq, dk, dv, Bo, T, S, H, D, scale, st); break;
-        default: return mvi::unet_fail(MVI_EINVAL, "temporal attention backward: unknown dtype");
-    }
-    return rc ? mvi::unet_fail(rc, "temporal attention backward: kernel launch failed") : MVI_OK;
+    return mvi::dispatch_dtype(dtype, "temporal attention backward: unknown dtype", [&](auto t) {
+        const int rc = mvi::bwd::temporal_bwd_launch<typename decltype(t)::type>(q, k, v, dout, dq, dk, dv, Bo, T, S, H, D, scale, st);
+        return rc ? mvi::unet_fail(rc, "temporal attention backward: kernel launch failed") : MVI_OK;
+    });
 }

@@ -17,8 +17,6 @@
 // row of 68 elements (b64 reads conflict-free).
 #include <type_traits>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
 #include "attn_launch.h"
 #include "mfma_common.h"
 
@@ -30,13 +28,7 @@ constexpr int kFK = 64;          // keys per tile
 constexpr int kKStride = 72;     // elements per K row in LDS
 constexpr int kVStride = 68;     // elements per V^T row in LDS
 
-template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
-    __device__ static f32x16 mfma(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma<__half> : MmaType<__half> {
-    __device__ static f32x16 mfma(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
+template <typename T> using Mma = MmaBuiltin32<T>;
 
 // Forms measured in round 1 (micro-benchmark B28 H5 S9216 / B28 H10 S2304, bf16, TFLOP/s); only the first is built:
 //   pipelined, 3 waves per SIMD (this file)         781 / 761     QK^T of tile t+1 issued under the softmax of tile t

@@ -48,8 +48,6 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
 #include "attn_launch.h"
 #include "mfma_common.h"
 
@@ -69,13 +67,7 @@ constexpr float kRescaleThreshold = 8.0f;         // log2 units: O, l rescaled o
 constexpr int kWaves = 8;
 constexpr int kLoaders = 4;
 
-template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
-    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma<__half> : MmaType<__half> {
-    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
+template <typename T> using Mma = MmaBuiltin16<T>;
 
 template <int N> __device__ __forceinline__ void wait_vm_then_barrier() {
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");

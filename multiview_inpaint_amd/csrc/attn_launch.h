@@ -4,9 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-namespace mvi {
+#include "unet_host.h"      // unet_fail, dispatch_dtype
 
-int unet_fail(int code, const char* msg);       // records msg for mvi_unet_last_error (groupnorm_silu.hip), returns code
+namespace mvi {
 
 // attn_flash.hip: 4 waves, 128 queries per block. scale_log2e: what a score is multiplied by on its way into exp2
 template <typename T>

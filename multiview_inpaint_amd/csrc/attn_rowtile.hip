@@ -15,8 +15,6 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
 #include "attn_launch.h"
 
 namespace mvi {

@@ -19,8 +19,6 @@
 // problem's fragments before it computes the current one.
 #include <cstdint>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
 #include "attn_launch.h"
 #include "mfma_common.h"
 
@@ -33,13 +31,7 @@ constexpr int kWaves = 4;                            // waves per block, one pro
 constexpr int kVRow = 136;                           // bytes per V row in LDS (128 + 8: lane group g lands 8 banks after g - 1)
 constexpr int kVTile = 16 * kVRow;
 
-template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
-    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma<__half> : MmaType<__half> {
-    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
+template <typename T> using Mma = MmaBuiltin16<T>;
 
 struct Operands {                                    // one problem's global loads, in flight while the previous problem computes
     u32x4 kq[4];                                     // K step 0, 1, Q step 0, 1 (frame T - 1 again for the rows >= T)

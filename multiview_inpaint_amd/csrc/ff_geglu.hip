@@ -17,19 +17,17 @@
 //     tile as the tile's 40 MFMAs occupy the matrix pipe (K = 320 is short), so it must not run in series with them;
 //   * the bias vector (2 inner floats) sits in LDS; one barrier per step; loader waves (4 of 8) issue the tile two steps ahead at the
 //     END of a step, behind that step's stores, and wait with a COUNTED vmcnt for everything older than the pieces just issued.
-// GELU: erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, below half an ulp of the bf16 / f16 output by four orders of magnitude)
-// with v_rcp_f32 / v_exp_f32: 14 instructions per output, branch-free.
+// GELU: geglu1 of geglu_math.h (erf by polynomial, 14 instructions per output, branch-free).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
+#include "geglu_math.h"
 #include "mfma_common.h"
+#include "unet_host.h"
 
 namespace mvi {
-int unet_fail(int code, const char* msg);
 namespace ffg {
 
 
@@ -45,29 +43,7 @@ constexpr int kRing = 3;
 constexpr int kLoaders = 4;
 constexpr int kPiecesPerLoader = kPieces / kLoaders; // 10
 
-template <typename T> struct Mma;
-// c += A B on v_mfma_f32_16x16x32, IN PLACE and in program order (tied inline assembly: csrc/linear_n320.hip, Mma, says why). The compiler
-// does not know these are matrix instructions: the wait states around ordinary reads / writes of an accumulator are written out below.
-template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
-    __device__ static void mfma(f32x4& c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
-};
-template <> struct Mma<__half> : MmaType<__half> {
-    __device__ static void mfma(f32x4& c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
-};
-
-// v * gelu(g), gelu(g) = g/2 (1 + erf(g / sqrt 2)); erf(z) = sign(z) (1 - (a1 t + ... + a5 t^5) e^(-z^2)), t = 1 / (1 + p |z|), z = g / sqrt 2
-__device__ __forceinline__ float geglu1(float v, float g) {
-    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(g), 0.3275911f * 0.70710678118654752f, 1.0f));
-    float p = __builtin_fmaf(1.061405429f, t, -1.453152027f);
-    p = __builtin_fmaf(p, t, 1.421413741f);
-    p = __builtin_fmaf(p, t, -0.284496736f);
-    p = __builtin_fmaf(p, t, 0.254829592f);
-    p *= t;
-    const float e = __builtin_amdgcn_exp2f(g * g * (-0.5f * 1.4426950408889634f));   // e^(-z^2)
-    const float erf_abs = __builtin_fmaf(-p, e, 1.0f);
-    const float hg = 0.5f * g;                                   // g/2 (1 + sign(g) erf|z|) = g/2 + |g|/2 erf|z|
-    return v * __builtin_fmaf(__builtin_fabsf(hg), erf_abs, hg);
-}
+template <typename T> using Mma = MmaTied16<T>;
 
 // kGeglu = true : out[r, j] = (x . W[j] + b[j]) * gelu(x . W[inner + j] + b[inner + j]), j < inner; a step = 32 outputs
 // kGeglu = false: out[r, j] = x . W[j] + b[j], j < inner (= the Linear's out_features); a step = 64 outputs (the same two 32-row
@@ -326,10 +302,10 @@ extern "C" int mvi_ff_geglu(const void* x, const void* weight, const float* bias
         return mvi::unet_fail(MVI_EINVAL, "ff_geglu: rows must be 16-byte aligned (x, weight) / 8-byte aligned (out)");
     if ((int64_t)2 * inner * K * 2 > 0xFFFFFFFFll) return mvi::unet_fail(MVI_EINVAL, "ff_geglu: weight exceeds 32-bit byte offsets");
     hipStream_t st = (hipStream_t)stream;
-    const int rc = dtype == MVI_DT_BF16
-                       ? mvi::ff_k320_launch<__hip_bfloat16, true>(x, weight, bias, out, rows, inner, x_row_stride, out_row_stride, st)
-                       : mvi::ff_k320_launch<__half, true>(x, weight, bias, out, rows, inner, x_row_stride, out_row_stride, st);
-    return rc ? mvi::unet_fail(rc, "ff_geglu: kernel launch failed") : MVI_OK;
+    return mvi::dispatch_dtype16(dtype, "ff_geglu: unknown dtype", [&](auto t) {
+        const int rc = mvi::ff_k320_launch<typename decltype(t)::type, true>(x, weight, bias, out, rows, inner, x_row_stride, out_row_stride, st);
+        return rc ? mvi::unet_fail(rc, "ff_geglu: kernel launch failed") : MVI_OK;
+    });
 }
 
 extern "C" int mvi_linear_k320_supported(int32_t K, int32_t out_features, int32_t dtype) {
@@ -352,8 +328,8 @@ extern "C" int mvi_linear_k320(const void* x, const void* weight, const float* b
         return mvi::unet_fail(MVI_EINVAL, "linear_k320: rows must be 16-byte aligned (x, weight) / 8-byte aligned (out)");
     if ((int64_t)out_features * K * 2 > 0xFFFFFFFFll) return mvi::unet_fail(MVI_EINVAL, "linear_k320: weight exceeds 32-bit byte offsets");
     hipStream_t st = (hipStream_t)stream;
-    const int rc = dtype == MVI_DT_BF16
-                       ? mvi::ff_k320_launch<__hip_bfloat16, false>(x, weight, bias, out, rows, out_features, x_row_stride, out_row_stride, st)
-                       : mvi::ff_k320_launch<__half, false>(x, weight, bias, out, rows, out_features, x_row_stride, out_row_stride, st);
-    return rc ? mvi::unet_fail(rc, "linear_k320: kernel launch failed") : MVI_OK;
+    return mvi::dispatch_dtype16(dtype, "linear_k320: unknown dtype", [&](auto t) {
+        const int rc = mvi::ff_k320_launch<typename decltype(t)::type, false>(x, weight, bias, out, rows, out_features, x_row_stride, out_row_stride, st);
+        return rc ? mvi::unet_fail(rc, "linear_k320: kernel launch failed") : MVI_OK;
+    });
 }

@@ -26,13 +26,11 @@
 #include <cstdint>
 #include <type_traits>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
 #include "geglu_math.h"
 #include "mfma_common.h"
+#include "unet_host.h"
 
 namespace mvi {
-int unet_fail(int code, const char* msg);
 namespace ffb {
 
 constexpr int kK = 320;
@@ -46,13 +44,7 @@ constexpr int kStride = 328;                    // LDS row stride in elements (6
 constexpr int kImg = kTR * kStride * 2;         // 41984 bytes
 constexpr int kPieces = kTR * (kK / 8) / (64 * kWaves);     // 16-byte pieces of a tile per thread: 5
 
-template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
-    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma<__half> : MmaType<__half> {
-    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
+template <typename T> using Mma = MmaBuiltin16<T>;
 
 template <typename T, bool kStoreDh, bool kDx>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))

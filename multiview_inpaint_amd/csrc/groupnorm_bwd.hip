@@ -22,13 +22,10 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
+#include "unet_host.h"
 #include "unet_io.h"
 
 namespace mvi {
-
-int unet_fail(int code, const char* msg);
 
 constexpr int kGbC = 64;                                  // channels per tile
 constexpr int kGbBlock = 256;
@@ -370,11 +367,8 @@ extern "C" int mvi_groupnorm_backward(const void* x, const void* dy, const float
     q.weight = weight; q.bias = bias; q.chan_bias = chan_bias; q.stats = stats;
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = mvi::gb_run<float>(x, dy, q, p, dy_layout, videos, ws, dweight, dbias, dchan_bias, dx, st); break;
-        case MVI_DT_BF16: rc = mvi::gb_run<__hip_bfloat16>(x, dy, q, p, dy_layout, videos, ws, dweight, dbias, dchan_bias, dx, st); break;
-        default: rc = mvi::gb_run<__half>(x, dy, q, p, dy_layout, videos, ws, dweight, dbias, dchan_bias, dx, st); break;
-    }
-    return rc ? mvi::unet_fail(MVI_EHIP, "groupnorm backward: kernel launch failed") : MVI_OK;
+    return mvi::dispatch_dtype(dtype, "groupnorm backward: unknown dtype", [&](auto t) {          // (gb_plan has turned an unknown dtype down)
+        return mvi::gb_run<typename decltype(t)::type>(x, dy, q, p, dy_layout, videos, ws, dweight, dbias, dchan_bias, dx, st)
+                   ? mvi::unet_fail(MVI_EHIP, "groupnorm backward: kernel launch failed") : MVI_OK;
+    });
 }

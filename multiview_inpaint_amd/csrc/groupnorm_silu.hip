@@ -16,8 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
+#include "unet_host.h"
 #include "unet_io.h"
 
 namespace mvi {
@@ -848,16 +847,12 @@ static int gn_dispatch(const void* x, void* y, const float* weight, const float*
         return mvi::unet_fail(MVI_ENOMEM, "groupnorm: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     float* part = (float*)workspace;
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = mvi::gn_launch<float>(x, y, weight, bias, chan_bias, stack3, Nv, T, C, spatial, groups, eps, fuse_silu, part, st, tokens, sync, stats); break;
-        case MVI_DT_BF16: rc = mvi::gn_launch<__hip_bfloat16>(x, y, weight, bias, chan_bias, stack3, Nv, T, C, spatial, groups, eps, fuse_silu, part, st, tokens, sync, stats); break;
-        case MVI_DT_F16: rc = mvi::gn_launch<__half>(x, y, weight, bias, chan_bias, stack3, Nv, T, C, spatial, groups, eps, fuse_silu, part, st, tokens, sync, stats); break;
-        default: return mvi::unet_fail(MVI_EINVAL, "groupnorm: unknown dtype");
-    }
-    if (rc == MVI_EINVAL)
-        return mvi::unet_fail(MVI_EINVAL, "groupnorm (token-major output): C and spatial must be multiples of the 16-byte vector, 16-B aligned");
-    return rc ? mvi::unet_fail(MVI_EHIP, "groupnorm: kernel launch failed") : MVI_OK;
+    return mvi::dispatch_dtype(dtype, "groupnorm: unknown dtype", [&](auto t) {
+        const int rc = mvi::gn_launch<typename decltype(t)::type>(x, y, weight, bias, chan_bias, stack3, Nv, T, C, spatial, groups, eps, fuse_silu, part, st, tokens, sync, stats);
+        if (rc == MVI_EINVAL)
+            return mvi::unet_fail(MVI_EINVAL, "groupnorm (token-major output): C and spatial must be multiples of the 16-byte vector, 16-B aligned");
+        return rc ? mvi::unet_fail(MVI_EHIP, "groupnorm: kernel launch failed") : MVI_OK;
+    });
 }
 
 extern "C" int mvi_groupnorm_silu(const void* x, void* y, const float* weight, const float* bias, int64_t N,

@@ -16,12 +16,10 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
+#include "unet_host.h"
 #include "unet_io.h"
 
 namespace mvi {
-int unet_fail(int code, const char* msg);
 
 constexpr int kGtPasses = 8;          // token rows per thread and chunk
 constexpr int kGtMaxGroups = 64;
@@ -476,14 +474,10 @@ static int tok2tok_impl(const void* x, void* y, const float* weight, const float
     if (workspace_bytes < mvi_groupnorm_tok2tok_workspace_bytes(N, C, spatial, groups, dtype))
         return mvi::unet_fail(MVI_ENOMEM, "groupnorm_tok2tok: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = mvi::gt_launch<float>(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, (float*)workspace, st, frames); break;
-        case MVI_DT_BF16: rc = mvi::gt_launch<__hip_bfloat16>(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, (float*)workspace, st, frames); break;
-        case MVI_DT_F16: rc = mvi::gt_launch<__half>(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, (float*)workspace, st, frames); break;
-        default: return mvi::unet_fail(MVI_EINVAL, "groupnorm_tok2tok: unknown dtype");
-    }
-    return rc ? mvi::unet_fail(MVI_EHIP, "groupnorm_tok2tok: kernel launch failed") : MVI_OK;
+    return mvi::dispatch_dtype(dtype, "groupnorm_tok2tok: unknown dtype", [&](auto t) {
+        return mvi::gt_launch<typename decltype(t)::type>(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, (float*)workspace, st, frames)
+                   ? mvi::unet_fail(MVI_EHIP, "groupnorm_tok2tok: kernel launch failed") : MVI_OK;
+    });
 }
 
 extern "C" int mvi_groupnorm_silu_tok2tok_pre(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
@@ -498,10 +492,10 @@ extern "C" int mvi_groupnorm_silu_tok2tok_pre(const void* x, void* y, const floa
     if (((uintptr_t)x | (uintptr_t)y) % 16) return mvi::unet_fail(MVI_EINVAL, "groupnorm_tok2tok_pre: x / y must be 16-byte aligned");
     if (workspace_bytes < (size_t)N * C * 2 * sizeof(float)) return mvi::unet_fail(MVI_ENOMEM, "groupnorm_tok2tok_pre: workspace too small (N C 2 floats)");
     hipStream_t st = (hipStream_t)stream;
-    const int rc = dtype == MVI_DT_BF16
-                       ? mvi::gt_launch_pre<__hip_bfloat16>(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, part, chunks_per_sample, (float*)workspace, st, frames)
-                       : mvi::gt_launch_pre<__half>(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, part, chunks_per_sample, (float*)workspace, st, frames);
-    return rc ? mvi::unet_fail(MVI_EHIP, "groupnorm_tok2tok_pre: kernel launch failed") : MVI_OK;
+    return mvi::dispatch_dtype16(dtype, "groupnorm_tok2tok_pre: unknown dtype", [&](auto t) {
+        return mvi::gt_launch_pre<typename decltype(t)::type>(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, part, chunks_per_sample, (float*)workspace, st, frames)
+                   ? mvi::unet_fail(MVI_EHIP, "groupnorm_tok2tok_pre: kernel launch failed") : MVI_OK;
+    });
 }
 
 extern "C" int mvi_groupnorm_silu_tok2tok(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
@@ -595,13 +589,10 @@ extern "C" int mvi_rows_fused_gnstats(int32_t mode, const void* a, const void* b
     if (groups > 0 && (!part || part_bytes < mvi_rows_gnstats_bytes(N, C, spatial, groups, dtype)))
         return mvi::unet_fail(MVI_EINVAL, "rows_fused_gnstats: statistics buffer missing or too small (mvi_rows_gnstats_bytes)");
     hipStream_t st = (hipStream_t)stream;
-    int rc, ch = 0;
-    switch (dtype) {
-        case MVI_DT_F32: rc = mvi::gt_fused_launch<float>(mode, a, b, base, bias, alpha, out, part, N, C, spatial, groups, &ch, st, C_first); break;
-        case MVI_DT_BF16: rc = mvi::gt_fused_launch<__hip_bfloat16>(mode, a, b, base, bias, alpha, out, part, N, C, spatial, groups, &ch, st, C_first); break;
-        case MVI_DT_F16: rc = mvi::gt_fused_launch<__half>(mode, a, b, base, bias, alpha, out, part, N, C, spatial, groups, &ch, st, C_first); break;
-        default: return mvi::unet_fail(MVI_EINVAL, "rows_fused_gnstats: unknown dtype");
-    }
-    if (chunks_per_sample) *chunks_per_sample = ch;
-    return rc ? mvi::unet_fail(MVI_EHIP, "rows_fused_gnstats: kernel launch failed") : MVI_OK;
+    return mvi::dispatch_dtype(dtype, "rows_fused_gnstats: unknown dtype", [&](auto t) {
+        int ch = 0;
+        const int rc = mvi::gt_fused_launch<typename decltype(t)::type>(mode, a, b, base, bias, alpha, out, part, N, C, spatial, groups, &ch, st, C_first);
+        if (chunks_per_sample) *chunks_per_sample = ch;
+        return rc ? mvi::unet_fail(MVI_EHIP, "rows_fused_gnstats: kernel launch failed") : MVI_OK;
+    });
 }

@@ -23,13 +23,10 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
+#include "unet_host.h"
 #include "unet_io.h"
 
 namespace mvi {
-
-int unet_fail(int code, const char* msg);
 
 constexpr int kLnbTargetBlocks = 512;       // two 256-thread blocks per CU: what the register budget of the K = 5 kernels allows
 constexpr int kLnbFinCols = 32;             // finalize: 32 columns x 8 segments of the partial rows per block
@@ -355,11 +352,8 @@ extern "C" int mvi_add_layernorm_backward(const void* gy, const void* s, const v
         return unet_fail(MVI_EINVAL, "add_layernorm backward: tensors must be 16-byte aligned");
     LnbArgs a{gy, s, gs, gs_pre, weight, g_out, p.direct ? drow : nullptr, (float*)workspace, R, p.run_len, p.slab_rows, p.blocks,
               (int)p.nb, C, p.L, p.log2L, eps};
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = lnb_run<float>(a, p, gp, par, dr, dweight, dbias, drow, (hipStream_t)stream); break;
-        case MVI_DT_BF16: rc = lnb_run<__hip_bfloat16>(a, p, gp, par, dr, dweight, dbias, drow, (hipStream_t)stream); break;
-        default: rc = lnb_run<__half>(a, p, gp, par, dr, dweight, dbias, drow, (hipStream_t)stream); break;
-    }
-    return rc ? unet_fail(MVI_EHIP, "add_layernorm backward: kernel launch failed") : MVI_OK;
+    return dispatch_dtype(dtype, "add_layernorm backward: unknown dtype", [&](auto t) {     // (turned down above already)
+        return lnb_run<typename decltype(t)::type>(a, p, gp, par, dr, dweight, dbias, drow, (hipStream_t)stream)
+                   ? unet_fail(MVI_EHIP, "add_layernorm backward: kernel launch failed") : MVI_OK;
+    });
 }

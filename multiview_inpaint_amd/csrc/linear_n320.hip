@@ -26,12 +26,11 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
+#include "geglu_math.h"
 #include "mfma_common.h"
+#include "unet_host.h"
 
 namespace mvi {
-int unet_fail(int code, const char* msg);
 namespace ln3 {
 
 
@@ -47,17 +46,7 @@ constexpr int kLoaders = 4;
 constexpr int kPiecesPerLoader = kPieces / kLoaders; // 10
 constexpr int kLdsBytes = kRing * kChunkBytes + kWaves * 4096;
 
-template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
-    // c += A B, IN PLACE and in program order: through the builtin the register allocator took the untied form for two MFMAs in three,
-    // rotated the forty 4-register accumulators through the W fragments' registers (write-after-read stalls on the next ds_read) and
-    // spilled; as volatile assembly the loop below is issued as written. The compiler does not know these are matrix instructions:
-    // the wait states between the last of them and the first ordinary read of an accumulator are in the kernel (mfma_settle).
-    __device__ static void mfma(f32x4& c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
-};
-template <> struct Mma<__half> : MmaType<__half> {
-    __device__ static void mfma(f32x4& c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
-};
+template <typename T> using Mma = MmaTied16<T>;
 
 // a pointer every lane of the wave holds the same value of, said to the compiler (the asynchronous loads take their base in scalar registers)
 __device__ __forceinline__ const char* wave_uniform(const char* p) {
@@ -118,19 +107,9 @@ struct GnStats {
 // tile t and gate tile t + 5 meet in the same lane and register), the epilogue gates in registers and stores 160 outputs per row.
 // The [rows, 2 inner] intermediate the library GEMM writes and geglu_kernel reads back (1 GB per call at level 1) never exists.
 // cg.groups = inner / 160 column groups; W is [2 inner][K], bias [2 inner] or NULL.
-// v * gelu(g), exact-erf GELU by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7): the arithmetic of csrc/ff_geglu.hip's geglu1
-__device__ __forceinline__ float geglu1(float v, float g) {
-    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(g), 0.3275911f * 0.70710678118654752f, 1.0f));
-    float p = __builtin_fmaf(1.061405429f, t, -1.453152027f);
-    p = __builtin_fmaf(p, t, 1.421413741f);
-    p = __builtin_fmaf(p, t, -0.284496736f);
-    p = __builtin_fmaf(p, t, 0.254829592f);
-    p *= t;
-    const float e = __builtin_amdgcn_exp2f(g * g * (-0.5f * 1.4426950408889634f));
-    const float erf_abs = __builtin_fmaf(-p, e, 1.0f);
-    const float hg = 0.5f * g;
-    return v * __builtin_fmaf(__builtin_fabsf(hg), erf_abs, hg);
-}
+// The gate is geglu_math.h's: geglu2, the packed pair form (the two values of a pair are adjacent accumulator registers, rows r, r + 1
+// of one tile: no register moves), or with MVI_GEGLU_PACKED=0 the scalar geglu1.
+static const int g_geglu_packed = [] { const char* e = getenv("MVI_GEGLU_PACKED"); return (e && e[0] == '0') ? 0 : 1; }();
 
 // kLn (round 5): the projection's output never reaches memory — the residual add(s) and the LayerNorm that FOLLOW it in the transformer
 // blocks (attention.py:544-572 `x = attn1(norm1(x)) + x; ... norm3(x)`, video_attention.py:110-141) run in the epilogue, on the
@@ -149,29 +128,6 @@ struct LnEpi {
 // NOUT (round 6): the block's column count — 320 everywhere in the UNet; 256 for the first-stage decoder's 128 / 256 / 512-channel
 // convolutions (split operands, fp32 out). Everything below is written in terms of kN / kNT / kChunkBytes / kPieces..., re-derived here
 // from NOUT (the epilogues that know about 320 — kStats, kGeglu, kLn — are only instantiated with it).
-// The same arithmetic on a PAIR of outputs with the packed fp32 instructions (v_pk_fma_f32 / v_pk_mul_f32: two lanes' worth per issue
-// slot). Round 5 found them an anti-lever BESIDE MFMAs (csrc/ff_geglu.hip's interleaved epilogue); this kernel's GEGLU epilogue runs after
-// the last MFMA of the block, with nothing on the matrix pipe. The two values of a pair are adjacent accumulator registers (rows r, r + 1
-// of one tile), so no register moves are needed. |v| enters through the scalar fma's abs modifier (the packed forms have none).
-typedef float f32p __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32p geglu2(f32p v, f32p g) {
-    const f32p d = {__builtin_fmaf(__builtin_fabsf(g.x), 0.3275911f * 0.70710678118654752f, 1.0f),
-                    __builtin_fmaf(__builtin_fabsf(g.y), 0.3275911f * 0.70710678118654752f, 1.0f)};
-    const f32p t = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-    f32p p = t * 1.061405429f + (-1.453152027f);
-    p = p * t + 1.421413741f;
-    p = p * t + (-0.284496736f);
-    p = p * t + 0.254829592f;
-    p = p * t;
-    const f32p gg = g * g * (-0.5f * 1.4426950408889634f);
-    const f32p e = {__builtin_amdgcn_exp2f(gg.x), __builtin_amdgcn_exp2f(gg.y)};
-    const f32p erf_abs = 1.0f - p * e;
-    const f32p hg = 0.5f * g;
-    const f32p s = {__builtin_fmaf(__builtin_fabsf(hg.x), erf_abs.x, hg.x), __builtin_fmaf(__builtin_fabsf(hg.y), erf_abs.y, hg.y)};
-    return v * s;
-}
-static const int g_geglu_packed = [] { const char* e = getenv("MVI_GEGLU_PACKED"); return (e && e[0] == '0') ? 0 : 1; }();
-
 template <typename T, bool kConv, bool kSplit = false, bool kStats = false, bool kGeglu = false, bool kLn = false, int NOUT = 320,
           bool kUps = false, bool kPersist = false>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -603,8 +559,8 @@ void linear_n320_kernel(const T* __restrict__ x, const T* __restrict__ w, const 
 #pragma unroll
                         for (int r = 0; r < 4; r += 2)
                             if (cg.dup3) {           // (kGeglu launches carry the packed-erf switch in this otherwise unused field)
-                                const f32p o2 = geglu2(f32p{acc[t][j0 + jj][r], acc[t][j0 + jj][r + 1]},
-                                                       f32p{acc[t][j0 + jj + kNT / 2][r], acc[t][j0 + jj + kNT / 2][r + 1]});
+                                const f32x2 o2 = geglu2(f32x2{acc[t][j0 + jj][r], acc[t][j0 + jj][r + 1]},
+                                                       f32x2{acc[t][j0 + jj + kNT / 2][r], acc[t][j0 + jj + kNT / 2][r + 1]});
                                 tile_put(t, jj, r, M::pack2(o2.x, o2.y));
                             } else
                             tile_put(t, jj, r, M::pack2(geglu1(acc[t][j0 + jj][r], acc[t][j0 + jj + kNT / 2][r]),
@@ -899,9 +855,10 @@ extern "C" int mvi_linear_n320(const void* x, const void* weight, const float* b
     // (the persistent form — kPersist, taken by the GEGLU projection below — is 0 ... +5 % SLOWER here: this epilogue is 20 stores, nothing
     // for the next tile's first loads to hide under, and the plain grid's dispatch already overlaps a block's drain with the next one's start:
     // profiles/round6_n320_persistent.txt)
-    const int rc = dtype == MVI_DT_BF16 ? mvi::linear_n320_launch<__hip_bfloat16>(x, weight, bias, out, rows, K, x_row_stride, out_row_stride, st, cg)
-                                        : mvi::linear_n320_launch<__half>(x, weight, bias, out, rows, K, x_row_stride, out_row_stride, st, cg);
-    return rc ? mvi::unet_fail(rc, "linear_n320: kernel launch failed") : MVI_OK;
+    return mvi::dispatch_dtype16(dtype, "linear_n320: unknown dtype", [&](auto t) {
+        const int rc = mvi::linear_n320_launch<typename decltype(t)::type>(x, weight, bias, out, rows, K, x_row_stride, out_row_stride, st, cg);
+        return rc ? mvi::unet_fail(rc, "linear_n320: kernel launch failed") : MVI_OK;
+    });
 }
 
 // Projection into 320 channels + residual add(s) + LayerNorm in one kernel: see kLn at the kernel
@@ -925,12 +882,11 @@ extern "C" int mvi_linear_n320_add_layernorm(const void* x, const void* weight, 
     const mvi::ln3::LnEpi ln = {resid, row, row ? row_div : 1, ln_weight, ln_bias, s_pre, s, eps};
     const mvi::ln3::ConvGeom cg = {0, 0, 0, 0, 1, 1, 1, 0, 0, 0, 0};
     hipStream_t st = (hipStream_t)stream;
-    const int rc = dtype == MVI_DT_BF16
-                       ? mvi::linear_n320_launch<__hip_bfloat16, false, false, false, false, true>(x, weight, bias, y, rows, K, x_row_stride,
-                                                                                                   out_row_stride, st, cg, nullptr, {nullptr, nullptr, 0, 0}, ln)
-                       : mvi::linear_n320_launch<__half, false, false, false, false, true>(x, weight, bias, y, rows, K, x_row_stride, out_row_stride, st,
-                                                                                           cg, nullptr, {nullptr, nullptr, 0, 0}, ln);
-    return rc ? mvi::unet_fail(rc, "linear_n320_add_layernorm: kernel launch failed") : MVI_OK;
+    return mvi::dispatch_dtype16(dtype, "linear_n320_add_layernorm: unknown dtype", [&](auto t) {
+        const int rc = mvi::linear_n320_launch<typename decltype(t)::type, false, false, false, false, true>(x, weight, bias, y, rows, K, x_row_stride, out_row_stride,
+                                                                                                         st, cg, nullptr, {nullptr, nullptr, 0, 0}, ln);
+        return rc ? mvi::unet_fail(rc, "linear_n320_add_layernorm: kernel launch failed") : MVI_OK;
+    });
 }
 
 // GEGLU projection with a long contraction (the level-1 / level-2 FeedForward layers): see kGeglu at the kernel

@@ -1,6 +1,6 @@
-// What the MFMA kernels of this directory share: register vector types, the I/O-type conversions and the LDS-DMA piece. What differs
-// from kernel to kernel stays in its file: the matrix instruction itself (`Mma<T>::mfma`: builtin 32x32x16, builtin 16x16x32, or
-// tied inline assembly) and the tile constants.
+// What the MFMA kernels of this directory share: register vector types, the I/O-type conversions, the three forms of the matrix
+// instruction (builtin 16x16x32, builtin 32x32x16, tied inline assembly 16x16x32) and the LDS-DMA piece. A kernel file names the
+// form it runs on (`template <typename T> using Mma = MmaBuiltin16<T>;`) and keeps its tile constants.
 #pragma once
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
@@ -22,7 +22,7 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 #define MVI_AS3 __attribute__((address_space(3)))
 
 // Per I/O type: the MFMA operand fragment of 8 elements, two floats -> one packed dword (round to nearest even) and back.
-// A kernel's Mma<T> derives from this and adds its mfma().
+// The Mma forms below derive from this and add mfma().
 template <typename T> struct MmaType;
 template <> struct MmaType<__hip_bfloat16> {
     using frag = bf16x8;
@@ -43,6 +43,34 @@ template <> struct MmaType<__half> {
     }
     __device__ static float lo(uint32_t w) { f16x2 h = *reinterpret_cast<f16x2*>(&w); return (float)h[0]; }
     __device__ static float hi(uint32_t w) { f16x2 h = *reinterpret_cast<f16x2*>(&w); return (float)h[1]; }
+};
+
+// c + A B through the builtin: the compiler schedules it and keeps the wait states
+template <typename T> struct MmaBuiltin16;               // v_mfma_f32_16x16x32
+template <> struct MmaBuiltin16<__hip_bfloat16> : MmaType<__hip_bfloat16> {
+    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+};
+template <> struct MmaBuiltin16<__half> : MmaType<__half> {
+    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+};
+template <typename T> struct MmaBuiltin32;               // v_mfma_f32_32x32x16
+template <> struct MmaBuiltin32<__hip_bfloat16> : MmaType<__hip_bfloat16> {
+    __device__ static f32x16 mfma(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <> struct MmaBuiltin32<__half> : MmaType<__half> {
+    __device__ static f32x16 mfma(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+// c += A B on v_mfma_f32_16x16x32, IN PLACE and in program order. Through the builtin the register allocator took the untied form
+// for two MFMAs in three of linear_n320's loop, rotated the forty 4-register accumulators through the W fragments' registers
+// (write-after-read stalls on the next ds_read) and spilled; as volatile assembly the loop is issued as written. The compiler does
+// not know these are matrix instructions: the KERNEL owns the wait states between the last of them and the first ordinary read or
+// write of an accumulator (linear_n320.hip: mfma_settle; ff_geglu.hip writes them out).
+template <typename T> struct MmaTied16;
+template <> struct MmaTied16<__hip_bfloat16> : MmaType<__hip_bfloat16> {
+    __device__ static void mfma(f32x4& c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
+};
+template <> struct MmaTied16<__half> : MmaType<__half> {
+    __device__ static void mfma(f32x4& c, u32x4 a, u32x4 b) { asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
 };
 
 template <typename F> __device__ __forceinline__ F as_frag(u32x4 v) { return *reinterpret_cast<F*>(&v); }

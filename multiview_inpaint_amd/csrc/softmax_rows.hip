@@ -9,13 +9,10 @@
 // normalise) straight from global memory. fp32 statistics; exp2 with the scale folded into one fma.
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
+#include "unet_host.h"
 #include "unet_io.h"
 
 namespace mvi {
-
-int unet_fail(int code, const char* msg);
 
 constexpr int kSmThreads = 256;
 constexpr int kSmMaxLds = 12288;        // 48 KB of fp32 per block: 3 blocks per CU
@@ -109,13 +106,9 @@ extern "C" int mvi_softmax_rows(void* x, int64_t rows, int32_t cols, float scale
     if (!(scale > 0.f)) return unet_fail(MVI_EINVAL, "softmax_rows: scale must be positive");
     if (rows == 0) return MVI_OK;
     if (!x) return unet_fail(MVI_EINVAL, "softmax_rows: NULL pointer");
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = softmax_rows_launch<float>(x, rows, cols, scale, (hipStream_t)stream); break;
-        case MVI_DT_BF16: rc = softmax_rows_launch<__hip_bfloat16>(x, rows, cols, scale, (hipStream_t)stream); break;
-        case MVI_DT_F16: rc = softmax_rows_launch<__half>(x, rows, cols, scale, (hipStream_t)stream); break;
-        default: return unet_fail(MVI_EINVAL, "softmax_rows: unknown dtype");
-    }
-    if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "softmax_rows: too many rows");
-    return rc ? unet_fail(MVI_EHIP, "softmax_rows: kernel launch failed") : MVI_OK;
+    return dispatch_dtype(dtype, "softmax_rows: unknown dtype", [&](auto t) {
+        const int rc = softmax_rows_launch<typename decltype(t)::type>(x, rows, cols, scale, (hipStream_t)stream);
+        if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "softmax_rows: too many rows");
+        return rc ? unet_fail(MVI_EHIP, "softmax_rows: kernel launch failed") : MVI_OK;
+    });
 }

@@ -13,25 +13,17 @@
 //   * the accumulator starts from the bias; a lane ends with 4 consecutive pixels of one output channel: SiLU, pack, one 8-byte store.
 #include <cstdint>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
 #include "mfma_common.h"
+#include "unet_host.h"
 
 namespace mvi {
-int unet_fail(int code, const char* msg);
 namespace sc {
 
 
 constexpr int kTW = 64;                // tile width in pixels
 constexpr int kTHMax = 8;              // tile rows = waves: 8 for the 16-output forms, 4 for the 32-output form (registers, LDS)
 
-template <typename T> struct Mma;
-template <> struct Mma<__hip_bfloat16> : MmaType<__hip_bfloat16> {
-    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma<__half> : MmaType<__half> {
-    __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
+template <typename T> using Mma = MmaBuiltin16<T>;
 
 template <typename T, int CINP, int COUT, int kTH, int STRIDE>
 __global__ __launch_bounds__(64 * kTH) void stem_conv3x3_kernel(const T* __restrict__ x, const T* __restrict__ wp, const float* __restrict__ bias,

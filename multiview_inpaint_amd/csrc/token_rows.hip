@@ -18,13 +18,10 @@
 // storage type exactly there, so the fused result equals the op-by-op result bit for bit.
 #include <hip/hip_runtime.h>
 
-#include "../../include/mvi_raster.h"
-#include "../../include/mvi_unet_ops.h"
+#include "unet_host.h"
 #include "unet_io.h"
 
 namespace mvi {
-
-int unet_fail(int code, const char* msg);
 
 struct AddLnArgs {
     const void *x, *h, *row;
@@ -322,15 +319,11 @@ extern "C" int mvi_add_layernorm(const void* x, const void* h, const void* row, 
     if (s_pre && !h) return unet_fail(MVI_EINVAL, "add_layernorm: s_pre requested without h");
     if (s && !h && !row) return unet_fail(MVI_EINVAL, "add_layernorm: s requested without h or row");
     AddLnArgs a{x, h, row, weight, bias, s_pre, s, y, R, row ? row_div : 1, C, 0, 0, eps};
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = add_layernorm_launch<float>(a, (hipStream_t)stream); break;
-        case MVI_DT_BF16: rc = add_layernorm_launch<__hip_bfloat16>(a, (hipStream_t)stream); break;
-        case MVI_DT_F16: rc = add_layernorm_launch<__half>(a, (hipStream_t)stream); break;
-        default: return unet_fail(MVI_EINVAL, "add_layernorm: unknown dtype");
-    }
-    if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "add_layernorm: C must split into 2^k lanes x <= 8 16-byte vectors");
-    return rc ? unet_fail(MVI_EHIP, "add_layernorm: kernel launch failed") : MVI_OK;
+    return dispatch_dtype(dtype, "add_layernorm: unknown dtype", [&](auto t) {
+        const int rc = add_layernorm_launch<typename decltype(t)::type>(a, (hipStream_t)stream);
+        if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "add_layernorm: C must split into 2^k lanes x <= 8 16-byte vectors");
+        return rc ? unet_fail(MVI_EHIP, "add_layernorm: kernel launch failed") : MVI_OK;
+    });
 }
 
 extern "C" int mvi_layernorm_supported(int32_t C, int32_t dtype) {
@@ -360,15 +353,11 @@ extern "C" int mvi_add_lerp(const void* x, const void* h, const void* base, cons
     if (R < 0 || C <= 0 || row_div <= 0) return unet_fail(MVI_EINVAL, "add_lerp: bad shape");
     if (R == 0) return MVI_OK;
     if (!x || !base || !alpha || !out) return unet_fail(MVI_EINVAL, "add_lerp: NULL pointer");
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = add_lerp_launch<float>(x, h, base, alpha, row_div, out, R, C, (hipStream_t)stream); break;
-        case MVI_DT_BF16: rc = add_lerp_launch<__hip_bfloat16>(x, h, base, alpha, row_div, out, R, C, (hipStream_t)stream); break;
-        case MVI_DT_F16: rc = add_lerp_launch<__half>(x, h, base, alpha, row_div, out, R, C, (hipStream_t)stream); break;
-        default: return unet_fail(MVI_EINVAL, "add_lerp: unknown dtype");
-    }
-    if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "add_lerp: C must be a multiple of the 16-byte vector width");
-    return rc ? unet_fail(MVI_EHIP, "add_lerp: kernel launch failed") : MVI_OK;
+    return dispatch_dtype(dtype, "add_lerp: unknown dtype", [&](auto t) {
+        const int rc = add_lerp_launch<typename decltype(t)::type>(x, h, base, alpha, row_div, out, R, C, (hipStream_t)stream);
+        if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "add_lerp: C must be a multiple of the 16-byte vector width");
+        return rc ? unet_fail(MVI_EHIP, "add_lerp: kernel launch failed") : MVI_OK;
+    });
 }
 
 // out[r][c] = a[r][c] + alpha * (b[r][c] + bias[c]) on fp32 rows [R, C] (round 6): the two adds that end a ResBlock of the first-stage
@@ -420,15 +409,11 @@ extern "C" int mvi_tokens_to_planes_add(const void* tok, const void* x_in, void*
     if (N < 0 || C <= 0 || spatial < 0) return unet_fail(MVI_EINVAL, "tokens_to_planes_add: bad shape");
     if (N == 0 || spatial == 0) return MVI_OK;
     if (!tok || !out) return unet_fail(MVI_EINVAL, "tokens_to_planes_add: NULL pointer");
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = tokens_to_planes_launch<float>(tok, x_in, out, N, C, spatial, (hipStream_t)stream); break;
-        case MVI_DT_BF16: rc = tokens_to_planes_launch<__hip_bfloat16>(tok, x_in, out, N, C, spatial, (hipStream_t)stream); break;
-        case MVI_DT_F16: rc = tokens_to_planes_launch<__half>(tok, x_in, out, N, C, spatial, (hipStream_t)stream); break;
-        default: return unet_fail(MVI_EINVAL, "tokens_to_planes_add: unknown dtype");
-    }
-    if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "tokens_to_planes_add: C and spatial must be multiples of the 16-byte vector width");
-    return rc ? unet_fail(MVI_EHIP, "tokens_to_planes_add: kernel launch failed") : MVI_OK;
+    return dispatch_dtype(dtype, "tokens_to_planes_add: unknown dtype", [&](auto t) {
+        const int rc = tokens_to_planes_launch<typename decltype(t)::type>(tok, x_in, out, N, C, spatial, (hipStream_t)stream);
+        if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "tokens_to_planes_add: C and spatial must be multiples of the 16-byte vector width");
+        return rc ? unet_fail(MVI_EHIP, "tokens_to_planes_add: kernel launch failed") : MVI_OK;
+    });
 }
 
 extern "C" int mvi_tokens_to_planes_add_bias(const void* tok, const void* x_in, const float* bias, void* out, int64_t N, int32_t C, int64_t spatial,
@@ -436,15 +421,11 @@ extern "C" int mvi_tokens_to_planes_add_bias(const void* tok, const void* x_in, 
     if (N < 0 || C <= 0 || spatial < 0) return unet_fail(MVI_EINVAL, "tokens_to_planes_add_bias: bad shape");
     if (N == 0 || spatial == 0) return MVI_OK;
     if (!tok || !out) return unet_fail(MVI_EINVAL, "tokens_to_planes_add_bias: NULL pointer");
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = tokens_to_planes_launch<float>(tok, x_in, out, N, C, spatial, (hipStream_t)stream, bias); break;
-        case MVI_DT_BF16: rc = tokens_to_planes_launch<__hip_bfloat16>(tok, x_in, out, N, C, spatial, (hipStream_t)stream, bias); break;
-        case MVI_DT_F16: rc = tokens_to_planes_launch<__half>(tok, x_in, out, N, C, spatial, (hipStream_t)stream, bias); break;
-        default: return unet_fail(MVI_EINVAL, "tokens_to_planes_add_bias: unknown dtype");
-    }
-    if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "tokens_to_planes_add_bias: C and spatial must be multiples of the 16-byte vector width");
-    return rc ? unet_fail(MVI_EHIP, "tokens_to_planes_add_bias: kernel launch failed") : MVI_OK;
+    return dispatch_dtype(dtype, "tokens_to_planes_add_bias: unknown dtype", [&](auto t) {
+        const int rc = tokens_to_planes_launch<typename decltype(t)::type>(tok, x_in, out, N, C, spatial, (hipStream_t)stream, bias);
+        if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "tokens_to_planes_add_bias: C and spatial must be multiples of the 16-byte vector width");
+        return rc ? unet_fail(MVI_EHIP, "tokens_to_planes_add_bias: kernel launch failed") : MVI_OK;
+    });
 }
 
 template <typename T>
@@ -466,15 +447,11 @@ extern "C" int mvi_planes_to_tokens(const void* x, void* out, int64_t N, int32_t
     const int64_t S = (int64_t)H * W;
     if (N == 0 || S == 0) return MVI_OK;
     if (!x || !out) return unet_fail(MVI_EINVAL, "planes_to_tokens: NULL pointer");
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = planes_to_tokens_launch<float>(x, out, N, C, S, W, upsample, (hipStream_t)stream); break;
-        case MVI_DT_BF16: rc = planes_to_tokens_launch<__hip_bfloat16>(x, out, N, C, S, W, upsample, (hipStream_t)stream); break;
-        case MVI_DT_F16: rc = planes_to_tokens_launch<__half>(x, out, N, C, S, W, upsample, (hipStream_t)stream); break;
-        default: return unet_fail(MVI_EINVAL, "planes_to_tokens: unknown dtype");
-    }
-    if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "planes_to_tokens: C and H W must be multiples of the 16-byte vector width");
-    return rc ? unet_fail(MVI_EHIP, "planes_to_tokens: kernel launch failed") : MVI_OK;
+    return dispatch_dtype(dtype, "planes_to_tokens: unknown dtype", [&](auto t) {
+        const int rc = planes_to_tokens_launch<typename decltype(t)::type>(x, out, N, C, S, W, upsample, (hipStream_t)stream);
+        if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "planes_to_tokens: C and H W must be multiples of the 16-byte vector width");
+        return rc ? unet_fail(MVI_EHIP, "planes_to_tokens: kernel launch failed") : MVI_OK;
+    });
 }
 
 /* out[n, p, c] = x[n, c, p] + tok[n, p, c] + bias[c] (bias optional): a ResBlock's last add with tokens in and tokens out. */
@@ -483,15 +460,11 @@ extern "C" int mvi_planes_add_to_tokens(const void* x, const void* tok, const fl
     if (N < 0 || C <= 0 || spatial < 0) return unet_fail(MVI_EINVAL, "planes_add_to_tokens: bad shape");
     if (N == 0 || spatial == 0) return MVI_OK;
     if (!x || !tok || !out) return unet_fail(MVI_EINVAL, "planes_add_to_tokens: NULL pointer");
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = planes_to_tokens_launch<float>(x, out, N, C, spatial, 1, 1, (hipStream_t)stream, tok, bias); break;
-        case MVI_DT_BF16: rc = planes_to_tokens_launch<__hip_bfloat16>(x, out, N, C, spatial, 1, 1, (hipStream_t)stream, tok, bias); break;
-        case MVI_DT_F16: rc = planes_to_tokens_launch<__half>(x, out, N, C, spatial, 1, 1, (hipStream_t)stream, tok, bias); break;
-        default: return unet_fail(MVI_EINVAL, "planes_add_to_tokens: unknown dtype");
-    }
-    if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "planes_add_to_tokens: C and spatial must be multiples of the 16-byte vector width");
-    return rc ? unet_fail(MVI_EHIP, "planes_add_to_tokens: kernel launch failed") : MVI_OK;
+    return dispatch_dtype(dtype, "planes_add_to_tokens: unknown dtype", [&](auto t) {
+        const int rc = planes_to_tokens_launch<typename decltype(t)::type>(x, out, N, C, spatial, 1, 1, (hipStream_t)stream, tok, bias);
+        if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "planes_add_to_tokens: C and spatial must be multiples of the 16-byte vector width");
+        return rc ? unet_fail(MVI_EHIP, "planes_add_to_tokens: kernel launch failed") : MVI_OK;
+    });
 }
 
 /* out[n, c, p] = base[n, p, c] + (1 - alpha[n]) * (tok[n, p, c] + bias[c]): the tail of a VideoResBlock evaluated on tokens. */
@@ -500,13 +473,9 @@ extern "C" int mvi_tokens_blend_to_planes(const void* tok, const void* base, con
     if (N < 0 || C <= 0 || spatial < 0) return unet_fail(MVI_EINVAL, "tokens_blend_to_planes: bad shape");
     if (N == 0 || spatial == 0) return MVI_OK;
     if (!tok || !base || !alpha || !out) return unet_fail(MVI_EINVAL, "tokens_blend_to_planes: NULL pointer");
-    int rc;
-    switch (dtype) {
-        case MVI_DT_F32: rc = tokens_to_planes_launch<float>(tok, nullptr, out, N, C, spatial, (hipStream_t)stream, bias, base, alpha); break;
-        case MVI_DT_BF16: rc = tokens_to_planes_launch<__hip_bfloat16>(tok, nullptr, out, N, C, spatial, (hipStream_t)stream, bias, base, alpha); break;
-        case MVI_DT_F16: rc = tokens_to_planes_launch<__half>(tok, nullptr, out, N, C, spatial, (hipStream_t)stream, bias, base, alpha); break;
-        default: return unet_fail(MVI_EINVAL, "tokens_blend_to_planes: unknown dtype");
-    }
-    if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "tokens_blend_to_planes: C and spatial must be multiples of the 16-byte vector width");
-    return rc ? unet_fail(MVI_EHIP, "tokens_blend_to_planes: kernel launch failed") : MVI_OK;
+    return dispatch_dtype(dtype, "tokens_blend_to_planes: unknown dtype", [&](auto t) {
+        const int rc = tokens_to_planes_launch<typename decltype(t)::type>(tok, nullptr, out, N, C, spatial, (hipStream_t)stream, bias, base, alpha);
+        if (rc == MVI_EINVAL) return unet_fail(MVI_EINVAL, "tokens_blend_to_planes: C and spatial must be multiples of the 16-byte vector width");
+        return rc ? unet_fail(MVI_EHIP, "tokens_blend_to_planes: kernel launch failed") : MVI_OK;
+    });
 }
