@@ -19,6 +19,7 @@ import torch.nn.functional as F
 from torch.utils.checkpoint import checkpoint as _torch_checkpoint
 
 from . import ops
+from .derived import Signature, derived, derived1
 
 
 def zero_module(m: nn.Module) -> nn.Module:
@@ -434,6 +435,10 @@ class ResBlock(TimestepBlock):
         return self.skip_connection(x) + h
 
 
+def _stacked_taps(w):
+    return w[:, :, :, 0, 0].permute(0, 2, 1).reshape(w.shape[0], 3 * w.shape[1])
+
+
 def temporal_conv3_stacked(x3, conv: nn.Conv3d, with_bias=True):
     """Conv3d with kernel (3,1,1), padding (1,0,0) along the frame axis, given its input already stacked
     as x3 [(b T), 3 Ci, H, W] = (frame t-1 | frame t | frame t+1) (ops.group_norm_frames(stack3=True)):
@@ -441,12 +446,10 @@ def temporal_conv3_stacked(x3, conv: nn.Conv3d, with_bias=True):
     instead of permuting to b c t h w and running an im2col 3-D convolution."""
     ci3 = x3.shape[1]
     w = conv.weight
-    key = (w.data_ptr(), w._version, w.dtype, w.device)
-    hit = getattr(conv, "_w_stacked", None)
-    if hit is None or hit[0] != key:        # tap-major channels [Co, 3 Ci], rebuilt only when the weight changes
-        hit = (key, w.detach()[:, :, :, 0, 0].permute(0, 2, 1).reshape(conv.out_channels, ci3).contiguous())
-        conv._w_stacked = hit
-    wt = hit[1] if not (torch.is_grad_enabled() and w.requires_grad) else w[:, :, :, 0, 0].permute(0, 2, 1).reshape(conv.out_channels, ci3)
+    if torch.is_grad_enabled() and w.requires_grad:
+        wt = _stacked_taps(w)
+    else:                                   # tap-major channels [Co, 3 Ci], rebuilt only when the weight changes
+        wt = derived1("w_stacked", w, lambda w: _stacked_taps(w.detach()).contiguous())
     return F.conv2d(x3, wt.reshape(conv.out_channels, ci3, 1, 1), conv.bias if with_bias else None)
 
 
@@ -458,22 +461,9 @@ def _f32_param(p):
     return p.float()
 
 
-_bias_sums = {}
-
-
 def _sum_param(a, b):
-    """a + b (fp32) for two small parameters, computed once per version of either (two bias vectors met by one fused add).
-    Entries hold weak references to both parameters: ids and addresses recur after a model is freed."""
-    import weakref
-    key = (id(a), id(b))
-    ver = (a.data_ptr(), a._version, b.data_ptr(), b._version, a.dtype, a.device)
-    hit = _bias_sums.get(key)
-    if hit is None or hit[0] != ver or hit[2]() is not a or hit[3]() is not b:
-        hit = (ver, a.detach().float() + b.detach().float(), weakref.ref(a), weakref.ref(b))
-        if len(_bias_sums) > 4096:
-            _bias_sums.clear()
-        _bias_sums[key] = hit
-    return hit[1]
+    """a + b (fp32) for two small parameters, computed once per version of either (two bias vectors met by one fused add)."""
+    return derived("bias_sum", (a, b), lambda: a.detach().float() + b.detach().float())
 
 
 _silu_emb_cache = []          # [(weakref(emb), version, silu(emb))], newest first: UNet and ControlNet each have one embedding per step
@@ -517,9 +507,9 @@ def _emb_plan(root):
         params += [lin.weight, lin.bias, conv.bias]
     if any(p is not None and p.requires_grad and torch.is_grad_enabled() for p in params):
         return None
-    sig = tuple((id(p), p._version, p.data_ptr()) if p is not None else None for p in params)
+    live, absent = [p for p in params if p is not None], tuple(p is None for p in params)
     hit = _emb_plans.get(id(root))
-    if hit is not None and hit[0]() is root and hit[1] == sig:
+    if hit is not None and hit[0]() is root and hit[1].holds(live, absent):
         return hit[2]
     by_width = {}
     for b in blocks:
@@ -535,7 +525,7 @@ def _emb_plan(root):
             cb = torch.cat([(b.in_layers[2].bias.float() if b.in_layers[2].bias is not None else torch.zeros(C, device=dev)) for b in bs], 0)
             groups.append((C, W, bl, cb.contiguous(), [id(b.emb_layers[1]) for b in bs]))
     key = id(root)
-    _emb_plans[key] = (weakref.ref(root, lambda _r, k=key: _emb_plans.pop(k, None)), sig, groups)
+    _emb_plans[key] = (weakref.ref(root, lambda _r, k=key: _emb_plans.pop(k, None)), Signature(live, absent), groups)
     return groups
 
 
@@ -581,42 +571,26 @@ def _emb_chan_bias(emb_layers, emb, conv):
 
 
 NHWC_CONVS = os.environ.get("MVI_SVD_NHWC_CONVS", "1") != "0"
-_cl_weights = {}
 
 
 def _channels_last_weight(w):
     """The convolution weight in channels-last memory format, converted once per parameter version."""
-    key = id(w)
-    hit = _cl_weights.get(key)
-    if hit is None or hit[0]() is not w or hit[1] != (w.data_ptr(), w._version, w.dtype, w.device):
-        import weakref
-        hit = (weakref.ref(w, lambda _r, k=key: _cl_weights.pop(k, None)), (w.data_ptr(), w._version, w.dtype, w.device),
-               w.detach().contiguous(memory_format=torch.channels_last))
-        _cl_weights[key] = hit
-    return hit[2]
+    return derived1("channels_last", w, lambda w: w.detach().contiguous(memory_format=torch.channels_last))
 
 
 CONV_N320 = os.environ.get("MVI_SVD_CONV_N320", "1") != "0"
 CONV_N320_MIN_BLOCKS = 128         # fewer blocks of 256 rows x 320 channels than this leave most of the 256 CUs idle: the kernel splits K
                                    # then (level 3: 64 blocks x 4), or, for a K too short to split, the library runs
-_tap_weights = {}
 
 
 def _tap_major_weight(w):
     """A convolution weight in csrc/linear_n320.hip's implicit-GEMM order, [C_out][taps C_in] tap-major — 3x3 Conv2d weights
     ([C_out, C_in, 3, 3] -> 9 taps) and (3,1,1) Conv3d weights ([C_out, C_in, 3, 1, 1] -> 3 taps) — once per parameter version."""
     from . import hip_ops
-    key = id(w)
-    hit = _tap_weights.get(key)
-    # the packing order of the 3x3 weights is a process-global switch of the kernel (mvi_conv3x3_n320_k_order, read again at every
-    # launch): part of the version, so a switch after the first forward re-packs instead of silently mis-convolving (ADVICE r5)
-    ver = (w.data_ptr(), w._version, w.dtype, w.device, int(hip_ops._lib.lib().mvi_conv3x3_n320_k_order(-1)) if w.dim() == 4 else -1)
-    if hit is None or hit[0]() is not w or hit[1] != ver:
-        import weakref
-        build = hip_ops.conv3t_n320_weight if w.dim() == 5 else hip_ops.conv3x3_n320_weight
-        hit = (weakref.ref(w, lambda _r, k=key: _tap_weights.pop(k, None)), ver, build(w.detach()))
-        _tap_weights[key] = hit
-    return hit[2]
+    if w.dim() == 5:
+        return derived1("tap_major", w, lambda w: hip_ops.conv3t_n320_weight(w.detach()))
+    # the packing order of the 3x3 weights is a process-global switch of the kernel: part of the signature (hip_ops.conv3x3_k_order)
+    return derived1("tap_major", w, lambda w: hip_ops.conv3x3_n320_weight(w.detach()), hip_ops.conv3x3_k_order())
 
 
 def conv3x3_planes_via_tokens(conv, x, upsample=1, tokens_out=False):
@@ -703,7 +677,7 @@ def _tok2tok_ok(N, C, S, groups, dtype):
     """The token-major GroupNorm between the two convolutions has geometry limits of its own (rows per launch, groups, its
     row pass in LDS): a shape outside them keeps the whole block on the NCHW path instead of raising inside it."""
     from . import hip_ops
-    return hip_ops._lib.lib().mvi_groupnorm_tok2tok_workspace_bytes(int(N), int(C), int(S), int(groups), hip_ops._DT[dtype]) != 0
+    return hip_ops.group_norm_tok2tok_supported(N, C, S, groups, dtype)
 
 
 def _planes_add_to_tokens(t, x, bias):

@@ -539,12 +539,8 @@ def linear(x, weight, bias=None):
 
 def linear_module(mod, x):
     """`mod(x)` for an nn.Linear (or Sequential(Linear, Dropout) at inference) through linear()."""
-    if isinstance(mod, torch.nn.Sequential) and len(mod) == 2 and isinstance(mod[0], torch.nn.Linear) \
-            and isinstance(mod[1], torch.nn.Dropout) and not (mod[1].training and mod[1].p > 0):
-        return linear(x, mod[0].weight, mod[0].bias)
-    if type(mod) is torch.nn.Linear:
-        return linear(x, mod.weight, mod.bias)
-    return mod(x)
+    lin = _plain_linear(mod)
+    return mod(x) if lin is None else linear(x, lin.weight, lin.bias)
 
 
 def bias_residual_add(h, bias=None, x=None):

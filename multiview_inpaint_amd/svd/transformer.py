@@ -17,6 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .derived import Signature, derived
 from .layers import AlphaBlender, Tok, linear, maybe_checkpoint, timestep_embedding, to_tok, zero_module
 
 
@@ -56,9 +57,8 @@ def _row_plan(root):
     params = [p for v in kinds.values() for a in v for p in (a.to_v.weight, a.to_out[0].weight, a.to_out[0].bias)]
     if len(params) < 12 or any(p.requires_grad and torch.is_grad_enabled() for p in params):
         return None
-    sig = tuple((id(p), p._version, p.data_ptr()) for p in params)
     hit = _row_plans.get(id(root))
-    if hit is not None and hit[0]() is root and hit[1] == sig:
+    if hit is not None and hit[0]() is root and hit[1].holds(params):
         return hit[2]
     plans = {}
     with torch.no_grad():
@@ -77,7 +77,7 @@ def _row_plan(root):
             M = torch.cat([(a.to_out[0].weight.float() @ a.to_v.weight.float()).to(dt) for a in order], 0).contiguous()     # [sum C, D]
             plans[k] = (M, torch.cat([a.to_out[0].bias for a in order], 0).contiguous(), groups)
     key = id(root)
-    _row_plans[key] = (weakref.ref(root, lambda _r, kk=key: _row_plans.pop(kk, None)), sig, plans)
+    _row_plans[key] = (weakref.ref(root, lambda _r, kk=key: _row_plans.pop(kk, None)), Signature(params), plans)
     return plans
 
 
@@ -219,16 +219,13 @@ class CrossAttention(nn.Module):
         ws = (self.to_q.weight, self.to_k.weight, self.to_v.weight)
         fold = bool(fold and FOLD_SCALE_INTO_WQ and ws[0].is_cuda and ws[0].dtype in (torch.bfloat16, torch.float16)
                     and (act_dtype is None or act_dtype == ws[0].dtype) and not torch.is_grad_enabled())
-        key = tuple((w.data_ptr(), w._version, w.dtype, w.device) for w in ws)
-        slot = "_wqkv_folded" if fold else "_wqkv"
-        hit = getattr(self, slot, None)
-        if hit is None or hit[0] != key:
+
+        def pack():
             wq = ws[0].detach()
             if fold:
                 wq = (wq.float() * (self.scale * LOG2E)).to(wq.dtype)
-            hit = (key, torch.cat([wq, ws[1].detach(), ws[2].detach()], dim=0).contiguous(), fold)
-            setattr(self, slot, hit)
-        return hit[1], hit[2]
+            return torch.cat([wq, ws[1].detach(), ws[2].detach()], dim=0).contiguous()
+        return derived("wqkv_folded" if fold else "wqkv", ws, pack), fold
 
     def forward_temporal(self, x, T, fuse=None):
         """Self-attention over frames for x [(b t), s, c] in place of regroup -> forward -> regroup back (fuse: see forward)."""
@@ -530,13 +527,11 @@ class SpatialVideoTransformer(SpatialTransformer):
         mlp = self.time_pos_embed
         if not CACHE_FRAME_MLP or (torch.is_grad_enabled() and any(p.requires_grad for p in mlp.parameters())):
             return mlp(pe)[:, None, :]
-        key = (id(pe),) + tuple((p.data_ptr(), p._version) for p in mlp.parameters())
-        hit = self.__dict__.get("_pe_mlp")
-        if hit is None or hit[0] != key or hit[1] is not pe:
+
+        def run():
             with torch.no_grad():
-                hit = (key, pe, mlp(pe)[:, None, :])
-            self.__dict__["_pe_mlp"] = hit
-        return hit[2]
+                return mlp(pe)[:, None, :]
+        return derived("pe_mlp", (pe, *mlp.parameters()), run)
 
     def forward(self, x, context=None, time_context=None, timesteps=None, image_only_indicator=None):
         if isinstance(x, Tok) and not self._tok_route_ok(x):

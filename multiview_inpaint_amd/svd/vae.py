@@ -28,6 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .derived import derived
 from .layers import ResBlock, conv_no_bias, temporal_conv3_stacked, timestep_embedding
 from .transformer import VideoTransformerBlock
 
@@ -528,13 +529,12 @@ class AutoencodingEngine(nn.Module):
 
 
 def _decoder_in(first_stage_model, dtype):
-    """A copy of the decoder in `dtype`, made once per version of its parameters and kept on the model object (not a submodule: the
-    state dict stays the reference's)."""
+    """A copy of the decoder in `dtype`, made once per version of its parameters (svd/derived.py; not a submodule: the state dict stays
+    the reference's)."""
     import copy
     dec = first_stage_model.decoder
-    key = tuple((p.data_ptr(), p._version) for p in dec.parameters())
-    hit = first_stage_model.__dict__.get("_mvi_decoder_copies", {}).get(dtype)
-    if hit is None or hit[0] != key:
+
+    def reduced():
         red = copy.deepcopy(dec).to(dtype).eval()
         # what an autocast run keeps in fp32 stays in fp32 here: the affine parameters of the norms (a rounded per-channel gain is a
         # systematic error that no spatial average removes: 1.7 x the reference's bf16-autocast error with them rounded) and the
@@ -544,9 +544,8 @@ def _decoder_in(first_stage_model, dtype):
             mod = red.get_submodule(name.rsplit(".", 1)[0]) if "." in name else red
             if isinstance(mod, nn.GroupNorm) or name.endswith("mix_factor"):
                 p.data = src[name].detach().float().clone()
-        hit = (key, red)
-        first_stage_model.__dict__.setdefault("_mvi_decoder_copies", {})[dtype] = hit
-    return hit[1]
+        return red
+    return derived(("decoder_in", dtype), tuple(dec.parameters()), reduced)
 
 
 DECODE_DTYPE = {"": None, "fp32": None, "bf16": torch.bfloat16, "f16": torch.float16}[os.environ.get("MVI_VAE_DECODE_DTYPE", "")]

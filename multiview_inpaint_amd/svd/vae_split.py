@@ -20,22 +20,15 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from .derived import derived1
 
 SPLIT_DECODE = os.environ.get("MVI_VAE_SPLIT", "1") != "0"      # 0: the fp32 library path of svd/vae.py (same-box A/B)
-_w3_cache = {}
 
 
 def _w3(weight, mode):
-    """split3_weight(weight, mode), once per parameter version and operand mode."""
-    import weakref
+    """split3_weight(weight, mode), once per parameter version, operand mode and packing order of the kernel."""
     from . import hip_ops
-    key = (id(weight), mode)
-    ver = (weight.data_ptr(), weight._version, weight.dtype, weight.device, int(hip_ops._lib.lib().mvi_conv3x3_n320_k_order(-1)))
-    hit = _w3_cache.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != ver:
-        hit = (weakref.ref(weight, lambda _r, k=key: _w3_cache.pop(k, None)), ver, hip_ops.split3_weight(weight, mode))
-        _w3_cache[key] = hit
-    return hit[2]
+    return derived1(("w3", mode), weight, lambda w: hip_ops.split3_weight(w, mode), hip_ops.conv3x3_k_order())
 
 
 def applies(decoder, z):
