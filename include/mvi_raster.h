@@ -257,6 +257,10 @@ int mvi_raster_backward_mode(int dense);
  * binning partition kernel of `pass` (1 | 2) writes 8 shader-clock stamps (uint64) at its phase boundaries into
  * device_buffer[block][8]. The caller sizes the buffer for the launch grid (mvi_raster_binning_bytes / 8 is ample). */
 int mvi_raster_dev_stamps(int pass, void* device_buffer);
+/* Diagnostics for kernel work (tests/test_render_backward_reduce_gpu.py): the 64-lane sum of nine values that the render
+ * backward uses for its per-Gaussian moments, on its own. One wave per w reads in[w][m][lane] (n_waves x 9 x 64 floats on
+ * the device) and writes the nine wave totals to out[w][m] (n_waves x 9 floats), through the same device function. */
+int mvi_raster_dev_wave_sum9(const float* in, float* out, int n_waves, void* stream);
 
 const char* mvi_raster_last_error(void);
 const char* mvi_version(void);

@@ -139,6 +139,8 @@ def lib():
     L.mvi_raster_resolve_colors.argtypes = [C.POINTER(RasterSettings), i32, vp, sz, vp]
     L.mvi_raster_dev_stamps.restype = C.c_int
     L.mvi_raster_dev_stamps.argtypes = [C.c_int, vp]
+    L.mvi_raster_dev_wave_sum9.restype = C.c_int
+    L.mvi_raster_dev_wave_sum9.argtypes = [vp, vp, C.c_int, vp]
     _bind_unet_ops(L)
     _bind_train_ops(L)
     _bind_box_region(L)

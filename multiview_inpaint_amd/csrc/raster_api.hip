@@ -131,6 +131,11 @@ const char* mvi_raster_stage_name(int i) {
     return (i >= 0 && i < MVI_RASTER_NSTAGES) ? n[i] : "";
 }
 int mvi_raster_dev_stamps(int pass, void* device_buffer) { mvi::set_dev_stamps(pass, device_buffer); return MVI_OK; }
+int mvi_raster_dev_wave_sum9(const float* in, float* out, int n_waves, void* stream) {
+    if (n_waves < 0 || (n_waves > 0 && (!in || !out))) return fail(MVI_EINVAL, "wave_sum9: NULL buffer or negative n_waves%s");
+    if (mvi::launch_wave_sum9_probe(in, out, n_waves, (hipStream_t)stream)) return hip_fail("wave_sum9 probe", hipGetLastError());
+    return MVI_OK;
+}
 int mvi_raster_backward_mode(int dense) {
     const int old = g_dense_backward;
     if (dense == 0 || dense == 1) g_dense_backward = dense;

@@ -296,53 +296,88 @@ int launch_zero_regions(const ZeroRegions& z, hipStream_t st) {
 // Per evaluated (half tile, Gaussian) pair every pixel produces 9 RAW moments
 //     W = o G dL/dalpha,  W dx,  W dy,  W dx^2,  W dx dy,  W dy^2,  alpha T dL/dC_{r,g,b}
 // (the per-Gaussian factors — conic coefficients, 1/o, the 0.5 W / 0.5 H screen scale — are applied
-// once per (tile, Gaussian) after the sums). A lane adds its two pixels, two DPP steps give quad totals,
-// then the 16 quad partials of up to kSlabG Gaussians x 9 moments are parked in a per-wave LDS slab
-// (rows of 16, stride 20) and summed by ONE lane per row, which adds the row total into the block's
-// per-entry accumulator. Once per staged batch the block turns the raw sums into gradients and flushes
+// once per (tile, Gaussian) after the sums). A lane adds its two pixels, wave_sum9 sums the nine values over the 64 lanes
+// in registers, and nine lanes add the wave totals into the block's per-entry accumulator (one LDS float atomic, nothing
+// to wait for). Once per staged batch the block turns the raw sums into gradients and flushes
 // them with float atomics shaped as whole 64-byte rows (16 lanes per Gaussian): MI355X float atomics
 // run at the 64-B-request rate. Row layout of grad_rows [P][16]:
 //   0 mean2D.x  1 mean2D.y  2 conic A  3 conic B  4 conic C  5 opacity  6 r  7 g  8 b  9..15 unused
 constexpr int kRow = 16;
-#ifndef MVI_RB_SLAB
-#define MVI_RB_SLAB 3
-#endif
-constexpr int kSlabG = MVI_RB_SLAB;   // Gaussians parked per wave before a row-sum pass (3 x 9 = 27 rows; <= 7: one lane per row)
-constexpr int kSlabStride = 20;    // floats per slab row (16 used; 80-byte rows keep b128 reads conflict-free)
 
-
-// Quad totals of nine values in 18 instructions: v_add_f32_dpp reads the neighbour lane and adds in ONE instruction.
-// Written as asm because the compiler lowers update_dpp + add to v_mov_b32_dpp + v_add (two issues each; the kernel is
-// VALU-issue-bound, SQ_INSTS_VALU x 4 cycles ~ its whole duration). The leading s_nop covers the VALU-write -> DPP-read
-// hazard for whatever instruction precedes the block (the assembler does not pad inline asm); inside the block every
-// value is re-read nine instructions after it was written.
-#define MVI_DPP1 " quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-#define MVI_DPP2 " quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-__device__ __forceinline__ void quad_sum9(float& a, float& b, float& c, float& d, float& e, float& f, float& g, float& h,
-                                          float& i) {
+// Wave totals of nine values by a halving butterfly: one level per bit of the lane index, and at every level TWO live
+// registers are folded into ONE that carries the first value's partial sums in the lanes whose bit is 0 and the second
+// value's in the lanes whose bit is 1 (9 -> 5 -> 3 -> 2 -> 1 registers); the odd register of a level takes a plain
+// full-width step and carries its partial sums in both halves. Levels, in order:
+//   bit 3, bit 2   two v_add_f32_dpp per pair, each writing half of the banks of a row (row_ror:n reads lane (l - n) mod 16
+//                  of the own row of 16: ror 8 is the partner l ^ 8 for every lane; ror 12 / ror 4 is l ^ 4 for the lanes with
+//                  bit 2 clear / set); one full-width add for the odd register (its partial sums no longer depend on bit 3
+//                  when bit 2 is folded, so ror 4 reads a value equal to the partner's in every lane)
+//   bit 4, bit 5   v_permlane16_swap / v_permlane32_swap exchange the odd rows (upper half) of the first register with
+//                  the even rows (lower half) of the second, then one plain add
+//   bit 0, bit 1   two quad_perm adds on the one register that is left
+// Lane <-> moment map of the result (a compile-time function of the lane, wave_sum9_moment): lane l < 32 holds the wave
+// total of argument (l >> 2), lanes 32..63 hold that of argument 8, every lane of a quad the same number. Lanes 0, 4, ..,
+// 32 are the nine owners (wave_sum9_owner). The sum is a balanced tree over the 64 lanes.
+// The DPP adds are asm because the compiler lowers update_dpp + add to v_mov_b32_dpp + v_add (two issues each; the
+// kernel is VALU-issue-bound). The s_nop in front covers the VALU-write -> DPP-read hazard for whatever precedes a block
+// (the assembler does not pad inline asm, and the compiler does not look into it; it does pad the swaps that read a
+// block's outputs); inside the first block every register is re-read at least four instructions after it was written.
+__device__ __forceinline__ constexpr int wave_sum9_moment(int lane) { return lane < 32 ? lane >> 2 : 8; }
+__device__ __forceinline__ constexpr bool wave_sum9_owner(int lane) { return (lane & 3) == 0 && lane <= 32; }
+#define MVI_FOLD(a, b, lo, hi, mlo, mhi)                                                                  \
+    "v_add_f32_dpp " a ", " a ", " a " row_ror:" lo " row_mask:0xf bank_mask:" mlo "\n\t"                  \
+    "v_add_f32_dpp " a ", " b ", " b " row_ror:" hi " row_mask:0xf bank_mask:" mhi "\n\t"
+#define MVI_FULL(a, n) "v_add_f32_dpp " a ", " a ", " a " row_ror:" n " row_mask:0xf bank_mask:0xf\n\t"
+__device__ __forceinline__ float wave_sum9(float m0, float m1, float m2, float m3, float m4, float m5, float m6, float m7,
+                                           float m8) {
     asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0" MVI_DPP1 "v_add_f32_dpp %1, %1, %1" MVI_DPP1 "v_add_f32_dpp %2, %2, %2" MVI_DPP1
-        "v_add_f32_dpp %3, %3, %3" MVI_DPP1 "v_add_f32_dpp %4, %4, %4" MVI_DPP1 "v_add_f32_dpp %5, %5, %5" MVI_DPP1
-        "v_add_f32_dpp %6, %6, %6" MVI_DPP1 "v_add_f32_dpp %7, %7, %7" MVI_DPP1 "v_add_f32_dpp %8, %8, %8" MVI_DPP1
-        "v_add_f32_dpp %0, %0, %0" MVI_DPP2 "v_add_f32_dpp %1, %1, %1" MVI_DPP2 "v_add_f32_dpp %2, %2, %2" MVI_DPP2
-        "v_add_f32_dpp %3, %3, %3" MVI_DPP2 "v_add_f32_dpp %4, %4, %4" MVI_DPP2 "v_add_f32_dpp %5, %5, %5" MVI_DPP2
-        "v_add_f32_dpp %6, %6, %6" MVI_DPP2 "v_add_f32_dpp %7, %7, %7" MVI_DPP2 "v_add_f32_dpp %8, %8, %8" MVI_DPP2
-        : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h), "+v"(i));
+        // bit 3: (m0, m2) -> m0, (m1, m3) -> m1, (m4, m6) -> m4, (m5, m7) -> m5: lanes 0..7 of a row | lanes 8..15
+        MVI_FOLD("%0", "%2", "8", "8", "0x3", "0xc") MVI_FOLD("%1", "%3", "8", "8", "0x3", "0xc")
+        MVI_FOLD("%4", "%6", "8", "8", "0x3", "0xc") MVI_FOLD("%5", "%7", "8", "8", "0x3", "0xc") MVI_FULL("%8", "8")
+        // bit 2: (m0, m1) -> m0, (m4, m5) -> m4: banks 0 and 2 | banks 1 and 3. Lane bits (3, 2) of m0 now name 2 a + b
+        MVI_FOLD("%0", "%1", "12", "4", "0x5", "0xa") MVI_FOLD("%4", "%5", "12", "4", "0x5", "0xa") MVI_FULL("%8", "4")
+        : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3), "+v"(m4), "+v"(m5), "+v"(m6), "+v"(m7), "+v"(m8));
+    // bit 4: rows 0, 2 <- m0..m3, rows 1, 3 <- m4..m7; the odd register is folded with itself
+    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(m0), __float_as_uint(m4), false, false);
+    const auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(m8), __float_as_uint(m8), false, false);
+    const float lo = __uint_as_float(a[0]) + __uint_as_float(a[1]), hi = __uint_as_float(b[0]) + __uint_as_float(b[1]);
+    // bit 5: lanes 0..31 <- m0..m7, lanes 32..63 <- m8
+    const auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
+    float s = __uint_as_float(c[0]) + __uint_as_float(c[1]);
+    asm("s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
+        : "+v"(s));
+    return s;
 }
-#undef MVI_DPP1
-#undef MVI_DPP2
+#undef MVI_FOLD
+#undef MVI_FULL
+
+// Diagnostics (mvi_raster_dev_wave_sum9): one wave per block runs in[w][m][lane] through wave_sum9, the owners write out[w][m]
+__global__ __launch_bounds__(64) void wave_sum9_probe_kernel(const float* __restrict__ in, float* __restrict__ out) {
+    const int lane = threadIdx.x;
+    const float* x = in + (size_t)blockIdx.x * 9 * 64 + lane;
+    const float s = wave_sum9(x[0], x[64], x[128], x[192], x[256], x[320], x[384], x[448], x[512]);
+    if (wave_sum9_owner(lane)) out[blockIdx.x * 9 + wave_sum9_moment(lane)] = s;
+}
+int launch_wave_sum9_probe(const float* in, float* out, int n_waves, hipStream_t st) {
+    if (n_waves <= 0) return 0;
+    hipLaunchKernelGGL(wave_sum9_probe_kernel, dim3(n_waves), dim3(64), 0, st, in, out);
+    return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
+}
 
 // ---- backward, two pixels per lane --------------------------------------------------------------------------------
 // Back-to-front replay of the tile's list (positions < max n_contrib of the tile only) with the same exact box
 // culling as the forward. Every pixel produces 9 raw moments per evaluated Gaussian (W, W dx, W dy, W dx^2, W dx dy,
-// W dy^2, alpha T dL/dC); quad totals by DPP, the 16 quad partials of up to kSlabG Gaussians are parked in a per-wave
-// LDS slab and summed by one lane per row; per (tile, Gaussian) the block converts raw sums into gradients once and
-// flushes them with float atomics shaped as whole 64-byte rows (grad_rows [P][16]).
+// W dy^2, alpha T dL/dC); wave totals in registers (wave_sum9), added into the block's per-entry accumulator by nine
+// lanes; per (tile, Gaussian) the block converts raw sums into gradients once and flushes them with float atomics
+// shaped as whole 64-byte rows (grad_rows [P][16]).
 // The kernel sits at the fp32 VALU issue roof. With one pixel per lane it needed ~90 vector
-// instructions per (wave, Gaussian), ~33 of them (DPP quad sums, slab, drain) independent of how many pixels the wave
+// instructions per (wave, Gaussian), about a third of them (the cross-lane sums) independent of how many pixels the wave
 // covers. Here a wave covers a 16x8 half tile, lane l owning the vertically adjacent pixels (x = l & 15, y = 2 (l >> 4) + {0, 1}):
 // the per-pixel math runs on packed fp32 (v_pk_mul/add/fma_f32: two pixels per instruction at full rate), the two
-// pixels are summed in the lane before the quad reduction, and the reduction/slab cost is paid once per 128 pixels.
+// pixels are summed in the lane before the wave reduction, and the reduction cost is paid once per 128 pixels.
 // Block = 128 threads = one tile; 128 list entries are staged per round. Decisions (alpha, active) use the same
 // operation order as the forward kernel (products rounded, one fma per sum), element-wise.
 #ifndef MVI_RB_WAVES
@@ -363,8 +398,6 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
     __shared__ float4 s_co[kB2];
     __shared__ float4 s_rgb[kB2];
     __shared__ float s_acc[kB2][9];                                   // raw moment sums per staged entry
-    __shared__ __attribute__((aligned(16))) float s_slab[2][kSlabG * 9][kSlabStride];
-    __shared__ int s_slot[2][8];
     __shared__ uint32_t s_blast[2];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int tile = xcd_band_tile(blockIdx.x, f.gx * f.gy);
@@ -399,17 +432,8 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
     __syncthreads();
     const int total = (int)max(s_blast[0], s_blast[1]);
     const int rounds = (total + kB2 - 1) / kB2;
-    const int my_slot = (lane * 57) >> 9, my_mom = lane - 9 * my_slot;      // lane / 9, lane % 9 for lane < 64
-    float (*slab)[kSlabStride] = s_slab[wave];
-    auto drain = [&](int parked) {
-        if (lane < 9 * parked) {
-            const float4* row = reinterpret_cast<const float4*>(slab[lane]);
-            float4 a = row[0], b = row[1], c = row[2], d = row[3];
-            float sum = ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w)) + ((c.x + c.y) + (c.z + c.w)) +
-                        ((d.x + d.y) + (d.z + d.w));
-            atomicAdd(&s_acc[0][0] + (__mul24(s_slot[wave][my_slot], 9) + my_mom), sum);
-        }
-    };
+    const bool owner = wave_sum9_owner(lane);
+    const int my_mom = wave_sum9_moment(lane);
 
     uint32_t n_id = 0;
     float2 n_xy = make_float2(0.f, 0.f);
@@ -435,7 +459,6 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
         for (int c = 0; c < 9; ++c) s_acc[tid][c] = 0.0f;
         __syncthreads();
         if (r + 1 < rounds) fetch(r + 1);
-        int parked = 0;                                         // wave-uniform
         for (int c = 0; c < n; c += 64) {
             const int e = c + lane;
             const bool keep = e < n && (uint32_t)(hi - 1 - e) < wave_last &&
@@ -479,17 +502,8 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
                     const f2 vxx = vx * dx, vxy = vx * dy, vyy = vy * dy;
                     float m_w = mw.x + mw.y, m_x = vx.x + vx.y, m_y = vy.x + vy.y, m_xx = vxx.x + vxx.y,
                           m_xy = vxy.x + vxy.y, m_yy = vyy.x + vyy.y, m_r = vr.x + vr.y, m_g = vg.x + vg.y, m_b = vb.x + vb.y;
-                    quad_sum9(m_w, m_x, m_y, m_xx, m_xy, m_yy, m_r, m_g, m_b);
-                    const int pk = __builtin_amdgcn_readfirstlane(parked);
-                    if ((lane & 3) == 3) {
-                        float* colp = &slab[0][0] + (pk * (9 * kSlabStride) + (lane >> 2));
-                        colp[0 * kSlabStride] = m_w;  colp[1 * kSlabStride] = m_x;  colp[2 * kSlabStride] = m_y;
-                        colp[3 * kSlabStride] = m_xx; colp[4 * kSlabStride] = m_xy; colp[5 * kSlabStride] = m_yy;
-                        colp[6 * kSlabStride] = m_r;  colp[7 * kSlabStride] = m_g;  colp[8 * kSlabStride] = m_b;
-                    }
-                    if (lane == 0) s_slot[wave][pk] = jc;
-                    parked = pk + 1;
-                    if (parked == kSlabG) { drain(kSlabG); parked = 0; }
+                    const float sum = wave_sum9(m_w, m_x, m_y, m_xx, m_xy, m_yy, m_r, m_g, m_b);
+                    if (owner) atomicAdd(&s_acc[0][0] + (__mul24(jc, 9) + my_mom), sum);   // both waves add into the same rows; nobody waits for it
                 }
                 return more;
             };
@@ -501,7 +515,6 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
                 if (!entry(jB, pB, coB, colB, pA, coA, colA, j)) break;
             }
         }
-        if (parked) drain(parked);
         __syncthreads();
         // flush, in two steps per wave (a wave handles the 64 staged entries with its own index range, so only the wave has to
         // agree on LDS): (1) ONE lane per entry turns the raw sums into the nine gradients in place and marks entries that
