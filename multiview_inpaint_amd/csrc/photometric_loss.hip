@@ -10,6 +10,8 @@
 //             partial and writes the three maps D1 = d map/d mu1, D2 = d map/d E[x^2], D3 = d map/d E[xy];
 //   gradient: dL/dx[q] = (1-lambda)/N sign(x - y) - lambda/N (conv(D1) + 2 x conv(D2) + y conv(D3))[q]  (the window is
 //             symmetric and the padding zero, so the adjoint of the convolution is the same convolution), times w.
+// x and y enter both passes minus one offset per channel plane (plane_offset below): the moments, and the maps' derivatives, are taken
+// about it, so that E[x^2] - mu^2 of a nearly constant image is not the difference of two numbers of order one.
 // The per-block partial sums are reduced in a fixed order by one small block: the loss value is deterministic.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,15 +28,38 @@ constexpr int kLR = 5;                  // window radius
 constexpr int kHX = kLX + 2 * kLR, kHY = kLY + 2 * kLR;      // 42 x 26: tile + halo
 constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
 
-struct Win { float w[11]; };
+struct Win {
+    float w[11];
+    float sum;      // sum of the 11 weights
+    float d2;       // 1 - sum of the 121 fp32 products w[i] * w[j] (the reference's 2-D window), formed in double
+};
 
-// x/y value at (py, px) of channel plane `c`, zero outside the image (F.conv2d zero padding)
+// The moments are taken about an offset: x = x' + off inside the image (0 outside, F.conv2d's zero padding), off one value per
+// channel plane (the weighted gt at the image centre; any value is exact, a value near the image's level is accurate). With
+// S = sum of the window weights that fall inside the image, mu = mu' + off S, and
+//   E[x^2] - mu^2 = E[x'^2] - mu'^2 + (2 mu' + off S) off (1 - S),   E[xy] - mu1 mu2 = E[x'y'] - mu1' mu2' + (mu1' + mu2' + off S) off (1 - S):
+// no difference of two numbers of order one is left, so a nearly constant image (variance far below C2) keeps its SSIM digits.
+__device__ __forceinline__ float plane_offset(const float* __restrict__ gt, const float* __restrict__ wmap, int c, int H, int W) {
+    const size_t o = (size_t)(H / 2) * W + W / 2;
+    const float v = gt[(size_t)c * H * W + o];
+    return wmap ? v * wmap[o] : v;
+}
+
+// x/y value minus `off` at (py, px) of channel plane `c`, zero outside the image (F.conv2d zero padding)
 __device__ __forceinline__ float ld_img(const float* __restrict__ img, const float* __restrict__ wmap, int c, int py, int px,
-                                        int H, int W) {
+                                        int H, int W, float off) {
     if (py < 0 || py >= H || px < 0 || px >= W) return 0.0f;
     const size_t o = (size_t)py * W + px;
     const float v = img[(size_t)c * H * W + o];
-    return wmap ? v * wmap[o] : v;
+    return (wmap ? v * wmap[o] : v) - off;
+}
+
+// weight of the window taps around p that fall outside [0, n)
+__device__ __forceinline__ float taps_outside(const Win& win, int p, int n) {
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) s += (p + k - kLR < 0 || p + k - kLR >= n) ? win.w[k] : 0.0f;
+    return s;
 }
 
 // Separable 11-tap passes with register sliding windows (LDS and the vector ALU, not HBM, bound these kernels): in the
@@ -56,6 +81,7 @@ __global__ __launch_bounds__(256) void loss_stats_kernel(const float* __restrict
     // without bounds checks for tiles whose halo lies inside the image)
     const int lane = tid & 63, wv = tid >> 6;
     const bool interior = x0 >= kLR && x0 + kLX + kLR <= W && y0 >= kLR && y0 + kLY + kLR <= H;
+    const float off = plane_offset(gt, wmap, c, H, W);
     if (lane < kHX) {
         const int px = x0 + lane - kLR;
         if (interior) {
@@ -63,11 +89,11 @@ __global__ __launch_bounds__(256) void loss_stats_kernel(const float* __restrict
 #pragma unroll
             for (int r = wv; r < kHY; r += 4) {
                 const float m = wmap ? wmap[mbase + (size_t)r * W] : 1.0f;
-                s_xy[r][lane] = f2{img[base + (size_t)r * W] * m, gt[base + (size_t)r * W] * m};
+                s_xy[r][lane] = f2{img[base + (size_t)r * W] * m - off, gt[base + (size_t)r * W] * m - off};
             }
         } else {
             for (int r = wv; r < kHY; r += 4)
-                s_xy[r][lane] = f2{ld_img(img, wmap, c, y0 + r - kLR, px, H, W), ld_img(gt, wmap, c, y0 + r - kLR, px, H, W)};
+                s_xy[r][lane] = f2{ld_img(img, wmap, c, y0 + r - kLR, px, H, W, off), ld_img(gt, wmap, c, y0 + r - kLR, px, H, W, off)};
         }
     }
     __syncthreads();
@@ -107,20 +133,29 @@ __global__ __launch_bounds__(256) void loss_stats_kernel(const float* __restrict
     }
     float map_sum = 0.f, l1_sum = 0.f;
     const int px = x0 + tx;
+    const float out_x = interior ? 0.0f : taps_outside(win, px, W);
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
         const int py = y0 + ty + o;
         if (px < W && py < H) {
-            const float mu1 = m1[o].x, mu2 = m1[o].y, e11 = m2[o].x, e22 = m2[o].y, e12 = m3[o];
-            const float mu1s = mu1 * mu1, mu2s = mu2 * mu2, mu12 = mu1 * mu2;
-            const float s1 = e11 - mu1s, s2 = e22 - mu2s, s12 = e12 - mu12;
-            const float A1 = 2.0f * mu12 + kC1, A2 = 2.0f * s12 + kC2, B1 = mu1s + mu2s + kC1, B2 = s1 + s2 + kC2;
+            // 1 - S: exactly win.d2 where the whole window lies inside the image
+            const float out_y = interior ? 0.0f : taps_outside(win, py, H);
+            const float omS = win.d2 + (win.sum * (out_x + out_y) - out_x * out_y);
+            const float cS = off * (1.0f - omS), kk = off * omS;
+            const float a = m1[o].x, b = m1[o].y, e11 = m2[o].x, e22 = m2[o].y, e12 = m3[o];       // moments about `off`
+            const float mu1 = a + cS, mu2 = b + cS;
+            const float s1 = (e11 - a * a) + (2.0f * a + cS) * kk, s2 = (e22 - b * b) + (2.0f * b + cS) * kk,
+                        s12 = (e12 - a * b) + (a + b + cS) * kk;
+            const float A1 = 2.0f * mu1 * mu2 + kC1, A2 = 2.0f * s12 + kC2, B1 = mu1 * mu1 + mu2 * mu2 + kC1, B2 = s1 + s2 + kC2;
             const float inv = 1.0f / (B1 * B2);
             const float map = A1 * A2 * inv;
+            const float d2 = -map / B2, d3 = 2.0f * A1 * inv;
             const size_t idx = ((size_t)c * H + py) * W + px, plane = (size_t)3 * H * W;
-            dmaps[idx] = (2.0f * mu2 * (A2 - A1) - 2.0f * mu1 * map * (B2 - B1)) * inv;     // d map / d mu1
-            dmaps[plane + idx] = -map / B2;                                                 // d map / d E[x^2]
-            dmaps[2 * plane + idx] = 2.0f * A1 * inv;                                       // d map / d E[xy]
+            // d map / d mu1' with E[x'^2], E[x'y'] held: through A1, B1 (mu2 B1 - mu1 A1 = (mu2 - mu1)(mu2 (mu1 + mu2) + C1), and
+            // mu2 - mu1 = b - a exactly) and through s1, s12
+            dmaps[idx] = 2.0f * A2 * inv / B1 * ((b - a) * (mu2 * (mu1 + mu2) + kC1)) + d2 * (2.0f * kk - 2.0f * a) + d3 * (kk - b);
+            dmaps[plane + idx] = d2;                                                        // d map / d E[x'^2]
+            dmaps[2 * plane + idx] = d3;                                                    // d map / d E[x'y']
             map_sum += map;
             const f2 ctr = s_xy[ty + o + kLR][tx + kLR];
             l1_sum += fabsf(ctr.x - ctr.y);
@@ -236,6 +271,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
         }
     }
     const int px = x0 + tx;
+    const float off = plane_offset(gt, wmap, c, H, W);
     const float inv_n = 1.0f / (3.0f * (float)H * (float)W);
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
@@ -245,7 +281,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
         const float wv = wmap ? wmap[o2] : 1.0f;
         const float x = img[idx] * wv, y = gt[idx] * wv;
         const float sgn = x > y ? 1.0f : (x < y ? -1.0f : 0.0f);
-        const float conv = g12[o].x + 2.0f * x * g12[o].y + y * g3[o];
+        const float conv = g12[o].x + 2.0f * (x - off) * g12[o].y + (y - off) * g3[o];     // the maps are derivatives about `off`
         if (kTwo) {
             dL_dimg[idx] = (w2[0] * inv_n * sgn + w2[1] * inv_n * conv) * wv;
         } else {
@@ -269,6 +305,13 @@ static Win make_window() {
     for (int i = 0; i < 11; ++i) sf += gf[i];
     for (int i = 0; i < 11; ++i) w.w[i] = gf[i] / sf;
     (void)s;
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = 0; i < 11; ++i) {
+        s1 += (double)w.w[i];
+        for (int j = 0; j < 11; ++j) s2 += (double)(w.w[i] * w.w[j]);       // fp32 products: _1D_window.mm(_1D_window.t())
+    }
+    w.sum = (float)s1;
+    w.d2 = (float)(1.0 - s2);
     return w;
 }
 
