@@ -476,6 +476,18 @@ int mvi_conv3x3_split3_f32(const void* x2, const void* weight, float* out, int64
                            int32_t terms, int32_t dtype, int64_t out_rows_capacity, void* stream);
 int mvi_conv3t_split3_f32(const void* x2, const void* weight, float* out, int64_t B, int32_t T, int32_t pixels, int32_t C, int32_t C_out,
                           int32_t terms, int32_t dtype, int64_t out_rows_capacity, void* stream);
+/* The first-stage ENCODER's Downsample.conv (sgm/modules/diffusionmodules/model.py Downsample.forward: 3x3, stride 2, padding 0 over
+ * F.pad(x, (0, 1, 0, 1))) on the operands of mvi_conv3x3_split3_f32 (same x2 / weight formats, terms / dtype rules, alignment, 32-bit
+ * offset limit on the INPUT tensor): rows are OUTPUT pixels [N, Ho, Wo], Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1; needs H, W >= 2;
+ * out [mvi_conv_split3_out_rows(N Ho Wo), C_out] fp32, no bias. */
+int mvi_conv3x3_s2_split3_f32(const void* x2, const void* weight, float* out, int64_t N, int32_t H, int32_t W, int32_t C, int32_t C_out,
+                              int32_t terms, int32_t dtype, int64_t out_rows_capacity, void* stream);
+/* Encoder.conv_in for the token-major fp32 walk (csrc/stem_conv_f32.hip): x [N, C_in, H, W] fp32 planes, weight [C_out, C_in, 3, 3] fp32 as the
+ * module stores it, bias [C_out] or NULL -> out [N, H W, C_out] fp32 = conv2d(x, weight, bias, stride 1, padding 1) as token rows. Exact fp32
+ * FMA chains (no operand rounding). 1 <= C_in <= 4, C_out a multiple of 4 (<= 1024); weight, bias, out 16-byte aligned. */
+int mvi_conv3x3_small_cin_f32_tokens_supported(int32_t C_in, int32_t C_out);
+int mvi_conv3x3_small_cin_f32_tokens(const float* x, const float* weight, const float* bias, float* out, int64_t N, int32_t C_in, int32_t H,
+                                     int32_t W, int32_t C_out, void* stream);
 /* GroupNorm(+SiLU) of fp32 token-major x [N, S, C] written as split bf16 y2 [N, S, 2 C] = (hi | lo) (out_mode 0) or as one rounded value per
  * element, y2 [N, S, C] bf16 (out_mode 1) / f16 (out_mode 2); frames > 1: statistics per video of `frames` consecutive samples; groups = 0:
  * no normalisation (plain split / rounding). Workspace: mvi_groupnorm_tok2tok_workspace_bytes(.., MVI_DT_F32). */

@@ -84,6 +84,10 @@ struct ConvGeom {
                                                      // chunk cc of a tap reads physical chunk cc - cpc / 3 once cc >= cpc / 3 (cpc = 3 C / 64)
     int out_cols;                                    // > 0 (with kSplit): the fp32 accumulators ARE the result — stored to `part` [ksplit][padded
                                                      // rows][out_cols], columns >= out_cols (the padding of C_out to whole column groups) dropped, no reduction
+    // The first-stage ENCODER's Downsample (model.py Downsample.forward: 3x3 / stride 2 / padding 0 over F.pad(x, (0, 1, 0, 1))):
+    int origin;                                      // 0 or 1 (last: every shorter initialiser means 0): the row's centre is input pixel
+                                                     // (stride yo + origin, stride xo + origin). With origin 1 the border tests below ARE the zero
+                                                     // row / column of the asymmetric pad: conv(pad(x, (0,1,0,1)), stride 2) == conv(x, padding 1)[1::2, 1::2]
 };
 // kUps (round 6, the token stream's Upsample.conv: openaimodel.py:107-150): cg.H, cg.W are those of the nearest-neighbour 2x UPSAMPLED image, x
 // holds the (H / 2) x (W / 2) source — pixel (y, x) reads source (y >> 1, x >> 1): the convolution of F.interpolate(x, scale_factor=2)
@@ -234,7 +238,7 @@ void linear_n320_kernel(const T* __restrict__ x, const T* __restrict__ w, const 
         if (kConv) {
             const int64_t img = rclamp / ((int64_t)cg.Ho * cg.Wo);
             const int pix = (int)(rclamp - img * ((int64_t)cg.Ho * cg.Wo));
-            const int py = pix / cg.Wo * cg.stride, px = (pix - pix / cg.Wo * cg.Wo) * cg.stride;  // the centre, in the input image
+            const int py = pix / cg.Wo * cg.stride + cg.origin, px = (pix - pix / cg.Wo * cg.Wo) * cg.stride + cg.origin;  // the centre, in the input image
             if (cg.stride != 1) x_voff[t] = (uint32_t)(((img * cg.H + py) * cg.W + px) * x_rs * 2 + 16 * kg);
             if (kUps) {
                 x_voff[t] = (uint32_t)(((img * (cg.H >> 1) + (py >> 1)) * (cg.W >> 1) + (px >> 1)) * x_rs * 2 + 16 * kg);
@@ -1114,8 +1118,9 @@ extern "C" int mvi_conv_split3_group(int32_t C_out) {
 
 extern "C" int64_t mvi_conv_split3_out_rows(int64_t rows) { return (rows + mvi::ln3::kRows - 1) / mvi::ln3::kRows * mvi::ln3::kRows; }
 
+// down2: the encoder's Downsample form (mvi_conv3x3_s2_split3_f32 below) — rows are the output pixels, everything else is the same launch
 static int conv_split3(const char* what, const void* x2, const void* weight, float* out, int64_t N, int32_t H, int32_t W, int32_t taps,
-                       int32_t C, int32_t C_out, int32_t terms, int32_t dtype, int64_t out_rows_capacity, void* stream) {
+                       int32_t C, int32_t C_out, int32_t terms, int32_t dtype, int64_t out_rows_capacity, void* stream, bool down2 = false) {
     char msg[200];
     auto fail = [&](const char* m) {
         snprintf(msg, sizeof msg, "%s: %s", what, m);
@@ -1125,7 +1130,9 @@ static int conv_split3(const char* what, const void* x2, const void* weight, flo
     if (!((terms == 3 && dtype == MVI_DT_BF16) || (terms == 1 && (dtype == MVI_DT_BF16 || dtype == MVI_DT_F16))))
         return fail("terms = 3 (split operands, bf16) or terms = 1 (plain bf16 / f16 operands)");
     if (terms == 1 && taps * C < 2 * mvi::ln3::kKC) return fail("the contraction needs at least two chunks of 64");
-    const int64_t rows = N * H * W;
+    if (down2 && (H < 2 || W < 2)) return fail("stride 2 over pad (0, 1, 0, 1) needs H, W >= 2");
+    const int32_t stride = down2 ? 2 : 1, Ho = down2 ? (H - 2) / 2 + 1 : H, Wo = down2 ? (W - 2) / 2 + 1 : W;
+    const int64_t rows = N * Ho * Wo;
     if (rows == 0) return MVI_OK;
     if (!x2 || !weight || !out) return fail("NULL pointer");
     if (((uintptr_t)x2 | (uintptr_t)weight | (uintptr_t)out) % 16) return fail("x2, weight and out must be 16-byte aligned");
@@ -1133,11 +1140,11 @@ static int conv_split3(const char* what, const void* x2, const void* weight, flo
     const int group = mvi_conv_split3_group(C_out);
     const int groups = (C_out + group - 1) / group;
     const int64_t x_rs = (terms == 3 ? 2 : 1) * (int64_t)C;       // physical row: (hi | lo), or the one rounded value
-    if ((int64_t)group * taps * terms * C * 2 > 0xFFFFFFFFll || rows * x_rs * 2 > 0xFFFFFFFFll || (int64_t)H * W > 0x7FFFFFFFll)
+    if ((int64_t)group * taps * terms * C * 2 > 0xFFFFFFFFll || N * H * W * x_rs * 2 > 0xFFFFFFFFll || (int64_t)H * W > 0x7FFFFFFFll)
         return fail("weight group / activation tensor exceeds 32-bit byte offsets (split the batch)");
     const int k_order = taps == 9 ? g_conv_k_order : 0;
-    const mvi::ln3::ConvGeom cg = {H, W, terms * C / mvi::ln3::kKC, taps, groups, 1, 1, H, W, k_order,
-                                   (taps == 3 && g_conv_k_order && W % mvi::ln3::kRows == 0) ? 1 : 0, terms == 3 ? 1 : 0, C_out};
+    const mvi::ln3::ConvGeom cg = {H, W, terms * C / mvi::ln3::kKC, taps, groups, 1, stride, Ho, Wo, k_order,
+                                   (taps == 3 && g_conv_k_order && W % mvi::ln3::kRows == 0) ? 1 : 0, terms == 3 ? 1 : 0, C_out, down2 ? 1 : 0};
     hipStream_t st = (hipStream_t)stream;
     const int K = taps * terms * C;
     int rc;
@@ -1162,4 +1169,12 @@ extern "C" int mvi_conv3x3_split3_f32(const void* x2, const void* weight, float*
 extern "C" int mvi_conv3t_split3_f32(const void* x2, const void* weight, float* out, int64_t B, int32_t T, int32_t pixels, int32_t C,
                                      int32_t C_out, int32_t terms, int32_t dtype, int64_t out_rows_capacity, void* stream) {
     return conv_split3("conv3t_split3_f32", x2, weight, out, B, T, pixels, 3, C, C_out, terms, dtype, out_rows_capacity, stream);
+}
+
+// The first-stage ENCODER's Downsample.conv (sgm/modules/diffusionmodules/model.py Downsample.forward: 3x3, stride 2, padding 0 over
+// F.pad(x, (0, 1, 0, 1))) on the same operands: rows are OUTPUT pixels [N, Ho, Wo], Ho = (H - 2) / 2 + 1, Wo = (W - 2) / 2 + 1, the
+// row's centre is input pixel (2 yo + 1, 2 xo + 1) (ConvGeom::origin) and the taps past the last row / column are the pad's zeros.
+extern "C" int mvi_conv3x3_s2_split3_f32(const void* x2, const void* weight, float* out, int64_t N, int32_t H, int32_t W, int32_t C,
+                                         int32_t C_out, int32_t terms, int32_t dtype, int64_t out_rows_capacity, void* stream) {
+    return conv_split3("conv3x3_s2_split3_f32", x2, weight, out, N, H, W, 9, C, C_out, terms, dtype, out_rows_capacity, stream, true);
 }

@@ -1240,6 +1240,67 @@ def conv_split3(x2, w3, N, H, W, C_out, taps=9, mode="split3", _max_bytes=0xFFFF
     return out[:rows]
 
 
+def conv_split3_s2_plan(N, H, W, row_bytes, max_bytes=0xFFFFFFFF):
+    """(Ho, Wo, images per launch) of conv_split3_s2 — pure arithmetic, no device. Ho, Wo: the output of a 3x3 / stride 2 convolution over
+    F.pad(x, (0, 1, 0, 1)); the batch is cut by INPUT image bytes (H W row_bytes each: the kernel's 32-bit offsets span the input tensor)."""
+    if H < 2 or W < 2:
+        raise ValueError("conv_split3_s2: H, W >= 2 expected")
+    per = H * W * row_bytes
+    if per > 0xFFFFFFFF:
+        raise ValueError("conv_split3_s2: one image exceeds the kernel's 32-bit activation offsets")
+    return (H - 2) // 2 + 1, (W - 2) // 2 + 1, max(1, min(N, max_bytes // per))
+
+
+def conv_split3_s2(x2, w3, N, H, W, C_out, mode="split3", _max_bytes=0xFFFFFFFF):
+    """Downsample.conv of the first-stage encoder (3x3, stride 2, padding 0 over F.pad(x, (0, 1, 0, 1))) on the operands of conv_split3:
+    x2 [N H W, 2 C] (or [N H W, C] in modes "bf16" / "f16"), w3 from split3_weight -> fp32 [N Ho Wo, C_out], no bias
+    (mvi_conv3x3_s2_split3_f32). The batch is cut by input bytes; the output advances by Ho Wo rows per image."""
+    L = _lib.lib()
+    terms, dt, _ = _OPERANDS[mode]
+    Cx = x2.shape[-1]
+    C = Cx // 2 if terms == 3 else Cx
+    if x2.dtype != dt or not x2.is_contiguous() or x2.numel() != N * H * W * Cx or w3.shape[1] != 9 * terms * C or w3.dtype != dt:
+        raise ValueError(f"conv_split3_s2 ({mode}): x2 contiguous {dt} [N H W, {'2 C' if terms == 3 else 'C'}] and w3 [C_out padded, 9 {terms} C] expected")
+    Ho, Wo, n_max = conv_split3_s2_plan(N, H, W, Cx * 2, _max_bytes)
+    x2 = x2.reshape(N * H * W, Cx)
+    rows = N * Ho * Wo
+    cap = int(L.mvi_conv_split3_out_rows(rows)) + 256
+    out = torch.empty(cap, C_out, dtype=torch.float32, device=x2.device)
+    with torch.cuda.device(x2.device), _Timed("conv_split3_s2", 2.0 * rows * 9 * terms * C * C_out, x2.device):
+        for n0 in range(0, N, n_max):
+            n = min(n_max, N - n0)
+            r0 = n0 * Ho * Wo
+            _check(L.mvi_conv3x3_s2_split3_f32(x2[n0 * H * W:].data_ptr(), w3.data_ptr(), out[r0:].data_ptr(), n, H, W, C, C_out, terms, _DT[dt],
+                                               cap - r0, _stream(x2.device)), "conv_split3_s2")
+    return out[:rows]
+
+
+def conv_in_f32_tokens_supported(conv, x):
+    """A 3x3 / stride 1 / padding 1 fp32 Conv2d of at most 4 input channels on a contiguous fp32 GPU tensor (csrc/stem_conv_f32.hip)."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and conv.weight.dtype == torch.float32
+            and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1)
+            and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros" and x.shape[1] == conv.in_channels
+            and bool(_lib.lib().mvi_conv3x3_small_cin_f32_tokens_supported(int(conv.in_channels), int(conv.out_channels))))
+
+
+def conv_in_f32_tokens(x, conv):
+    """conv(x) for fp32 planes x [N, C_in <= 4, H, W] as token-major fp32 [N, H W, C_out], bias included: exact fp32 FMA chains, the
+    output written once in the layout the split-operand walk reads (mvi_conv3x3_small_cin_f32_tokens)."""
+    L = _lib.lib()
+    if not conv_in_f32_tokens_supported(conv, x):
+        raise ValueError(f"conv_in_f32_tokens: unsupported convolution / input {tuple(x.shape)} {x.dtype}")
+    xc = _contig(x)
+    N, Cin, H, W = xc.shape
+    Co = conv.out_channels
+    wc = _contig(conv.weight.detach())
+    b = None if conv.bias is None else _contig(conv.bias.detach())
+    out = torch.empty(N, H * W, Co, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _Timed("conv_in_f32_tokens", float(xc.numel() + out.numel()) * 4, x.device):
+        _check(L.mvi_conv3x3_small_cin_f32_tokens(xc.data_ptr(), wc.data_ptr(), _ptr(b), out.data_ptr(), N, Cin, H, W, Co, _stream(x.device)),
+               "conv_in_f32_tokens")
+    return out
+
+
 def rows_axpb(a, b, bias, alpha=1.0, out=None):
     """a + alpha * (b + bias[c]) for fp32 token-major a, b [..., C] in one pass (mvi_rows_axpb_f32); out may be a or b (default: b)."""
     L = _lib.lib()

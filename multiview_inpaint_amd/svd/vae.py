@@ -590,9 +590,32 @@ def decode_first_stage(first_stage_model, z, scale_factor: float = 0.18215, en_a
     return torch.cat(outs, dim=0)
 
 
+ENCODE_MODE = {"": None, "fp32": None, "split3": "split3"}[os.environ.get("MVI_VAE_ENCODE", "")]
+
+
 @torch.no_grad()
-def encode_first_stage(first_stage_model, x, scale_factor: float = 0.18215, en_and_decode_n_samples_a_time: Optional[int] = None):
-    """sgm/models/diffusion.py:214-226."""
+def encode_first_stage(first_stage_model, x, scale_factor: float = 0.18215, en_and_decode_n_samples_a_time: Optional[int] = None,
+                       mode: Optional[str] = None, unregularized: bool = False):
+    """sgm/models/diffusion.py:214-226.
+    mode "split3" (or MVI_VAE_ENCODE=split3): an opt-in of this package — the encoder's 3x3 convolutions on the bf16 matrix pipe with split
+    operands on token-major fp32 activations (svd/vae_split.py encode: the decoder's arithmetic, the fp32 contract of 1e-4), then the
+    model's regularization as AutoencodingEngine.encode applies it. An explicit mode="split3" the walk cannot serve raises; the
+    environment form falls back to the default. mode None / "fp32" without the variable: first_stage_model.encode, unchanged.
+    unregularized: the encoder's moments (AutoencodingEngine.encode(unregularized=True)), unscaled."""
+    if mode not in (None, "fp32", "split3"):
+        raise ValueError(f"encode_first_stage: unknown mode {mode!r}")
+    split = mode == "split3"
+    if mode is None and ENCODE_MODE == "split3":
+        from . import vae_split
+        split = vae_split.encoder_applies(first_stage_model.encoder, x)
     n = x.shape[0] if en_and_decode_n_samples_a_time is None else en_and_decode_n_samples_a_time
-    outs = [first_stage_model.encode(x[r * n:(r + 1) * n]) for r in range(math.ceil(x.shape[0] / n))]
-    return scale_factor * torch.cat(outs, dim=0)
+
+    def enc(xc):
+        if split:
+            from . import vae_split
+            m = vae_split.encode(first_stage_model.encoder, xc)              # (raises where the walk does not apply)
+            return m if unregularized else first_stage_model.regularization(m)[0]
+        return first_stage_model.encode(xc, unregularized=True)[0] if unregularized else first_stage_model.encode(xc)
+    outs = [enc(x[r * n:(r + 1) * n]) for r in range(math.ceil(x.shape[0] / n))]
+    z = torch.cat(outs, dim=0)
+    return z if unregularized else scale_factor * z

@@ -59,20 +59,28 @@ def _gn(h, norm, mode, silu=True, chan_bias=None, frames=1):
     return hip_ops.group_norm_split(h, norm.num_groups, norm.weight, norm.bias, norm.eps, silu, chan_bias=chan_bias, frames=frames, mode=mode)
 
 
-def _resblock(blk, h, N, H, W, T, alpha, mode):
-    """vae.VideoResBlock.forward on token-major fp32 h [N, H W, C_in] -> [N, H W, C_out]."""
+def _resblock_spatial(blk, h, N, H, W, mode, per_image=False):
+    """vae.ResnetBlock.forward without temb (model.py:96-158: norm1-SiLU-conv1, norm2(+conv1 bias)-SiLU-conv2, + shortcut) on
+    token-major fp32 h [N, H W, C_in] -> [N, H W, C_out]: the encoder's block, and the spatial half of the decoder's.
+    per_image: the 1x1 shortcut as one library GEMM per image (see encode)."""
     from . import hip_ops
     S, Co = H * W, blk.out_channels
-    # spatial ResnetBlock (model.py:96-158): norm1-SiLU-conv1, norm2(+conv1 bias)-SiLU-conv2, + shortcut
     c = hip_ops.conv_split3(_gn(h, blk.norm1, mode), _w3(blk.conv1.weight, mode), N, H, W, Co, mode=mode).view(N, S, Co)
     e = blk.conv1.bias.float()[None].expand(N, -1).contiguous()
     c = hip_ops.conv_split3(_gn(c, blk.norm2, mode, chan_bias=e), _w3(blk.conv2.weight, mode), N, H, W, Co, mode=mode).view(N, S, Co)
     if blk.in_channels != blk.out_channels:
         sk = blk.nin_shortcut
-        x = F.linear(h, sk.weight.reshape(Co, blk.in_channels), sk.bias)
-        x = hip_ops.rows_axpb(x, c, blk.conv2.bias)                   # shortcut + (conv2 + bias), one pass, into c's storage
-    else:
-        x = hip_ops.rows_axpb(h, c, blk.conv2.bias)                   # h + (conv2 + bias)
+        wsk = sk.weight.reshape(Co, blk.in_channels)
+        x = torch.stack([F.linear(h[n], wsk, sk.bias) for n in range(N)]) if per_image else F.linear(h, wsk, sk.bias)
+        return hip_ops.rows_axpb(x, c, blk.conv2.bias)                # shortcut + (conv2 + bias), one pass, into c's storage
+    return hip_ops.rows_axpb(h, c, blk.conv2.bias)                    # h + (conv2 + bias)
+
+
+def _resblock(blk, h, N, H, W, T, alpha, mode):
+    """vae.VideoResBlock.forward on token-major fp32 h [N, H W, C_in] -> [N, H W, C_out]."""
+    from . import hip_ops
+    S, Co = H * W, blk.out_channels
+    x = _resblock_spatial(blk, h, N, H, W, mode)
     # temporal ResBlock over the frame axis (temporal_ae.py:41-54 -> openaimodel.py:328-354 with dims = 3, skip_t_emb), blended
     ts = blk.time_stack
     g0, g1, c1, c2 = ts.in_layers[0], ts.out_layers[0], ts.in_layers[2], ts.out_layers[3]
@@ -146,3 +154,82 @@ def decode(decoder, z, timesteps, mode="split3"):
     else:
         y = tm(y.reshape(N // T, T, *y.shape[1:]).transpose(1, 2)).transpose(1, 2).reshape(N, -1, H, W)
     return torch.tanh(y) if decoder.tanh_out else y
+
+
+# ---- The ENCODER (sgm/modules/diffusionmodules/model.py:487-601) on the same arithmetic: opt-in (svd/vae.py encode_first_stage(mode="split3")
+# or MVI_VAE_ENCODE=split3); Encoder.forward itself stays on the planes path.
+
+def _encoder_levels(encoder, H, W):
+    """[(H, W)] of every resolution level: Downsample.conv halves as (H - 2) // 2 + 1 (3x3, stride 2 over pad (0, 1, 0, 1))."""
+    out = [(H, W)]
+    for _ in range(encoder.num_resolutions - 1):
+        H, W = (H - 2) // 2 + 1, (W - 2) // 2 + 1
+        out.append((H, W))
+    return out
+
+
+def encoder_applies(encoder, x):
+    """The split walk serves a plain vae.Encoder: fp32 parameters, an fp32 GPU input, no autograd, no attention inside the levels, a plain
+    AttnBlock in the middle, ResnetBlocks of channel counts % 64 == 0 without conv_shortcut, convolutional Downsamples, every level at
+    least 2 x 2, and a conv_in the fp32 stem kernel takes."""
+    from . import hip_ops, vae as V
+    if not (type(encoder) is V.Encoder and torch.is_tensor(x) and x.dim() == 4 and x.is_cuda and x.dtype == torch.float32
+            and not torch.is_grad_enabled() and all(p.dtype == torch.float32 for p in encoder.parameters())
+            and type(encoder.mid.attn_1) is V.AttnBlock and all(len(d.attn) == 0 for d in encoder.down)
+            and all(d.downsample.with_conv for d in encoder.down[:-1])):
+        return False
+    blocks = [b for d in encoder.down for b in d.block] + [encoder.mid.block_1, encoder.mid.block_2]
+    if not all(type(b) is V.ResnetBlock and b.in_channels % 64 == 0 and b.out_channels % 64 == 0
+               and not (b.in_channels != b.out_channels and b.use_conv_shortcut) for b in blocks):
+        return False
+    levels = _encoder_levels(encoder, x.shape[2], x.shape[3])
+    return all(h >= 2 and w >= 2 for h, w in levels[:-1]) and min(levels[-1]) >= 1 and hip_ops.conv_in_f32_tokens_supported(encoder.conv_in, x)
+
+
+def _downsample(down, h, N, H, W, mode):
+    """vae.Downsample.forward (model.py Downsample: pad (0, 1, 0, 1), 3x3 / stride 2) on tokens -> [N, Ho Wo, C] with the bias."""
+    from . import hip_ops
+    C = h.shape[-1]
+    t2 = hip_ops.group_norm_split(h, 0, None, None, 0.0, False, mode=mode)            # plain split / rounding
+    c = hip_ops.conv_split3_s2(t2, _w3(down.conv.weight, mode), N, H, W, C, mode=mode)
+    return c.view(N, -1, C).add_(down.conv.bias)
+
+
+@torch.no_grad()
+def encode(encoder, x, mode="split3"):
+    """Encoder.forward(x) (model.py:487-601) -> moments [N, 2 z, H / 8, W / 8] fp32, on token-major fp32 activations with the 3x3
+    convolutions on split operands: conv_in by the fp32 stem kernel straight into tokens, the ResnetBlocks as the decoder's spatial half,
+    Downsample.conv by the stride-2 entry, the middle attention as the decoder's, conv_out by the library on the channels-last view.
+    What goes to the GEMM / convolution libraries (the two 1x1 shortcuts, the attention block, conv_out) goes there ONE IMAGE AT A TIME:
+    the libraries choose kernels, and with them summation orders, by problem size, and a frame's moments must not depend on how many
+    frames the caller encodes at once (encode_first_stage(en_and_decode_n_samples_a_time=...)). This package's own kernels compute a
+    row independently of the batch; the one exception is the statistics pass of the token GroupNorm, whose partition of a large image
+    follows the launch size — bit-equality between chunkings is therefore a property of images of a few thousand pixels (tested), at
+    576x1024 the chunkings agree to rounding."""
+    from . import hip_ops
+    if not encoder_applies(encoder, x):
+        raise ValueError("vae_split.encode: this encoder / input is outside the split path (vae_split.encoder_applies)")
+    N, _, H, W = x.shape
+    h = hip_ops.conv_in_f32_tokens(x, encoder.conv_in)
+    for i_level in range(encoder.num_resolutions):
+        down = encoder.down[i_level]
+        for blk in down.block:
+            h = _resblock_spatial(blk, h, N, H, W, mode, per_image=True)
+        if i_level != encoder.num_resolutions - 1:
+            h = _downsample(down.downsample, h, N, H, W, mode)
+            H, W = (H - 2) // 2 + 1, (W - 2) // 2 + 1
+    h = _resblock_spatial(encoder.mid.block_1, h, N, H, W, mode)
+    h = torch.cat([_attn(encoder.mid.attn_1, h[n:n + 1]) for n in range(N)])
+    h = _resblock_spatial(encoder.mid.block_2, h, N, H, W, mode)
+    no = encoder.norm_out
+    h = ops.group_norm_tok2tok(h, no.num_groups, no.weight, no.bias, no.eps, silu=True)
+    co = encoder.conv_out
+    # (512 -> 8 channels: the library picks a solver that accumulates with atomics unless told not to — the only op of this walk whose
+    # bits changed from run to run; everything before it is deterministic by construction)
+    det = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    x = h.view(N, H, W, -1).permute(0, 3, 1, 2)                                          # [N, C, H, W] with channels-last strides: no copy
+    try:
+        return torch.cat([F.conv2d(x[n:n + 1], co.weight, co.bias, co.stride, co.padding) for n in range(N)]).contiguous()
+    finally:
+        torch.backends.cudnn.deterministic = det
