@@ -225,6 +225,20 @@ int mvi_conv3x3_n320(const void* x, const void* weight, const float* bias, void*
                      int32_t C_out, int32_t stride, int64_t out_rows_capacity, int64_t out_row_stride, int32_t dtype, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* Weight gradient of that 3x3 / padding 1 / stride 1 convolution (training: csrc/conv3x3_wgrad.hip):
+ *     dweight[co][ci][ky][kx] = sum over (n, y, x) of dy[n, y, x, co] * x[n, y + ky - 1, x + kx - 1, ci], pixels outside the image 0.
+ * x [N, H W, C_in] and dy [N, H W, C_out] token-major in one 16-bit dtype, contiguous, 16-byte aligned; dweight fp32 in the module's
+ * own [C_out, C_in, 3, 3] order, every element written once (N = 0: zeros). C_in and C_out multiples of 64, bf16 / f16 (fp32 is
+ * declined with the invalid-argument status), W <= 256. No atomics: where the output tiles alone would not fill the chip the pixel
+ * axis is split over blocks — a pure function of the shape —, fp32 partials go to `workspace` (..._workspace_bytes(); 0 = this shape
+ * is not split) and a second launch adds them in a fixed order. workspace NULL or too small: the unsplit launch. Two runs give the
+ * same bits. The input gradient needs no kernel of its own: it is mvi_conv3x3_n320 of dy with the weight
+ * W'[ci][co][ky][kx] = W[co][ci][2 - ky][2 - kx]. */
+int mvi_conv3x3_wgrad_supported(int32_t C_in, int32_t C_out, int32_t dtype);
+size_t mvi_conv3x3_wgrad_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out);
+int mvi_conv3x3_wgrad(const void* x, const void* dy, float* dweight, int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out,
+                      int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* conv3x3(F.interpolate(x, scale_factor=2, mode="nearest")) of token-major x [N, h w, C_in] -> out [N, (2 h)(2 w), C_out]: Upsample.conv
  * (openaimodel.py:107-150) with the upsampling in the kernel's addressing (round 6: the token-major residual stream). Conditions and
  * out capacity as mvi_conv3x3_n320 at (N, 2 h, 2 w), stride 1. */

@@ -1,0 +1,227 @@
+// Weight gradient of the 3x3 / padding 1 / stride 1 convolution on token-major activations for gfx950, bf16 / f16:
+//     dweight[co][ci][ky][kx] = sum over (n, y, x) of dy[n, y, x, co] * x[n, y + ky - 1, x + kx - 1, ci]      (outside the image: 0)
+// a GEMM per tap with M = C_out, N = C_in and the PIXEL as contraction index — the slow axis of both operands in memory. Both are
+// staged row-major ([pixel][channel]) in LDS and BOTH MFMA operands are read transposed with ds_read_b64_tr_b16 (ff_geglu_bwd.hip
+// reads its A operand this way): element j of lane (c, g) is pixel row (j < 4 ? 4 g + j : 16 + 4 g + j - 4) of the 32-pixel step,
+// the same order in A and B.
+//
+// The border rule lives in the LDS images, not in the loop. An image is walked in a PADDED linear pixel space with rows of
+// P = W + 2 positions: dy at position q = r P + c is dy[n, r, c] for c < W and 0 for the two pad positions; x at position
+// q' = rr P + cc is x[n, rr - 1, cc - 1], 0 outside the image (the forward's tap_ok rule). Then tap (ky, kx) of dy position q reads
+// x position q + ky P + kx: the nine taps are nine ROW OFFSETS into one x image, the pad positions of dy annihilate what wraps
+// round a row end, and the loop has no mask and no divergence (every transposed read runs with EXEC all ones on addresses inside
+// the initialised image; pad, don't mask). Cost: (W + 2) / W more contraction steps (3 % at W = 64, 25 % at W = 8).
+//
+// Block = 4 waves, a 64 (C_out) x 64 (C_in) tile of all nine taps. Per chunk of kKc = 160 padded positions of one image it loads the
+// dy rows once (160 x 64 channels) and the x rows with their halo once (160 + 2 P + 2 rows), then runs 5 steps of 32 pixels. A wave
+// owns 16 input channels: NINE ACCUMULATOR SETS (nine taps x four 16 x 16 tiles of C_out = 36 tiles, 144 registers), so a step is
+// 8 transposed reads for the four A fragments shared by the taps, 18 for the nine B fragments, 36 MFMAs. Nine passes would have
+// needed the accumulators of one tap at a time and so either nine loads of dy or a write of partials per chunk.
+// LDS rows are 160 bytes apart (40 banks: the 8 rows of a 32-lane half of a transposed read cover the 64 banks once).
+//
+// Split: the output-tile grid alone is (C_out / 64)(C_in / 64) blocks, 25 at 320 x 320. The chunks (N x ceil(H P / 160)) are cut into
+// S contiguous ranges, S = min(chunks, 512 / tiles, 64) — a pure host function of the shape (split_of). S = 1: blocks store dweight.
+// S > 1: block (tile, s) stores its fp32 partial to workspace[s], and a second launch adds the S partials in index order. No atomics;
+// run-to-run identical bits. Addresses are 64-bit throughout.
+//
+// -Rpass-analysis=kernel-resource-usage (hipcc 7, -O3, the flags of attn_bwd.hip), per instance:
+//   conv3x3_wgrad_kernel<bf16> and <f16>: 196 VGPRs, 0 AGPRs, 69 SGPRs, no scratch, occupancy 2 waves per SIMD;
+//   LDS dynamic, 160 (2 kKc + 2 P + 2) bytes: 72 640 at W = 64 (two blocks per CU), 56 000 at W = 12; W <= 256 (134 400).
+//   conv3x3_wgrad_reduce_kernel: 12 VGPRs, no LDS, no scratch.
+#include <atomic>
+#include <cstdint>
+
+#include "mfma_common.h"
+#include "unet_host.h"
+
+namespace mvi {
+namespace cwg {
+
+constexpr int kBM = 64;                         // C_out per block
+constexpr int kBN = 64;                         // C_in per block (16 per wave)
+constexpr int kWaves = 4;
+constexpr int kKc = 160;                        // padded pixel positions per chunk
+constexpr int kSteps = kKc / 32;
+constexpr int kRow = 160;                       // LDS row stride in bytes: 64 channels + 32 bytes of padding
+constexpr int kMaxW = 256;
+constexpr int kMaxSplit = 64;
+constexpr int kTargetBlocks = 512;              // two blocks on each of the 256 CUs
+
+template <typename T> using Mma = MmaBuiltin16<T>;
+
+__host__ __device__ constexpr int x_rows(int W) { return kKc + 2 * (W + 2) + 2; }
+
+template <typename T>
+__global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void conv3x3_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ out, int H, int W, int C_in, int C_out,
+                          int chunks_per_image, int64_t chunks, int splits) {
+    using M = Mma<T>;
+    using frag = typename M::frag;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    MVI_AS3 char* const ldy = (MVI_AS3 char*)smem;
+    MVI_AS3 char* const lx = ldy + kKc * kRow;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c16 = lane & 15, g = lane >> 4;
+    const int ci_tiles = C_in / kBN;
+    const int co0 = ((int)blockIdx.x / ci_tiles) * kBM, ci0 = ((int)blockIdx.x % ci_tiles) * kBN;
+    const int s = blockIdx.y;
+    const int64_t ch_begin = chunks * s / splits, ch_end = chunks * (s + 1) / splits;
+    const int P = W + 2;
+    const int XR = x_rows(W);
+
+    // transposed read of a 4-row x 16-column block: lane 4 q + p of a 16-lane group addresses row q, columns 4 p .. 4 p + 3
+    const uint32_t tr = (uint32_t)((4 * g + (c16 >> 2)) * kRow + 8 * (c16 & 3));
+    const uint32_t tr_b = tr + (uint32_t)(32 * wave);              // the wave's 16 input channels
+
+    f32x4 acc[9][4];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) acc[t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int piece = tid & 7, row0 = tid >> 3;                    // 16-byte piece of a 64-channel row; 32 rows per pass of the block
+    for (int64_t ch = ch_begin; ch < ch_end; ++ch) {
+        const int64_t n = ch / chunks_per_image;
+        const int q0 = (int)(ch - n * chunks_per_image) * kKc;
+        const T* const dyn = dy + n * H * W * (int64_t)C_out + co0 + 8 * piece;
+        const T* const xn = x + n * H * W * (int64_t)C_in + ci0 + 8 * piece;
+        __syncthreads();                                           // the previous chunk's reads are done
+        u32x4 v[kKc / 32];
+#pragma unroll
+        for (int i = 0; i < kKc / 32; ++i) {
+            const int q = q0 + row0 + 32 * i;
+            const int r = q / P, c = q - r * P;
+            v[i] = u32x4{0u, 0u, 0u, 0u};
+            if (r < H && c < W) v[i] = *reinterpret_cast<const u32x4*>(dyn + (int64_t)(r * W + c) * C_out);
+        }
+#pragma unroll
+        for (int i = 0; i < kKc / 32; ++i) *reinterpret_cast<MVI_AS3 u32x4*>(ldy + (row0 + 32 * i) * kRow + 16 * piece) = v[i];
+#pragma unroll 4
+        for (int row = row0; row < XR; row += 32) {
+            const int q = q0 + row;
+            const int rr = q / P, cc = q - rr * P;
+            u32x4 w = u32x4{0u, 0u, 0u, 0u};
+            if (rr >= 1 && rr <= H && cc >= 1 && cc <= W) w = *reinterpret_cast<const u32x4*>(xn + (int64_t)((rr - 1) * W + cc - 1) * C_in);
+            *reinterpret_cast<MVI_AS3 u32x4*>(lx + row * kRow + 16 * piece) = w;
+        }
+        __syncthreads();
+
+#pragma unroll 1
+        for (int st = 0; st < kSteps; ++st) {
+            const uint32_t so = (uint32_t)(32 * st * kRow);
+            frag a[4];
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(ldy + so + tr + 32 * mt));
+                s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(ldy + so + tr + 32 * mt + 16 * kRow));
+                const u32x2 l = *reinterpret_cast<u32x2*>(&lo4), h = *reinterpret_cast<u32x2*>(&hi4);
+                a[mt] = as_frag<frag>(u32x4{l[0], l[1], h[0], h[1]});
+            }
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const uint32_t to = so + (uint32_t)(((t / 3) * P + t % 3) * kRow) + tr_b;
+                s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(lx + to));
+                s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(lx + to + 16 * kRow));
+                const u32x2 l = *reinterpret_cast<u32x2*>(&lo4), h = *reinterpret_cast<u32x2*>(&hi4);
+                const frag b = as_frag<frag>(u32x4{l[0], l[1], h[0], h[1]});
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt) acc[t][mt] = M::mfma(a[mt], b, acc[t][mt]);
+            }
+        }
+    }
+
+    // register i of lane (c, g) of tile (t, mt) = dweight[co0 + 16 mt + 4 g + i][ci0 + 16 wave + c][tap t]
+    float* const op = out + (int64_t)s * C_out * C_in * 9 + ((int64_t)(co0 + 4 * g) * C_in + ci0 + 16 * wave + c16) * 9;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int t = 0; t < 9; ++t) op[(int64_t)(16 * mt + i) * C_in * 9 + t] = acc[t][mt][i];
+}
+
+// out[i] = part[0][i] + part[1][i] + ... in that order
+__global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_kernel(const f32x4* __restrict__ part, f32x4* __restrict__ out, int64_t n4,
+                                                                   int splits) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    f32x4 a = part[i];
+    for (int s = 1; s < splits; ++s) a += part[s * n4 + i];
+    out[i] = a;
+}
+
+static bool shape_ok(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out) {
+    return N >= 0 && H >= 1 && W >= 1 && W <= kMaxW && C_in > 0 && C_out > 0 && C_in % kBN == 0 && C_out % kBM == 0 &&
+           (int64_t)H * (W + 2) < (1ll << 30) && (int64_t)(C_in / kBN) * (C_out / kBM) <= 0x7FFFFFFFll;
+}
+
+// The split policy: a pure function of the shape.
+static int split_of(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out, int* chunks_per_image) {
+    const int cpi = (int)(((int64_t)H * (W + 2) + kKc - 1) / kKc);
+    const int64_t chunks = N * cpi, tiles = (int64_t)(C_in / kBN) * (C_out / kBM);
+    int64_t S = kTargetBlocks / tiles;
+    if (S > kMaxSplit) S = kMaxSplit;
+    if (S > chunks) S = chunks;
+    if (chunks_per_image) *chunks_per_image = cpi;
+    return S < 2 ? 1 : (int)S;
+}
+
+template <typename T>
+static int launch(const void* x, const void* dy, float* dweight, int64_t N, int H, int W, int C_in, int C_out, void* ws, size_t ws_bytes,
+                  hipStream_t st) {
+    int cpi = 0;
+    int S = split_of(N, H, W, C_in, C_out, &cpi);
+    const int64_t total = (int64_t)C_out * C_in * 9;
+    if (S > 1 && (!ws || ws_bytes < (size_t)S * total * sizeof(float))) S = 1;          // no workspace: the unsplit launch
+    const int lds_bytes = (kKc + x_rows(W)) * kRow;
+    static std::atomic<unsigned long long> attr_set{0};          // per device and instantiation: the opt-in for > 64 KiB of dynamic LDS
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MVI_EHIP;
+    auto kern = &conv3x3_wgrad_kernel<T>;
+    if (!(attr_set.load(std::memory_order_acquire) >> dev & 1ull)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+            return MVI_EHIP;
+        attr_set.fetch_or(1ull << dev, std::memory_order_release);
+    }
+    const unsigned tiles = (unsigned)((C_in / kBN) * (C_out / kBM));
+    hipLaunchKernelGGL(kern, dim3(tiles, (unsigned)S), dim3(64 * kWaves), lds_bytes, st, (const T*)x, (const T*)dy,
+                       S > 1 ? (float*)ws : dweight, H, W, C_in, C_out, cpi, N * cpi, S);
+    if (hipGetLastError() != hipSuccess) return MVI_EHIP;
+    if (S > 1) {
+        const int64_t n4 = total / 4;
+        hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const f32x4*)ws, (f32x4*)dweight,
+                           n4, S);
+        if (hipGetLastError() != hipSuccess) return MVI_EHIP;
+    }
+    return 0;
+}
+
+}  // namespace cwg
+}  // namespace mvi
+
+extern "C" int mvi_conv3x3_wgrad_supported(int32_t C_in, int32_t C_out, int32_t dtype) {
+    return C_in > 0 && C_out > 0 && C_in % mvi::cwg::kBN == 0 && C_out % mvi::cwg::kBM == 0 && (dtype == MVI_DT_BF16 || dtype == MVI_DT_F16);
+}
+
+extern "C" size_t mvi_conv3x3_wgrad_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out) {
+    if (!mvi::cwg::shape_ok(N, H, W, C_in, C_out) || N == 0) return 0;
+    const int S = mvi::cwg::split_of(N, H, W, C_in, C_out, nullptr);
+    return S > 1 ? (size_t)S * (size_t)C_out * C_in * 9 * sizeof(float) : 0;
+}
+
+extern "C" int mvi_conv3x3_wgrad(const void* x, const void* dy, float* dweight, int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out,
+                                 int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!mvi_conv3x3_wgrad_supported(C_in, C_out, dtype) || !mvi::cwg::shape_ok(N, H, W, C_in, C_out))
+        return mvi::unet_fail(MVI_EINVAL, "conv3x3 wgrad: needs C_in and C_out multiples of 64, bf16 or f16, 1 <= W <= 256");
+    if (!x || !dy || !dweight) return mvi::unet_fail(MVI_EINVAL, "conv3x3 wgrad: NULL pointer");
+    if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dweight | (uintptr_t)workspace) % 16)
+        return mvi::unet_fail(MVI_EINVAL, "conv3x3 wgrad: x, dy, dweight and workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) return hipMemsetAsync(dweight, 0, (size_t)C_out * C_in * 9 * sizeof(float), st) == hipSuccess ? MVI_OK : MVI_EHIP;
+    const int rc = mvi::dispatch_dtype16(dtype, "conv3x3 wgrad: unknown dtype", [&](auto t) {
+        return mvi::cwg::launch<typename decltype(t)::type>(x, dy, dweight, N, H, W, C_in, C_out, workspace, workspace_bytes, st);
+    });
+    return rc == MVI_EHIP ? mvi::unet_fail(rc, "conv3x3 wgrad: kernel launch failed") : rc;
+}

@@ -757,18 +757,65 @@ def conv3t_n320_fills_chip(B, T, S, C_in, C_out, min_blocks):
     return blocks >= min_blocks or int(_lib.lib().mvi_conv3t_n320_workspace_bytes(B, T, S, C_in, C_out)) > 0
 
 
-def conv3x3_n320(tok, weight_taps, bias, H, W, stride=1, split=True, gn=None, up2=False):
+def conv3x3_n320(tok, weight_taps, bias, H, W, stride=1, split=True, gn=None, up2=False, kind="conv3x3_n320"):
     """3x3 / padding 1 convolution (stride 1 or 2) to a multiple of 320 output channels of token-major activations tok [N, H W, C_in]
     (csrc/linear_n320.hip in its implicit-GEMM mode) -> [N, Ho Wo, C_out]; weight_taps from conv3x3_n320_weight.
     gn = (groups, chan_bias): -> (out, GnPartials) for the GroupNorm that follows (see _conv_taps_n320).
-    up2: the convolution of the nearest-neighbour 2x upsampled image (mvi_conv3x3_up2_n320) -> [N, (2 H)(2 W), C_out]."""
+    up2: the convolution of the nearest-neighbour 2x upsampled image (mvi_conv3x3_up2_n320) -> [N, (2 H)(2 W), C_out].
+    kind: the PROFILE kind of the launch ("conv3x3_dgrad" when it computes an input gradient, conv3x3_dgrad below)."""
     N, S, C = tok.shape
     if S != H * W:
         raise ValueError("conv3x3_n320: tok [N, H W, C_in] expected")
-    r = _conv_taps_n320("conv3x3_n320", tok, weight_taps, bias, N, H, W, 9, stride, split, gn=gn, up2=up2)
+    r = _conv_taps_n320(kind, tok, weight_taps, bias, N, H, W, 9, stride, split, gn=gn, up2=up2)
     if gn is not None:
         return r[0].view(N, -1, weight_taps.shape[0]), r[1]
     return r.view(N, -1, weight_taps.shape[0])
+
+
+# ---- the 3x3 convolution under autograd (ops._Conv3x3TokensFn): dgrad on the forward kernel, wgrad in csrc/conv3x3_wgrad.hip ----------
+
+CONV3X3_WGRAD_MAX_W = 256                       # csrc/conv3x3_wgrad.hip: the x chunk with its two halo rows has to fit in LDS
+
+
+def conv3x3_transposed_weight(weight):
+    """The weight whose 3x3 / padding 1 / stride 1 convolution of dy is the input gradient of conv(x, weight):
+    W'[ci, co, ky, kx] = W[co, ci, 2 - ky, 2 - kx], as a view [C_in, C_out, 3, 3]. Pure torch; loads no library."""
+    return weight.flip(2, 3).transpose(0, 1)
+
+
+def conv3x3_dgrad(dy_tok, weight_t_taps, H, W, split=True):
+    """dx [N, H W, C_in] of the 3x3 / padding 1 / stride 1 convolution from dy [N, H W, C_out]: the forward kernel on the packed
+    transposed weight (conv3x3_n320_weight(conv3x3_transposed_weight(weight))), channel roles swapped. PROFILE kind conv3x3_dgrad."""
+    return conv3x3_n320(dy_tok, weight_t_taps, None, H, W, split=split, kind="conv3x3_dgrad")
+
+
+def conv3x3_wgrad_supported(C_in, C_out, dtype):
+    return dtype in (torch.bfloat16, torch.float16) and bool(_lib.lib().mvi_conv3x3_wgrad_supported(int(C_in), int(C_out), _DT[dtype]))
+
+
+def conv3x3_wgrad_workspace_bytes(N, H, W, C_in, C_out):
+    """> 0: csrc/conv3x3_wgrad.hip splits the pixel axis of this shape over blocks (a pure host function of the shape)."""
+    return int(_lib.lib().mvi_conv3x3_wgrad_workspace_bytes(int(N), int(H), int(W), int(C_in), int(C_out)))
+
+
+def conv3x3_wgrad(tok, dy_tok, H, W, split=True):
+    """dweight, fp32 [C_out, C_in, 3, 3], of the 3x3 / padding 1 / stride 1 convolution from its input tok [N, H W, C_in] and the output
+    gradient dy_tok [N, H W, C_out] (one 16-bit dtype): csrc/conv3x3_wgrad.hip, deterministic. split = False withholds the workspace
+    (the unsplit launch). PROFILE kind conv3x3_wgrad."""
+    L = _lib.lib()
+    if tok.dim() != 3 or dy_tok.dim() != 3 or tok.shape[:2] != dy_tok.shape[:2] or tok.shape[1] != H * W or tok.dtype != dy_tok.dtype:
+        raise ValueError("conv3x3_wgrad: tok [N, H W, C_in] and dy_tok [N, H W, C_out] of one dtype expected")
+    N, S, C = tok.shape
+    Co = dy_tok.shape[2]
+    xc = tok if tok.is_contiguous() and tok.data_ptr() % 16 == 0 else tok.contiguous().clone()
+    dc = dy_tok if dy_tok.is_contiguous() and dy_tok.data_ptr() % 16 == 0 else dy_tok.contiguous().clone()
+    dw = torch.empty(Co, C, 3, 3, dtype=torch.float32, device=tok.device)
+    ws_bytes = int(L.mvi_conv3x3_wgrad_workspace_bytes(N, H, W, C, Co)) if split else 0
+    ws = _workspace(tok.device, ws_bytes) if ws_bytes else None
+    with torch.cuda.device(tok.device), _Timed("conv3x3_wgrad", 2.0 * N * S * 9 * C * Co, tok.device):
+        _check(L.mvi_conv3x3_wgrad(xc.data_ptr(), dc.data_ptr(), dw.data_ptr(), N, H, W, C, Co, _DT.get(tok.dtype, -1), _ptr(ws), ws_bytes,
+                                   _stream(tok.device)), "conv3x3_wgrad")
+    return dw
 
 
 def conv3t_n320(tok, weight_taps, bias, T, split=True, gn=None):

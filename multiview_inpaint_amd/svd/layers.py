@@ -673,6 +673,32 @@ def _nhwc_path_ok(self, x):
             and _tok2tok_ok(x.shape[0], conv1.out_channels, x.shape[2] * x.shape[3], self.out_layers[0].num_groups, x.dtype))
 
 
+# The ResBlock under autograd with its two convolutions on ops.conv3x3_tokens (MVI_RESBLOCK_CONV_BWD=1, or layers.RESBLOCK_CONV_BWD = True).
+# Off by default — a tested opt-in, like encode_first_stage(mode="split3"): parity-tested (tests/test_conv3x3_bwd_gpu.py) and ahead in
+# the bench's ResBlock line (14 x 320 x 48x64 bf16, forward + backward: 1.383 against 1.940 ms, spread 0.055;
+# profiles/conv3x3_bwd_bench.json), but the existing suite has not been run with it on, which is the other condition for the default.
+RESBLOCK_CONV_BWD = os.environ.get("MVI_RESBLOCK_CONV_BWD", "0") == "1"
+
+
+def _conv_bwd_path_ok(self, x, emb):
+    """Under autograd: do both convolutions of this block pass ops.conv3x3_tokens' conditions (switches, the three kernels' gates, the
+    speed decision)?"""
+    conv1, conv2 = self.in_layers[2], self.out_layers[3]
+    if not (RESBLOCK_CONV_BWD and ops.CONV3X3_BACKWARD and torch.is_grad_enabled() and x.is_cuda and x.dim() == 4
+            and x.dtype in (torch.bfloat16, torch.float16) and isinstance(conv1, nn.Conv2d) and isinstance(conv2, nn.Conv2d)
+            and conv1.weight.dtype == x.dtype and conv2.weight.dtype == x.dtype
+            and all(tuple(c.kernel_size) == (3, 3) and tuple(c.stride) == (1, 1) and tuple(c.padding) == (1, 1)
+                    and tuple(c.dilation) == (1, 1) and c.groups == 1 for c in (conv1, conv2))
+            and x.shape[1] % 8 == 0 and conv1.out_channels % 8 == 0 and (x.shape[2] * x.shape[3]) % 8 == 0):
+        return False
+    if not (x.requires_grad or emb.requires_grad or any(p.requires_grad for p in self.parameters())):
+        return False
+    N, C, H, W = x.shape
+    return all(ops.conv3x3_tokens_gates(N, H, W, ci, c.out_channels, x.dtype)
+               and ops.conv3x3_backward_pays(N, H, W, ci, c.out_channels, x.dtype, c.weight.requires_grad)
+               for c, ci in ((conv1, C), (conv2, conv1.out_channels)))
+
+
 def _tok2tok_ok(N, C, S, groups, dtype):
     """The token-major GroupNorm between the two convolutions has geometry limits of its own (rows per launch, groups, its
     row pass in LDS): a shape outside them keeps the whole block on the NCHW path instead of raising inside it."""
@@ -710,6 +736,22 @@ def _resblock_forward_fused(self, x, emb, tokens_out=False):
         sb = sk.bias if conv2.bias is None else (conv2.bias if sk.bias is None else _sum_param(sk.bias, conv2.bias))
         return last_add(t, conv_no_bias(sk, x, None), sb)                      # both biases ride on the transposing add
     assert not tokens_out, "tokens_out is only offered on the channels-last route (_nhwc_path_ok)"
+    if _conv_bwd_path_ok(self, x, emb):
+        # under autograd with both convolutions on ops.conv3x3_tokens (HIP forward, dgrad and wgrad): the norms write tokens
+        # (ops.group_norm_tokens has a HIP backward), the turn back to planes between them is a plain copy autograd differentiates
+        g1, g2 = self.in_layers[0], self.out_layers[0]
+        N, _, H, W = x.shape
+        t = ops.group_norm_tokens(x, g1.num_groups, g1.weight, g1.bias, g1.eps, silu=True)
+        e = _emb_chan_bias(self.emb_layers, emb, conv1)
+        t = ops.conv3x3_tokens(t, conv1.weight, H, W)
+        hp = t.transpose(1, 2).reshape(N, conv1.out_channels, H, W)
+        t = ops.group_norm_tokens(hp, g2.num_groups, g2.weight, g2.bias, g2.eps, silu=True, chan_bias=e)
+        t = ops.conv3x3_tokens(self.out_layers[2](t), conv2.weight, H, W)
+        if isinstance(self.skip_connection, nn.Identity):
+            return ops.tokens_to_planes_add(t, x, conv2.bias)
+        sk = self.skip_connection
+        sb = sk.bias if conv2.bias is None else (conv2.bias if sk.bias is None else sk.bias + conv2.bias)
+        return ops.tokens_to_planes_add(t, conv_no_bias(sk, x, None), sb)
     h = conv_no_bias(conv1, norm_act(self.in_layers, x))
     e = _emb_chan_bias(self.emb_layers, emb, conv1)
     h = self.out_layers[0](h, silu=True, chan_bias=e)

@@ -11,9 +11,12 @@ forward takes), and so do GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip: `group_norm`
 from the sizes at which they were measured faster, `linear_geglu_backward_pays` / `geglu_backward_pays`), and the residual add(s) +
 LayerNorm of the transformer blocks (csrc/layernorm_bwd.hip: `add_layer_norm` for every width its forward takes, where
 `add_layer_norm_backward_pays` says so).
+The 3x3 convolution of token-major activations has a HIP backward too (`conv3x3_tokens`: the input gradient on the forward's
+implicit-GEMM kernel with the transposed weight, the weight gradient on csrc/conv3x3_wgrad.hip), where `conv3x3_backward_pays` says
+so; the ResBlock reaches it through the opt-in layers.RESBLOCK_CONV_BWD.
 Every other kernel is forward-only: a GPU tensor that requires grad goes through PyTorch-ROCm's differentiable ops there
-(the projections and convolutions — `linear_add_layer_norm` under grad is `linear_module` + `add_layer_norm` —, `add_lerp`, the
-token-major `group_norm_tok2tok`).
+(the projections, the strided, upsampling and frame convolutions — `linear_add_layer_norm` under grad is `linear_module` +
+`add_layer_norm` —, `add_lerp`, the token-major `group_norm_tok2tok`).
 
 Reference ops: GroupNorm32 + SiLU (sgm/modules/diffusionmodules/util.py:259-276,
 openaimodel.py:257-261,292-305), Normalize (sgm/modules/attention.py:125-128),
@@ -767,3 +770,117 @@ def tokens_to_planes_add(tok, x_in, bias=None):
     _fallback(tok, "tokens_to_planes_add", _why(tok, x_in))
     t = tok if bias is None else tok + bias.to(tok.dtype)
     return t.transpose(1, 2).reshape(x_in.shape) + x_in
+
+
+# The 3x3 / padding 1 / stride 1 convolution of token-major activations under autograd: forward and input gradient on
+# csrc/linear_n320.hip's implicit GEMM, weight gradient on csrc/conv3x3_wgrad.hip. MVI_CONV3X3_BWD=0 (or ops.CONV3X3_BACKWARD = False):
+# a convolution that requires grad takes PyTorch-ROCm's F.conv2d again.
+CONV3X3_BACKWARD = os.environ.get("MVI_CONV3X3_BWD", "1") != "0"
+CONV3X3_MIN_BLOCKS = 128                 # the forward's fill-the-chip line (layers.CONV_N320_MIN_BLOCKS)
+CONV3X3_BACKWARD_MIN_ROWS = 14 * 12 * 16          # from here every measured class won (profiles/conv3x3_bwd_bench.json)
+CONV3X3_BACKWARD_MIN_ROWS_SMALL = 14 * 6 * 8      # the smallest measured size: bf16, or f16 without the weight gradient
+
+
+def conv3x3_backward_pays(N, H, W, C_in, C_out, dtype, need_dweight):
+    """Whether forward + backward on the HIP kernels is faster than F.conv2d under autograd for this shape class — the routing's
+    second question after conv3x3_tokens_gates. Measured by tools/bench_conv_bwd.py (profiles/conv3x3_bwd_bench.json; DESIGN.md
+    '3x3 convolution under autograd'): forward + backward by device events, the two routes alternating in one process, 9 pairs, medians;
+    a class goes to HIP only where its median beats the PyTorch route's by more than that route's spread. ms HIP / PyTorch (spread),
+    dx only | all gradients, bf16 at N = 14 (N = 28 and f16: the JSON; same verdicts except where noted):
+      48x64   320 ->  320   0.314 / 0.524 (0.015) | 0.481 / 0.835 (0.023)    wins
+      48x64   640 ->  320   0.401 / 0.811 (0.013) | 0.648 / 1.276 (0.054)    wins
+      24x32   640 ->  640   0.292 / 0.467 (0.013) | 0.478 / 0.672 (0.034)    wins
+      24x32  1280 ->  640   0.385 / 0.701 (0.029) | 0.711 / 1.073 (0.029)    wins
+      12x16  1280 -> 1280   0.231 / 0.432 (0.017) | 0.453 / 0.702 (0.035)    wins
+      12x16  2560 -> 1280   0.394 / 0.750 (0.044) | 0.837 / 1.263 (0.013)    wins
+       6x8   1280 -> 1280   0.154 / 0.331 (0.019) | 0.303 / 0.491 (0.013)    wins in bf16; f16: dx only wins (0.229 / 0.276, N = 28
+                                                                             0.242 / 0.292), all gradients LOSES (0.344 / 0.342, 0.439 / 0.408)
+    Every class of 14 x 12x16 pixels and more won in both types, both batch sizes and both gradient sets; the 6x8 level won except in
+    f16 with the weight gradient. Nothing below 14 x 6x8 rows was measured and nothing there is routed. One run on one machine."""
+    rows = N * H * W
+    if rows >= CONV3X3_BACKWARD_MIN_ROWS:
+        return True
+    if rows >= CONV3X3_BACKWARD_MIN_ROWS_SMALL:
+        return dtype == torch.bfloat16 or not need_dweight
+    return False
+
+
+def conv3x3_tokens_gates(N, H, W, C_in, C_out, dtype):
+    """Do the three launches of _Conv3x3TokensFn take this shape? The forward's conditions (layers._conv_tokens: the kernel's channel
+    gate, 32-bit byte offsets, enough blocks or a K split), the same with the channel roles swapped for the input gradient, and
+    csrc/conv3x3_wgrad.hip's gate."""
+    from . import hip_ops
+    rows = N * H * W
+    return (dtype in (torch.bfloat16, torch.float16) and rows > 0
+            and hip_ops.conv3x3_n320_supported(C_in, C_out, dtype) and hip_ops.conv3x3_n320_supported(C_out, C_in, dtype)
+            and rows * max(C_in, C_out) * 2 < 2 ** 32
+            and hip_ops.conv3x3_n320_fills_chip(N, H, W, C_in, C_out, CONV3X3_MIN_BLOCKS)
+            and hip_ops.conv3x3_n320_fills_chip(N, H, W, C_out, C_in, CONV3X3_MIN_BLOCKS)
+            and hip_ops.conv3x3_wgrad_supported(C_in, C_out, dtype) and W <= hip_ops.CONV3X3_WGRAD_MAX_W)
+
+
+def _conv3x3_packed(weight):
+    """The weight in the forward kernel's order, once per parameter version (the entry layers._tap_major_weight keeps)."""
+    from . import hip_ops
+    from .derived import derived1
+    return derived1("tap_major", weight, lambda w: hip_ops.conv3x3_n320_weight(w.detach()), hip_ops.conv3x3_k_order())
+
+
+def _conv3x3_packed_transposed(weight):
+    """The transposed weight of the input gradient in the forward kernel's order: kept in svd/derived.py's table while the weight is
+    frozen, built from the live tensor while it trains (it changes every step)."""
+    from . import hip_ops
+    from .derived import derived1
+
+    def build(w):
+        return hip_ops.conv3x3_n320_weight(hip_ops.conv3x3_transposed_weight(w.detach()))
+    if weight.requires_grad:
+        return build(weight)
+    return derived1("tap_major_transposed", weight, build, hip_ops.conv3x3_k_order())
+
+
+class _Conv3x3TokensFn(torch.autograd.Function):
+    """conv3x3_tokens on the implicit-GEMM kernel with a deterministic HIP backward: dx is the same kernel on the transposed weight
+    (W'[ci, co, ky, kx] = W[co, ci, 2 - ky, 2 - kx]), dweight is csrc/conv3x3_wgrad.hip. No bias (the blocks fold it elsewhere). Holds
+    tok and weight only; nothing is cached outside ctx, so torch.utils.checkpoint may re-run the forward."""
+
+    @staticmethod
+    def forward(ctx, tok, weight, H, W):
+        from . import hip_ops
+        ctx.save_for_backward(tok, weight)
+        ctx.hw = (H, W)
+        return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), None, H, W)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        tok, weight = ctx.saved_tensors
+        H, W = ctx.hw
+        n = ctx.needs_input_grad
+        dy = dy if dy.is_contiguous() else dy.contiguous()
+        dx = hip_ops.conv3x3_dgrad(dy, _conv3x3_packed_transposed(weight), H, W) if n[0] else None
+        dw = hip_ops.conv3x3_wgrad(tok, dy, H, W).to(weight.dtype) if n[1] else None
+        return dx, dw, None, None
+
+
+def conv3x3_tokens(tok, weight, H, W):
+    """3x3 / padding 1 / stride 1 convolution of token-major activations tok [N, H W, C_in] with weight [C_out, C_in, 3, 3], no bias
+    -> [N, H W, C_out]. Without autograd: the implicit-GEMM kernel. Under autograd: _Conv3x3TokensFn where the switch is on, the three
+    launches take the shape (conv3x3_tokens_gates) and conv3x3_backward_pays says so; anything else is F.conv2d on the channels-last
+    view (a recorded fallback; strict mode raises)."""
+    N, S, C = tok.shape
+    Co = weight.shape[0]
+    if tok.is_cuda and tok.dtype == weight.dtype and S == H * W and tuple(weight.shape[1:]) == (C, 3, 3):
+        from . import hip_ops
+        if not _needs_autograd(tok, weight):
+            if (hip_ops.conv3x3_n320_supported(C, Co, tok.dtype) and N * S * C * 2 < 2 ** 32
+                    and hip_ops.conv3x3_n320_fills_chip(N, H, W, C, Co, CONV3X3_MIN_BLOCKS)):
+                return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), None, H, W)
+        elif CONV3X3_BACKWARD and conv3x3_tokens_gates(N, H, W, C, Co, tok.dtype) \
+                and conv3x3_backward_pays(N, H, W, C, Co, tok.dtype, weight.requires_grad):
+            return _Conv3x3TokensFn.apply(tok, weight, H, W)
+    _fallback(tok, "conv3x3_tokens", _why(tok, weight))
+    x = tok.view(N, H, W, C).permute(0, 3, 1, 2)                  # [N, C, H, W] with channels-last strides: no copy
+    y = F.conv2d(x, weight, None, 1, 1)
+    return y.permute(0, 2, 3, 1).reshape(N, S, Co)
