@@ -204,7 +204,9 @@ typedef struct mvi_raster_views {
     const uint32_t* tiles_touched;/* [P] */
     const uint8_t* clamped;       /* [P] bit c = colour channel c clamped at 0 (0 while the colour is pending) */
     const void* tile_ids_sorted;  /* [D] high word of the sort key, tile_id_bytes (2 or 4) per entry; the full key of
-                                   * pair i is tile_ids_sorted[i] << 32 | bits(depths[point_list[i]]) */
+                                   * pair i is tile_ids_sorted[i] << 32 | bits(depths[point_list[i]]). No kernel reads it and
+                                   * the forward does not write it (grids up to 256 x 256 tiles): the array is valid after
+                                   * mvi_raster_materialize_tile_ids, which derives it from `ranges` */
     const uint32_t* point_list;   /* [D] Gaussian index per sorted pair */
     const uint32_t* ranges;       /* [tiles,2] */
     const float* final_T;         /* [H,W] */
@@ -217,6 +219,11 @@ typedef struct mvi_raster_views {
 int mvi_raster_get_views(int32_t P, int64_t num_rendered, int32_t image_width, int32_t image_height,
                          const void* geom, const void* binning, const void* image,
                          mvi_raster_views* out);
+/* Fills tile_ids_sorted of a finished forward (same P, num_rendered, size and scratch buffers) from its tile ranges: pair
+ * positions [ranges[t][0], ranges[t][1]) get tile id t; empty tiles write nothing. Enqueued on `stream`; touches nothing else,
+ * so it may run before or after the backward. A no-op when num_rendered is 0. */
+int mvi_raster_materialize_tile_ids(int32_t P, int64_t num_rendered, int32_t image_width, int32_t image_height,
+                                    void* binning, const void* image, void* stream);
 
 /* Stage timing (measurement aid for bench.py): while enabled, every kernel stage the library
  * enqueues is bracketed by hipEvents on the caller's stream. mvi_raster_timing_read waits for the

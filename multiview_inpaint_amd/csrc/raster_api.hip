@@ -576,4 +576,15 @@ int mvi_raster_get_views(int32_t P, int64_t D, int32_t W, int32_t H, const void*
     return MVI_OK;
 }
 
+int mvi_raster_materialize_tile_ids(int32_t P, int64_t D, int32_t W, int32_t H, void* binning, const void* image, void* stream) {
+    if (P < 0 || D < 0 || W < 0 || H < 0) return fail(MVI_EINVAL, "negative size in materialize_tile_ids%s");
+    if (P == 0 || D == 0) return MVI_OK;
+    if (!binning || !image) return fail(MVI_EINVAL, "NULL scratch in materialize_tile_ids%s");
+    const int tiles = ((W + mvi::kTile - 1) / mvi::kTile) * ((H + mvi::kTile - 1) / mvi::kTile);
+    mvi::BinningView b = mvi::carve_binning(binning, D, W, H);
+    mvi::ImageView im = mvi::carve_image(const_cast<void*>(image), W, H);
+    if (mvi::launch_tile_ids_from_ranges(tiles, b, im, D, (hipStream_t)stream)) return hip_fail("materialize_tile_ids", hipGetLastError());
+    return MVI_OK;
+}
+
 }  // extern "C"

@@ -364,6 +364,26 @@ __global__ __launch_bounds__(kBlock) void tile_ranges_kernel(const KeyT* __restr
     if (i == D - 1) ranges[2 * t + 1] = (uint32_t)D;
 }
 
+// The inverse of tile_ranges_kernel, on demand (mvi_raster_materialize_tile_ids): block t writes tile id t to the pair
+// positions [ranges[t].x, ranges[t].y). Binning version 2 stores no tile id per pair: its tile ranges come out of the row scan
+// and no kernel reads the ids, only the parity tests do. Empty tiles, (0, 0), write nothing.
+template <typename KeyT>
+__global__ __launch_bounds__(kBlock) void tile_ids_from_ranges_kernel(const uint2* __restrict__ ranges, int64_t D,
+                                                                      KeyT* __restrict__ tile_keys) {
+    const uint2 r = ranges[blockIdx.x];
+    const int64_t r1 = (int64_t)r.y < D ? (int64_t)r.y : D;
+    for (int64_t i = (int64_t)r.x + threadIdx.x; i < r1; i += kBlock) tile_keys[i] = (KeyT)blockIdx.x;
+}
+int launch_tile_ids_from_ranges(int tiles, BinningView b, ImageView im, int64_t D, hipStream_t st) {
+    if (tiles <= 0 || D <= 0) return 0;
+    void* keys = b.keys[b.passes & 1];
+    const uint2* ranges = reinterpret_cast<const uint2*>(im.ranges);
+    if (b.key_bytes == 2)
+        hipLaunchKernelGGL((tile_ids_from_ranges_kernel<uint16_t>), dim3(tiles), dim3(kBlock), 0, st, ranges, D, (uint16_t*)keys);
+    else hipLaunchKernelGGL((tile_ids_from_ranges_kernel<uint32_t>), dim3(tiles), dim3(kBlock), 0, st, ranges, D, (uint32_t*)keys);
+    return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
+}
+
 // The per-block sums of the preprocess kernel are only needed as their TOTAL (num_rendered; pair emission works from
 // the depth-ordered sums): one block adds them up with no barrier inside the loop and leaves the total where the
 // scan used to put it (offsets[n]).

@@ -4,7 +4,7 @@
 // ties in Gaussian-index order, and the per-tile ranges — bit for bit, but no (tile, Gaussian) pair is written before it is
 // written to its final place:
 //   depth sort   the P Gaussians by depth bits: 4 stable 8-bit passes of TWO launches each (count, scatter). The count kernel
-//                leaves a row of digit counts per 4096-key tile and adds it into a row per 16 tiles; the scatter block sums the
+//                leaves a row of digit counts per 2048-key tile and adds it into a row per 16 tiles; the scatter block sums the
 //                few rows in front of it itself: no scan launch, no spin-wait;
 //   pass 1       a Gaussian's tile rectangle [x0, x0 + w) x [y0, y0 + h) is w COLUMN SEGMENTS (Gaussian, first row, rows).
 //                The Gaussians are walked in depth order and their segments are partitioned by tile column (stable): the
@@ -20,7 +20,8 @@
 // mask of each bin it covers (one 64-bit mask per wave round and bin); the thread that OWNS a bin then walks the set bits of
 // the bin's masks in round order — that is the bin's entries in item order — and writes them into the block's LDS image, which
 // leaves in bin runs.
-// Integer data: the parity tests compare point list, tile ids and ranges bit for bit with the oracle and with version 1.
+// Integer data: the parity tests compare point list, tile ids (derived from the ranges on demand) and ranges bit for bit with
+// the oracle and with version 1.
 #include <cstdlib>
 
 #include "raster_common.h"
@@ -177,18 +178,34 @@ __global__ __launch_bounds__(kDsThreads) void depth_scatter_kernel(
     const int tile0 = blockIdx.x * kDsTile;
     const int base = tile0 + wave * (kDsItems * 64);
     uint32_t key[kDsItems], val[kDsItems];
-#pragma unroll
-    for (int it = 0; it < kDsItems; ++it) {
-        const int idx = base + it * 64 + lane;
-        const bool valid = idx < P;
-        key[it] = valid ? keys_in[idx] : 0u;
-        val[it] = PASS == 0 ? (uint32_t)idx : (valid ? vals_in[idx] : 0u);
-    }
     uint2 rc[PASS == 3 ? kDsItems : 1];
     if (PASS == 3) {
+        // The value -> rectangle chain: every load goes through an index clamped to P - 1 (P > 0: the launcher returns for an
+        // empty scene) and what a lane past the end loaded is dropped by a select afterwards. No branch stands around a load,
+        // so the 16 loads are in flight together and the gathers follow their values without waiting for one another; a lane
+        // past the end gathers rect[0] and never stores it.
 #pragma unroll
-        for (int it = 0; it < kDsItems; ++it)
-            rc[it] = (base + it * 64 + lane) < P ? rect[val[it]] : make_uint2(0u, 0u);
+        for (int it = 0; it < kDsItems; ++it) val[it] = vals_in[min(base + it * 64 + lane, P - 1)];
+#pragma unroll
+        for (int it = 0; it < kDsItems; ++it) key[it] = keys_in[min(base + it * 64 + lane, P - 1)];
+#pragma unroll
+        for (int it = 0; it < kDsItems; ++it) {
+            const bool valid = (base + it * 64 + lane) < P;
+            key[it] = valid ? key[it] : 0u;
+            val[it] = valid ? val[it] : 0u;
+        }
+#pragma unroll
+        for (int it = 0; it < kDsItems; ++it) rc[it] = rect[val[it]];
+    } else {
+        // passes 0 - 2: the compiler already keeps these loads in flight together under their exec masks; the clamped form
+        // was measured and is no faster here
+#pragma unroll
+        for (int it = 0; it < kDsItems; ++it) {
+            const int idx = base + it * 64 + lane;
+            const bool valid = idx < P;
+            key[it] = valid ? keys_in[idx] : 0u;
+            val[it] = PASS == 0 ? (uint32_t)idx : (valid ? vals_in[idx] : 0u);
+        }
     }
     {   // row group rg sums rows rg, rg + 4, .. of the digits 4 dq .. 4 dq + 3
         const int dq = tid & 63, rg = tid >> 6;
@@ -314,8 +331,11 @@ __global__ __launch_bounds__(kExThreads) void column_count_kernel(int P, int gx,
 #pragma unroll
     for (int k = 0; k < kExItems; ++k) {
         const int i = base + k * kExThreads + tid;
-        rc[k] = i < P ? rect_sorted[i] : make_uint2(0u, 0u);
+        rc[k] = rect_sorted[min(i, P - 1)];                 // clamped, selected below: the four loads travel together
     }
+#pragma unroll
+    for (int k = 0; k < kExItems; ++k)
+        if (base + k * kExThreads + tid >= P) rc[k] = make_uint2(0u, 0u);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < kExItems; ++k) {
@@ -418,11 +438,17 @@ __global__ __launch_bounds__(kExThreads) void row_count_kernel(int gx, int gy, c
     if (tid <= 256) s_d[tid] = 0;
     Chunk ck;
     if (!load_chunk(chunk_first, col_start, gx, tid, s_first, s_col, ck)) return;
+    // An empty chunk (an empty tile column owns one) can start at the segment total: the loads are clamped to the last segment
+    // in front of the chunk's end, which exists whenever there is a pair at all, and travel together.
+    const uint32_t last = ck.seg1 ? ck.seg1 - 1u : 0u;
+    uint32_t yhs[kEx2Items];
+#pragma unroll
+    for (int k = 0; k < kEx2Items; ++k) yhs[k] = seg_yh[min(ck.seg0 + (uint32_t)(k * kExThreads + tid), last)];
 #pragma unroll
     for (int k = 0; k < kEx2Items; ++k) {
         const uint32_t i = ck.seg0 + (uint32_t)(k * kExThreads + tid);
         if (i < ck.seg1) {
-            const uint32_t yh = seg_yh[i];
+            const uint32_t yh = yhs[k];
             const uint32_t y0 = yh & 255u, h = (yh >> 8) + 1u;
             atomicAdd(&s_d[y0], 1u);
             atomicSub(&s_d[y0 + h], 1u);
@@ -507,7 +533,7 @@ struct ExpandArgs {
     const uint32_t* tot;                // [bins] totals
     int stride;
     uint32_t* out_idx;                  // pass 1: segment's Gaussian; pass 2: the sorted point list
-    uint16_t* out_aux;                  // pass 1: first row | rows - 1 << 8; pass 2: tile id of the pair
+    uint16_t* out_aux;                  // pass 1: first row | rows - 1 << 8; pass 2: unused
     unsigned long long* stamps;         // diagnostics (mvi_raster_dev_stamps): [blocks][8] shader-clock stamps, else null
 };
 static unsigned long long* g_dev_stamps[2] = {nullptr, nullptr};     // per pass
@@ -569,31 +595,18 @@ __global__ __launch_bounds__(kExThreads) void expand_scatter_kernel(ExpandArgs A
         item0 = ck.seg0; item1 = ck.seg1;
     }
     MVI_STAMP(0);
-    // requested first: they travel while the masks are cleared
-    uint32_t ia[ITEMS], in_[ITEMS];
+    // Requested first: they travel while the masks are cleared. No load sits behind a branch: the index is clamped to an
+    // element that exists (pass 1: P - 1, P > 0; pass 2: the last segment in front of the chunk's end — an empty chunk can
+    // start at the segment total — or segment 0, there is one whenever there is a pair) and what a lane past the end or an
+    // empty rectangle loaded is dropped by the select behind the clear. The values stay in registers until then.
+    const uint32_t last = PASS == 1 ? (uint32_t)A.n_items - 1u : (item1 ? item1 - 1u : 0u);
+    uint2 ld_rc[PASS == 1 ? ITEMS : 1];
+    uint32_t ld_pay[ITEMS], ld_yh[PASS == 2 ? ITEMS : 1];
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
-        const int li = (wave * ITEMS + k) * 64 + lane;             // item of round wave * ITEMS + k, lane
-        const uint32_t i = item0 + (uint32_t)li;
-        ia[k] = 0; in_[k] = 0;
-        uint32_t pay = 0, aux = 0;
-        if (i < item1) {
-            if (PASS == 1) {
-                const uint2 rc = A.rect_sorted[i];
-                const uint32_t w = rc.y & 0xFFFFu, h = rc.y >> 16;
-                if (w * h) {
-                    ia[k] = rc.x & 0xFFFFu; in_[k] = w;
-                    pay = A.order[i];
-                    aux = (rc.x >> 16) | ((h - 1u) << 8);
-                }
-            } else {
-                const uint32_t yh = A.seg_yh_in[i];
-                ia[k] = yh & 255u; in_[k] = (yh >> 8) + 1u;
-                pay = A.seg_idx_in[i];
-            }
-        }
-        s_pay[li] = pay;
-        if (PASS == 1) s_aux[li] = (uint16_t)aux;
+        const uint32_t i = min(item0 + (uint32_t)((wave * ITEMS + k) * 64 + lane), last);
+        if (PASS == 1) { ld_rc[k] = A.rect_sorted[i]; ld_pay[k] = A.order[i]; }
+        else { ld_yh[k] = A.seg_yh_in[i]; ld_pay[k] = A.seg_idx_in[i]; }
     }
     const int nb = A.nbins;
     // worker thread = (bin b, part q of the rounds), BIN-MAJOR: as many parts as 512 threads allow for the bins in use (68 tile
@@ -612,6 +625,27 @@ __global__ __launch_bounds__(kExThreads) void expand_scatter_kernel(ExpandArgs A
         uint4* m4 = reinterpret_cast<uint4*>(&s_mask[0]);
         for (int i = tid; i < (kRounds * kStride + 1) / 2; i += kExThreads) m4[i] = make_uint4(0u, 0u, 0u, 0u);
         if (tid < kRounds) s_rtot[tid] = 0;
+    }
+    // the loads have arrived by now: extents for A, payloads for D
+    uint32_t ia[ITEMS], in_[ITEMS];
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int li = (wave * ITEMS + k) * 64 + lane;             // item of round wave * ITEMS + k, lane
+        const bool inside = item0 + (uint32_t)li < item1;
+        if (PASS == 1) {
+            const uint2 rc = ld_rc[k];
+            const uint32_t w = rc.y & 0xFFFFu, h = rc.y >> 16;
+            const bool on = inside && w * h != 0u;
+            ia[k] = on ? rc.x & 0xFFFFu : 0u;
+            in_[k] = on ? w : 0u;
+            s_pay[li] = on ? ld_pay[k] : 0u;
+            s_aux[li] = on ? (uint16_t)((rc.x >> 16) | ((h - 1u) << 8)) : (uint16_t)0;
+        } else {
+            const uint32_t yh = ld_yh[k];
+            ia[k] = inside ? yh & 255u : 0u;
+            in_[k] = inside ? (yh >> 8) + 1u : 0u;
+            s_pay[li] = inside ? ld_pay[k] : 0u;
+        }
     }
     __syncthreads();
     MVI_STAMP(1);
@@ -699,8 +733,7 @@ __global__ __launch_bounds__(kExThreads) void expand_scatter_kernel(ExpandArgs A
             const uint32_t eb = e >> 16, item = e & 0xFFFFu;
             const uint32_t dst = p + s_delta[eb];
             A.out_idx[dst] = s_pay[item];
-            if (PASS == 1) A.out_aux[dst] = s_aux[item];
-            else A.out_aux[dst] = (uint16_t)(eb * (uint32_t)A.gx + (uint32_t)ck.x);
+            if (PASS == 1) A.out_aux[dst] = s_aux[item];      // pass 2 stores no tile id: nobody reads one (see the launcher)
         }
         MVI_STAMP(6);
         if (g1 >= kRounds) break;
@@ -736,7 +769,9 @@ int launch_binning2_level1(const Frame& f, GeomView g, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 
-// pass 1, pass 2 (count, scan, scatter + tile ranges). Result: b.vals[1] = point list, b.keys[1] = tile ids (uint16).
+// pass 1, pass 2 (count, scan, scatter + tile ranges). Result: b.vals[1] = point list. The tile id of each pair, b.keys[1], is
+// NOT written: the ranges come out of the row scan and no kernel reads the ids (2 bytes per pair, a third of pass 2's traffic);
+// launch_tile_ids_from_ranges (raster_binning.hip) derives them from the ranges for whoever asks (the parity tests).
 int launch_binning2(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, int64_t segments, hipStream_t st) {
     const size_t tiles = (size_t)f.gx * f.gy;
     if (D <= 0 || f.P <= 0) return launch_zero_fill(im.ranges, 8 * tiles, st);
@@ -762,7 +797,7 @@ int launch_binning2(const Frame& f, GeomView g, BinningView b, ImageView im, int
     a2.seg_idx_in = b.vals[0]; a2.seg_yh_in = (const uint16_t*)b.keys[0];
     a2.col_rel = b.col_rel; a2.ranges = im.ranges;
     a2.table = b.block_hist; a2.tot = b.digit_tot; a2.stride = b.nsort;
-    a2.out_idx = b.vals[1]; a2.out_aux = (uint16_t*)b.keys[1];
+    a2.out_idx = b.vals[1];
     a2.stamps = g_dev_stamps[1];
     StageTimer tm(kStSort, st);
     hipLaunchKernelGGL(row_count_kernel, dim3(nchunk), dim3(kExThreads), 0, st, f.gx, f.gy, g.chunk_first, g.col_start,

@@ -121,7 +121,7 @@ struct GeomView {
     uint32_t* chunk_first;    // [257] first pass-2 chunk of tile column x; [gx] = number of chunks
     uint32_t* col_start;      // [257] first column segment of tile column x; [gx] = number of segments
     uint32_t* arrivals;       // [1] blocks of the column scan that have finished (the last one builds the chunk table)
-    uint32_t* ds_table;       // [nds][256] depth-sort digit counts per 4096-key tile (aliases dhist)
+    uint32_t* ds_table;       // [nds][256] depth-sort digit counts per 2048-key tile (kDsTile) (aliases dhist)
     uint32_t* ds_super[2];    // [nsuper][256] sums over kDsSuper tiles, one region per pass parity (inside dhist)
     int nds, nsuper;
     int nblk1;                // blocks of pass 1
@@ -136,8 +136,9 @@ struct ImageView {
 };
 struct BinningView {
     // Version 2 (v2 != 0, grids up to 256 x 256 tiles): keys[0] = (first row | rows - 1 << 8) of each column segment,
-    // vals[0] = its Gaussian (pass 1 output, in column order); keys[1] = tile id of each sorted pair, vals[1] = the sorted
-    // point list (pass 2 output); passes = 1 so that keys / vals[passes & 1] is the result in both versions.
+    // vals[0] = its Gaussian (pass 1 output, in column order); vals[1] = the sorted point list (pass 2 output); keys[1] =
+    // tile id of each sorted pair, NOT written by the binning: no kernel reads it, launch_tile_ids_from_ranges derives it
+    // from the ranges when somebody asks; passes = 1 so that keys / vals[passes & 1] is the result in both versions.
     // block_hist = [256][nsort] rows-per-chunk table, digit_tot = pairs per tile row, col_rel = [gy][gx + 1].
     void* keys[2];        // ping-pong [D] tile ids, key_bytes each (the 64-bit (tile|depth) key is implicit: pairs are
                           // emitted in depth order and stably partitioned by tile)
@@ -561,6 +562,8 @@ int launch_preprocess_backward(const Frame& f, const float* means3D, const float
 int launch_binning(const Frame& f, GeomView g, const int32_t* radii, BinningView b, ImageView im,
                    int64_t D, hipStream_t st);
 int launch_zero_fill(void* p, size_t bytes, hipStream_t st);
+// fills the final tile-id array from the tile ranges (version 2 leaves it unwritten; the same values in version 1)
+int launch_tile_ids_from_ranges(int tiles, BinningView b, ImageView im, int64_t D, hipStream_t st);
 int launch_binning2_totals(GeomView g, int P, unsigned long long* totals_host_devptr, hipStream_t st);   // [0] = D, [1] = segments
 int launch_binning2_level1(const Frame& f, GeomView g, hipStream_t st);
 // segments: the exact number of column segments if known (> 0), else the bound D is used to size the pass-2 grids

@@ -93,15 +93,22 @@ class RasterState:
                                           _ptr(self.image), C.byref(v)), "get_views")
         return v
 
-    def tensor(self, name, shape, dtype):
+    def tensor(self, name, shape, dtype, _derive=True):
         """Copy of one intermediate array as a torch tensor (tests only)."""
         v = self.views()
         addr = getattr(v, name)
+        if _derive and name == "tile_ids_sorted" and self.D > 0 and self.binning is not None and self.image is not None:
+            # the forward leaves the array unwritten (no kernel reads it): derived from the tile ranges here
+            dev = self.binning.device
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().mvi_raster_materialize_tile_ids(
+                    self.P, self.D, self.W, self.H, _ptr(self.binning), _ptr(self.image),
+                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "materialize_tile_ids")
         n = 1
         for s in shape:
             n *= s
         if name == "tile_ids_sorted" and v.tile_id_bytes == 2 and torch.empty(0, dtype=dtype).element_size() == 4:
-            raw = self.tensor(name, tuple(shape) + (2,), torch.uint8).to(torch.int32)       # little-endian uint16 words
+            raw = self.tensor(name, tuple(shape) + (2,), torch.uint8, _derive=False).to(torch.int32)       # little-endian uint16 words
             return (raw[..., 0] | (raw[..., 1] << 8)).to(dtype)
         out = torch.empty(shape, dtype=dtype, device=self.geom.device)
         if n:
