@@ -10,21 +10,13 @@
 
 #include "../../include/mvi_raster.h"
 #include "../../include/mvi_train_ops.h"
+#include "raster_scan.h"
 
 namespace mvi {
 
 int train_fail(int code, const char* msg);
 
 constexpr int kCpBlock = 1024;      // mask entries per block of the count / fill kernels
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t t = __shfl_up(v, o);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(kCpBlock) void compact_count_kernel(const uint8_t* __restrict__ mask, int P,
                                                                  uint32_t* __restrict__ block_sums) {
@@ -45,24 +37,9 @@ __global__ __launch_bounds__(kCpBlock) void compact_count_kernel(const uint8_t* 
 __global__ __launch_bounds__(1024) void compact_scan_kernel(uint32_t* __restrict__ sums, int n) {
     __shared__ uint32_t s_wave[16];
     __shared__ uint32_t s_carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + tid;
-        const uint32_t v = i < n ? sums[i] : 0u;
-        const uint32_t inc = wave_incl_scan(v, lane);
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t wave_off = 0;
-        for (int w = 0; w < wave; ++w) wave_off += s_wave[w];
-        const uint32_t carry = s_carry;
-        if (i < n) sums[i] = carry + wave_off + inc - v;
-        __syncthreads();
-        if (tid == 1023) s_carry = carry + wave_off + inc;
-        __syncthreads();
-    }
-    if (tid == 0) sums[n] = s_carry;
+    const int tid = threadIdx.x;
+    const uint32_t total = row_excl_scan_1024(sums, sums, n, tid, s_wave, &s_carry);
+    if (tid == 0) sums[n] = total;
 }
 
 __global__ __launch_bounds__(kCpBlock) void compact_fill_kernel(const uint8_t* __restrict__ mask, int P,

@@ -5,14 +5,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
+#include <vector>
 
 #include "raster_common.h"
-
-namespace mvi {
-int launch_scan_block_sums(GeomView g, int P, unsigned long long* total_host_devptr, hipStream_t st);
-int launch_zero_fill(void* p, size_t bytes, hipStream_t st);
-int launch_binning_level1(const Frame& f, GeomView g, hipStream_t st);
-}
 
 static thread_local char g_err[512] = "";
 // 0 (default): one-call backward with outputs zeroed on the side + sparse chain rule; 1: the dense chain-rule kernel
@@ -24,7 +20,6 @@ static int g_defer_colors = [] { const char* e = getenv("MVI_RASTER_EAGER_COLORS
 // forward_render that follows on that scratch. Process-wide and locked, so the two halves of a forward may run on different
 // threads; an entry describes the scratch's CONTENTS (the last forward_geom that wrote it replaces it), so it can only be
 // stale if the caller overwrites a scratch while using it. Unknown scratch (table full and evicted): the bound num_rendered.
-#include <mutex>
 namespace {
 struct SegmentHint { const void* geom; int32_t P; int64_t segments; uint64_t stamp; };
 constexpr int kSegmentHints = 64;
@@ -49,7 +44,6 @@ int64_t recall_segments(const void* geom, int32_t P) {
 }  // namespace
 
 // ---- stage timing ------------------------------------------------------------------------------
-#include <vector>
 namespace {
 struct Rec { int stage; hipEvent_t a, b; };
 uint32_t g_timing_mask = 0;        // bit s = stage s is bracketed by events
@@ -278,7 +272,7 @@ static int forward_render_impl(const mvi_raster_settings* s, int32_t P, int64_t 
     if (D > 0 && geom_bytes < g.bytes) return fail(MVI_ENOMEM, "geom scratch too small%s", "");
     hipStream_t st = (hipStream_t)stream;
     const int64_t segments = recall_segments(geom, P);
-    if (f.bin_v2 ? mvi::launch_binning2(f, g, b, im, D, segments, st) : mvi::launch_binning(f, g, radii, b, im, D, st))
+    if (f.bin_v2 ? mvi::launch_binning2(f, g, b, im, D, segments, st) : mvi::launch_binning(f, g, b, im, D, st))
         return hip_fail("binning", hipGetLastError());
     {
         mvi::StageTimer tm(mvi::kStRenderFwd, st);

@@ -11,6 +11,7 @@
 // HBM traffic per pair drops from 6 passes x 32 B to 2 passes x 20 B; the order is bit-identical
 // because both levels are stable. Integer data: the parity tests compare it bit for bit.
 #include "raster_common.h"
+#include "raster_scan.h"
 
 namespace mvi {
 
@@ -33,29 +34,9 @@ __global__ __launch_bounds__(1024) void scan_block_sums_kernel(const uint32_t* _
                                                                uint32_t* __restrict__ offsets, int n) {
     __shared__ uint32_t s_wave[16];
     __shared__ uint32_t s_carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 1024) {
-        int i = base + tid;
-        uint32_t v = i < n ? sums[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            uint32_t t = __shfl_up(inc, o);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t wave_off = 0;
-        for (int w = 0; w < wave; ++w) wave_off += s_wave[w];
-        uint32_t carry = s_carry;
-        if (i < n) offsets[i] = carry + wave_off + inc - v;
-        __syncthreads();
-        if (tid == 1023) s_carry = carry + wave_off + inc;
-        __syncthreads();
-    }
-    if (tid == 0) offsets[n] = s_carry;
+    const int tid = threadIdx.x;
+    const uint32_t total = row_excl_scan_1024(sums, offsets, n, tid, s_wave, &s_carry);
+    if (tid == 0) offsets[n] = total;
 }
 
 // tiles touched per 256 depth-ordered Gaussians
@@ -86,12 +67,12 @@ __global__ __launch_bounds__(kBlock) void emit_pairs_kernel(Frame f, GeomView g,
                                                             KeyT* __restrict__ tile_keys,
                                                             uint32_t* __restrict__ vals) {
     __shared__ uint32_t s_off[kBlock];
-    __shared__ uint32_t s_wave[4];
+    __shared__ uint32_t s_wave[kBlock / 64];
     __shared__ int s_x0[kBlock], s_y0[kBlock], s_w[kBlock];
     __shared__ uint32_t s_gi[kBlock], s_t[kBlock];
     __shared__ KeyT s_outk[kEmitChunk + kEmitChunk / kEmitRun];
     __shared__ uint32_t s_outv[kEmitChunk + kEmitChunk / kEmitRun];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int pos = blockIdx.x * kBlock + tid;
     uint32_t t = 0, gi = 0;
     int x0 = 0, y0 = 0, x1 = 0;
@@ -104,18 +85,8 @@ __global__ __launch_bounds__(kBlock) void emit_pairs_kernel(Frame f, GeomView g,
         t = (uint32_t)(w * h);
     }
     s_x0[tid] = x0; s_y0[tid] = y0; s_w[tid] = x1 - x0; s_gi[tid] = gi; s_t[tid] = t;
-    uint32_t inc = t;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t wave_off = 0;
-    for (int w = 0; w < wave; ++w) wave_off += s_wave[w];
-    s_off[tid] = wave_off + inc - t;
-    const uint32_t total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    uint32_t total;
+    s_off[tid] = block_excl_scan<kBlock / 64>(t, tid, s_wave, &total);
     __syncthreads();
     const uint32_t base = block_offsets[blockIdx.x];
     // Chunks of kEmitChunk slots: every thread produces kEmitRun CONSECUTIVE slots — one binary search for the first,
@@ -201,29 +172,9 @@ __global__ __launch_bounds__(1024) void radix_scan_rows_kernel(uint32_t* __restr
     __shared__ uint32_t s_wave[16];
     __shared__ uint32_t s_carry;
     uint32_t* row = block_hist + (size_t)blockIdx.x * nblk;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nblk; base += 1024) {
-        int i = base + tid;
-        uint32_t v = i < nblk ? row[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            uint32_t t = __shfl_up(inc, o);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t wave_off = 0;
-        for (int w = 0; w < wave; ++w) wave_off += s_wave[w];
-        uint32_t carry = s_carry;
-        if (i < nblk) row[i] = carry + wave_off + inc - v;
-        __syncthreads();
-        if (tid == 1023) s_carry = carry + wave_off + inc;
-        __syncthreads();
-    }
-    if (tid == 0) digit_tot[blockIdx.x] = s_carry;
+    const int tid = threadIdx.x;
+    const uint32_t total = row_excl_scan_1024(row, row, nblk, tid, s_wave, &s_carry);
+    if (tid == 0) digit_tot[blockIdx.x] = total;
 }
 
 // Stable scatter. Wave w of a block owns 512 consecutive pairs, item `it` of lane l is pair
@@ -255,12 +206,7 @@ __global__ __launch_bounds__(64 * kW) void radix_scatter_kernel(
     uint32_t dv = 0, dinc = 0;
     if (digit_thread) {   // exclusive scan of the 256 digit totals -> start of each digit in the output
         dv = digit_tot[tid];
-        dinc = dv;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            uint32_t t = __shfl_up(dinc, o);
-            if (lane >= o) dinc += t;
-        }
+        dinc = wave_incl_scan(dv, lane);
         if (lane == 63) s_w4[wave] = dinc;
     }
     __syncthreads();
@@ -310,12 +256,7 @@ __global__ __launch_bounds__(64 * kW) void radix_scatter_kernel(
             run += c;
         }
         tot = run;
-        inc = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            uint32_t t = __shfl_up(inc, o);
-            if (lane >= o) inc += t;
-        }
+        inc = wave_incl_scan(tot, lane);
         if (lane == 63) s_w4[wave] = inc;                 // last read of s_w4 was two barriers ago
     }
     __syncthreads();
@@ -459,8 +400,6 @@ int launch_binning_level1(const Frame& f, GeomView g, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 
-// Emission in depth order + level 2. After this call the sorted pairs are in b.keys[b.passes & 1]
-// (tile ids), b.vals[b.passes & 1].
 // Emission in depth order + level 2 + tile ranges for one tile-id type. After this call the sorted pairs are in
 // b.keys[b.passes & 1] (tile ids), b.vals[b.passes & 1].
 template <typename KeyT>
@@ -493,8 +432,7 @@ static int binning_typed(const Frame& f, GeomView g, BinningView b, ImageView im
 
 // Tile ids travel as 16-bit words whenever the image has at most 65536 tiles (any image up to 4096 x 4096): a pair is then
 // 6 bytes instead of 8 in every pass of emission, partition and range finding (36 instead of 52 bytes per pair in all).
-int launch_binning(const Frame& f, GeomView g, const int32_t* radii, BinningView b, ImageView im,
-                   int64_t D, hipStream_t st) {
+int launch_binning(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, hipStream_t st) {
     size_t tiles = (size_t)f.gx * f.gy;
     if (launch_zero_fill(im.ranges, 8 * tiles, st)) return MVI_EHIP;
     if (D <= 0 || f.P <= 0) return 0;

@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "raster_common.h"
+#include "raster_scan.h"
 
 namespace mvi {
 
@@ -39,12 +40,7 @@ int set_binning_version(int v) {
 // exclusive scan over the values of the first 256 threads of a block (the others pass 0); every thread must call it
 __device__ __forceinline__ uint32_t block_excl_scan256(uint32_t v, int tid, uint32_t* s_w4, uint32_t* total) {
     const int lane = tid & 63, wave = tid >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
+    const uint32_t inc = wave_incl_scan(v, lane);
     if (wave < 4 && lane == 63) s_w4[wave] = inc;
     __syncthreads();
     uint32_t off = 0;
@@ -233,12 +229,7 @@ __global__ __launch_bounds__(kDsThreads) void depth_scatter_kernel(
     __syncthreads();
     const uint32_t all = s_red[0][0][tid] + s_red[1][0][tid] + s_red[2][0][tid] + s_red[3][0][tid];
     const uint32_t before = s_red[0][1][tid] + s_red[1][1][tid] + s_red[2][1][tid] + s_red[3][1][tid];
-    uint32_t dinc = all;                      // exclusive scan of the 256 digit totals -> start of each digit in the output
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t t = __shfl_up(dinc, o);
-        if (lane >= o) dinc += t;
-    }
+    const uint32_t dinc = wave_incl_scan(all, lane);   // exclusive scan of the 256 digit totals -> start of each digit in the output
     if (lane == 63) s_w4[wave] = dinc;
 
     // ranks inside the wave's 512 keys
@@ -277,12 +268,7 @@ __global__ __launch_bounds__(kDsThreads) void depth_scatter_kernel(
         }
         tot = run;
     }
-    uint32_t inc = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
+    const uint32_t inc = wave_incl_scan(tot, lane);
     __syncthreads();                                      // s_w4 of the first scan has been read
     if (lane == 63) s_w4[wave] = inc;
     __syncthreads();
@@ -374,30 +360,10 @@ __global__ __launch_bounds__(1024) void columns_scan_kernel(uint32_t* __restrict
     __shared__ uint32_t s_carry, s_last;
     __shared__ uint32_t s_w4[4];
     uint32_t* row = table + (size_t)blockIdx.x * stride;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + tid;
-        const uint32_t v = i < n ? row[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            uint32_t t = __shfl_up(inc, o);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t wave_off = 0;
-        for (int w = 0; w < wave; ++w) wave_off += s_wave[w];
-        const uint32_t carry = s_carry;
-        if (i < n) row[i] = carry + wave_off + inc - v;
-        __syncthreads();
-        if (tid == 1023) s_carry = carry + wave_off + inc;
-        __syncthreads();
-    }
+    const int tid = threadIdx.x;
+    const uint32_t total = row_excl_scan_1024(row, row, n, tid, s_wave, &s_carry);
     if (tid == 0) {
-        __hip_atomic_store(tot + blockIdx.x, s_carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(tot + blockIdx.x, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // the total has left before the arrival
         const uint32_t prev = __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_last = prev == (uint32_t)gridDim.x - 1u;
@@ -468,36 +434,16 @@ __global__ __launch_bounds__(1024) void row_scan_kernel(int gx, const uint32_t* 
     __shared__ uint32_t s_first[257];
     __shared__ uint32_t s_wave[16];
     __shared__ uint32_t s_carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid <= gx) s_first[tid] = chunk_first[tid];
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    const int n = (int)s_first[gx];
+    const int tid = threadIdx.x;
+    if (tid <= gx) s_first[tid] = chunk_first[tid];      // read behind the scan: its opening barrier serves
+    const int n = (int)chunk_first[gx];
     uint32_t* row = row_table + (size_t)blockIdx.x * stride;
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + tid;
-        const uint32_t v = i < n ? row[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            uint32_t t = __shfl_up(inc, o);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t wave_off = 0;
-        for (int w = 0; w < wave; ++w) wave_off += s_wave[w];
-        const uint32_t carry = s_carry;
-        if (i < n) row[i] = carry + wave_off + inc - v;
-        __syncthreads();
-        if (tid == 1023) s_carry = carry + wave_off + inc;
-        __syncthreads();
-    }
+    const uint32_t total = row_excl_scan_1024(row, row, n, tid, s_wave, &s_carry);
     // the offsets just written by this block are read back by it, behind the barrier (which drains the stores)
     __syncthreads();
     uint32_t* cr = col_rel + (size_t)blockIdx.x * (gx + 1);
     if (tid < gx) cr[tid] = __hip_atomic_load(row + s_first[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // L2, not L1
-    if (tid == 0) { cr[gx] = s_carry; row_tot[blockIdx.x] = s_carry; }
+    if (tid == 0) { cr[gx] = total; row_tot[blockIdx.x] = total; }
 }
 
 // =================================================================================================== expanding partition
@@ -544,12 +490,7 @@ void set_dev_stamps(int pass, void* buf) { if (pass == 1 || pass == 2) g_dev_sta
 __device__ __forceinline__ void block_excl_scan512x2(uint32_t a, uint32_t b, int tid, uint32_t (*s_w)[8], uint32_t& ea,
                                                      uint32_t& ta, uint32_t& eb) {
     const int lane = tid & 63, wave = tid >> 6;
-    uint32_t ia = a, ib = b;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t x = __shfl_up(ia, o), y = __shfl_up(ib, o);
-        if (lane >= o) { ia += x; ib += y; }
-    }
+    const uint32_t ia = wave_incl_scan(a, lane), ib = wave_incl_scan(b, lane);
     if (lane == 63) { s_w[0][wave] = ia; s_w[1][wave] = ib; }
     __syncthreads();
     uint32_t oa = 0, ob = 0, t = 0;

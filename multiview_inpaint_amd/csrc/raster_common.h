@@ -114,15 +114,16 @@ struct GeomView {
     uint32_t* perm_sums;      // [nblk]   tiles touched per 256 depth-ordered Gaussians
     uint32_t* perm_offsets;   // [nblk+1]
     // binning version 2
-    uint2* rect_sorted;       // [P] the tile rectangles in depth order (written by the column count, read by pass 1)
+    uint2* rect_sorted;       // [P] the tile rectangles in depth order (written by depth_scatter_kernel<3>, read by the column
+                              //     count and pass 1)
     uint32_t* col_table;      // [256][nblk1] column-major: column segments per (column, block of kExChunk Gaussians)
     uint32_t* col_tot;        // [256] column segments per tile column
     uint32_t* seg_sums;       // [npre] column segments (sum of rectangle widths) per preprocess block
     uint32_t* chunk_first;    // [257] first pass-2 chunk of tile column x; [gx] = number of chunks
     uint32_t* col_start;      // [257] first column segment of tile column x; [gx] = number of segments
     uint32_t* arrivals;       // [1] blocks of the column scan that have finished (the last one builds the chunk table)
-    uint32_t* ds_table;       // [nds][256] depth-sort digit counts per 2048-key tile (kDsTile) (aliases dhist)
-    uint32_t* ds_super[2];    // [nsuper][256] sums over kDsSuper tiles, one region per pass parity (inside dhist)
+    uint32_t* ds_table;       // [nds][256] depth-sort digit counts per 2048-key tile (kDsTile)
+    uint32_t* ds_super[2];    // [nsuper][256] sums over kDsSuper tiles, one region per pass parity
     int nds, nsuper;
     int nblk1;                // blocks of pass 1
     int nsortP;
@@ -559,8 +560,9 @@ int launch_preprocess_backward(const Frame& f, const float* means3D, const float
                                float* dL_dmeans2D, float* dL_dopacity, float* dL_dcolors, float* dL_dshs,
                                float* dL_dcov3D, float* dL_dscales, float* dL_drots, hipStream_t st,
                                RawBackwardExtra raw = RawBackwardExtra());
-int launch_binning(const Frame& f, GeomView g, const int32_t* radii, BinningView b, ImageView im,
-                   int64_t D, hipStream_t st);
+int launch_scan_block_sums(GeomView g, int P, unsigned long long* total_host_devptr, hipStream_t st);   // version 1: [0] = D
+int launch_binning_level1(const Frame& f, GeomView g, hipStream_t st);
+int launch_binning(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, hipStream_t st);
 int launch_zero_fill(void* p, size_t bytes, hipStream_t st);
 // fills the final tile-id array from the tile ranges (version 2 leaves it unwritten; the same values in version 1)
 int launch_tile_ids_from_ranges(int tiles, BinningView b, ImageView im, int64_t D, hipStream_t st);

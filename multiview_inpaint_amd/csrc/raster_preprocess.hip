@@ -12,6 +12,7 @@
 // from LDS with an odd row stride (conflict-free). Per-lane strided global accesses of those arrays
 // cost 2.4x the bytes on reads and 3.3x on writes (measured: FETCH_SIZE / WRITE_SIZE).
 #include "raster_common.h"
+#include "raster_scan.h"
 
 namespace mvi {
 
@@ -765,7 +766,7 @@ __global__ __launch_bounds__(kCompactThreads) void compact_touched_kernel(int P,
                                                                          uint32_t* __restrict__ list, uint32_t* __restrict__ count) {
     __shared__ uint32_t s_wave[kCompactThreads / 64];
     __shared__ uint32_t s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int i0 = (blockIdx.x * kCompactThreads + tid) * kCompactPer;
     uint4 w = make_uint4(0u, 0u, 0u, 0u);
     if (i0 < P) w = *reinterpret_cast<const uint4*>(touched + i0);      // bytes past P are padding of the segment, never set
@@ -774,21 +775,12 @@ __global__ __launch_bounds__(kCompactThreads) void compact_touched_kernel(int P,
 #pragma unroll
     for (int q = 0; q < 4; ++q)
         mine += ((ww[q] & 0xFFu) != 0) + ((ww[q] & 0xFF00u) != 0) + ((ww[q] & 0xFF0000u) != 0) + ((ww[q] >> 24) != 0);
-    uint32_t inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t off = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < kCompactThreads / 64; ++k) { const uint32_t c = s_wave[k]; if (k < wave) off += c; total += c; }
+    uint32_t total;
+    const uint32_t off = block_excl_scan<kCompactThreads / 64>(mine, tid, s_wave, &total);
     if (total == 0) return;
     if (tid == 0) s_base = atomicAdd(count, total);
     __syncthreads();
-    uint32_t dst = s_base + off + inc - mine;
+    uint32_t dst = s_base + off;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll

@@ -90,9 +90,11 @@ def _check(R, cam, sc):
     return a, st2
 
 
-@pytest.mark.parametrize("P", [1, 63, 65, 2047, 2048, 2049, 4097])
+@pytest.mark.parametrize("P", [1, 63, 65, 2047, 2048, 2049, 4097, 262_145, 2_097_153])
 def test_scene_ends_inside_a_lane_wave_tile_block(R, P):
-    """96 x 64: the scene ends one short of, at and one past a wave (64), a depth-sort tile and a pass-1 block (2048)."""
+    """96 x 64: the scene ends one short of, at and one past a wave (64), a depth-sort tile and a pass-1 block (2048).
+    P = 262 145 is the first at which version 1's row of block sums (one per 256 Gaussians) has a second 1024-value scan
+    round, of one element; P = 2 097 153 the same for version 2's column table (one entry per 2048 Gaussians)."""
     cam = syn.make_camera(96, 64, 50.0)
     sc = syn.make_scene(P, cam, 0, seed=31, log_scale_mean=np.log(0.05))
     a, _ = _check(R, cam, sc)
