@@ -125,6 +125,29 @@ int mvi_groupnorm_silu_tok2tok_frames(const void* x, void* y, const float* weigh
                                       int32_t frames, int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu,
                                       int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The token-major GroupNorm(+SiLU) under training (csrc/groupnorm_tokens.hip, csrc/groupnorm_bwd.hip): x, y, dy, dx all
+ * [N, spatial, C], statistics per (video of `frames` consecutive samples, group), chan_bias [N, C] per sample.
+ * mvi_groupnorm_tok2tok_forward_stats: mvi_groupnorm_silu_tok2tok_frames — the same launches, `y` bit-identical — that also writes
+ *     stats [N / frames * groups, 2] fp32 = (mean of x + chan_bias, rstd) of every (video, group). Same workspace.
+ * mvi_groupnorm_tok2tok_backward_supported: pure host function, 1 where the backward computes: the forward's geometry (C a multiple of
+ *     groups <= 64 and of the 16-byte vector, N <= 65535), N a whole number of videos, C <= 5461 (the reduce pass's LDS image), grids and
+ *     tables within 32 bits. It cannot see pointers: x, dy and dx must be 16-byte aligned (MVI_EINVAL otherwise; the caller checks).
+ * mvi_groupnorm_tok2tok_backward: the outputs of mvi_groupnorm_backward (dx [N, spatial, C] in the I/O type; dweight, dbias [C],
+ *     dchan_bias [N, C] fp32; every one nullable, dweight / dbias cost one small launch, dchan_bias none, dx one pass over x and dy) from
+ *     token-major x and dy read in place: a reduce pass and an apply pass in which a thread keeps the same 16-byte channel vector in every
+ *     token row, no transpose anywhere. fp32 math, one rounding on the way out; no atomics, two runs give the same bits.
+ *     workspace: mvi_groupnorm_tok2tok_backward_workspace_bytes(...) bytes (0 = unsupported), 4-byte aligned. */
+int mvi_groupnorm_tok2tok_forward_stats(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
+                                        float* stats, int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups, float eps,
+                                        int32_t fuse_silu, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
+int mvi_groupnorm_tok2tok_backward_supported(int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups, int32_t dtype);
+size_t mvi_groupnorm_tok2tok_backward_workspace_bytes(int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups,
+                                                      int32_t dtype);
+int mvi_groupnorm_tok2tok_backward(const void* x, const void* dy, const float* stats, const float* weight, const float* bias,
+                                   const float* chan_bias, void* dx, float* dweight, float* dbias, float* dchan_bias, int64_t N,
+                                   int32_t frames, int32_t C, int64_t spatial, int32_t groups, int32_t fuse_silu, int32_t dtype,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* out = softmax(q k^T * scale) v per (batch, head). Token-major layout, as the Linear projections
  * produce it: q/out [B, Sq, H, D], k/v [B, Sk, H, D], contiguous. No mask (none is used on the
  * denoise path). dtype selects the I/O type; fp32 I/O computes in fp32 (validation mode, 1e-4

@@ -18,10 +18,16 @@
 // dy is read in place in one of three layouts: planes [rows, C, S]; stack3 [rows, 3 C, S] (the gradient of frame t is block 1 of
 // row t + block 0 of row t + 1 + block 2 of row t - 1: the mirror of the forward's three writes); token-major [rows, S, C], which
 // crosses LDS once (XOR-swizzled 16-byte chunks, so that the transposed reads of a wave spread over the banks).
+//
+// Token-major x, dy AND dx [rows, S, C] (mvi_groupnorm_tok2tok_backward: the norm between the two convolutions of a ResBlock,
+// mvi_groupnorm_silu_tok2tok[_frames]) have kernels of their own for the two passes over the tensor, gn_bwd_tok_reduce_kernel and
+// gn_bwd_tok_apply_kernel: channels are contiguous in all three tensors, so nothing is transposed; finalize and params are the same
+// launches on the same `part` layout.
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
+#include "groupnorm_tok.h"
 #include "unet_host.h"
 #include "unet_io.h"
 
@@ -322,7 +328,213 @@ static int gb_run(const void* x, const void* dy, const GbGeom& q, const GbPlan& 
     return hipGetLastError() == hipSuccess ? MVI_OK : MVI_EHIP;
 }
 
+// ---- token-major x, dy, dx [N, S, C] ------------------------------------------------------------------------------------------------
+// The thread layout of groupnorm_tokens.hip: a block is vpr x rp threads (vpr = C / vec vectors per token row, rp rows per pass) on a
+// tile of kGtPasses rp tokens, and a thread owns the SAME vec channels in every row — its per-channel constants (rstd, (chan_bias -
+// mean) rstd, weight, bias, coef: looked up per CHANNEL, a vector may span groups) live in registers. kGkRows rows of x and of dy are
+// in flight per thread and step (the step loop stays rolled: unrolled, the compiler hoists every step's loads and spills); every
+// load is issued at a clamped row, rows past the end are masked where they are used.
+constexpr int kGkRows = 4;
+
+template <int V> struct GkChan { float a[V], b[V], w[V], bi[V]; };
+
+template <int V> __device__ __forceinline__ void gk_channel_constants(const GbGeom& q, int64_t n, int c0, GkChan<V>& k, const float* coef,
+                                                                      float* k2, float* k3) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const int c = c0 + i;
+        const int64_t vg = (n / q.T) * q.G + c / q.Cg;
+        const float mean = q.stats[2 * vg], rstd = q.stats[2 * vg + 1];
+        const float add = q.chan_bias ? q.chan_bias[n * q.C + c] : 0.f;
+        k.a[i] = rstd;
+        k.b[i] = (add - mean) * rstd;
+        k.w[i] = q.weight[c];
+        k.bi[i] = q.bias[c];
+        if (coef) { k2[i] = coef[2 * vg]; k3[i] = coef[2 * vg + 1]; }
+    }
+}
+
+// reduce: per tile and channel sum g, sum g xh, sum xh over the tile's tokens -> part [row, s_tile, C, 3]. A thread sums its rows in
+// pass order; the rp threads that share a channel are added through LDS in row order.
+template <typename T>
+__global__ __launch_bounds__(1024) void gn_bwd_tok_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, GbGeom q,
+                                                                 float* __restrict__ part, int vpr, int rp) {
+    constexpr int V = Io<T>::kVec;
+    // 8 channels' constants and sums are 56 registers: two rows of x and dy per step keep the kernel inside the 128 a 1024-thread
+    // block may use (four rows: 68 bytes of scratch)
+    constexpr int kGkRows = V == 8 ? 2 : 4;
+    extern __shared__ float s_red[];                       // [3][rp][C]
+    const int tid = threadIdx.x, v = tid % vpr, r0 = tid / vpr;
+    const int64_t n = blockIdx.y, S = q.S;
+    const int st = blockIdx.x, C = q.C;
+    const int64_t row0 = (int64_t)st * (kGtPasses * rp);
+    GkChan<V> k;
+    gk_channel_constants<V>(q, n, v * V, k, nullptr, nullptr, nullptr);
+    const T* xb = x + (n * S) * C + (int64_t)v * V;
+    const T* db = dy + (n * S) * C + (int64_t)v * V;
+    float p0[V], p1[V], p2[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) p0[i] = p1[i] = p2[i] = 0.f;
+#pragma unroll 1
+    for (int h = 0; h < kGtPasses / kGkRows; ++h) {
+        uint4 rx[kGkRows], rd[kGkRows];
+#pragma unroll
+        for (int p = 0; p < kGkRows; ++p) {
+            const int64_t row = row0 + (h * kGkRows + p) * rp + r0;
+            const int64_t rc = row < S ? row : S - 1;
+            rx[p] = *reinterpret_cast<const uint4*>(xb + rc * C);
+            rd[p] = *reinterpret_cast<const uint4*>(db + rc * C);
+        }
+#pragma unroll
+        for (int p = 0; p < kGkRows; ++p) {
+            const int64_t row = row0 + (h * kGkRows + p) * rp + r0;
+            float xv[V], gv[V];
+            Io<T>::load(reinterpret_cast<const T*>(&rx[p]), xv);
+            Io<T>::load(reinterpret_cast<const T*>(&rd[p]), gv);
+            const float m = row < S ? 1.f : 0.f;
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                const float xh = xv[i] * k.a[i] + k.b[i];
+                const float gg = m * (q.silu ? gv[i] * silu_grad(k.w[i] * xh + k.bi[i]) : gv[i]);
+                p0[i] += gg; p1[i] += gg * xh; p2[i] += m * xh;
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        s_red[((size_t)0 * rp + r0) * C + v * V + i] = p0[i];
+        s_red[((size_t)1 * rp + r0) * C + v * V + i] = p1[i];
+        s_red[((size_t)2 * rp + r0) * C + v * V + i] = p2[i];
+    }
+    __syncthreads();
+    for (int c = tid; c < C; c += blockDim.x) {
+        float* o = part + ((n * q.s_tiles + st) * C + c) * 3;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            float t = 0.f;
+            for (int r = 0; r < rp; ++r) t += s_red[((size_t)j * rp + r) * C + c];
+            o[j] = t;
+        }
+    }
+}
+
+// apply: dx = rstd w_c g - coef_A - xh coef_B, a straight 16-byte load / store pass
+template <typename T>
+__global__ __launch_bounds__(1024) void gn_bwd_tok_apply_kernel(const T* __restrict__ x, const T* __restrict__ dy, GbGeom q,
+                                                                const float* __restrict__ coef, T* __restrict__ dx, int vpr, int rp) {
+    constexpr int V = Io<T>::kVec;
+    const int tid = threadIdx.x, v = tid % vpr, r0 = tid / vpr;
+    const int64_t n = blockIdx.y, S = q.S;
+    const int C = q.C;
+    const int64_t row0 = (int64_t)blockIdx.x * (kGtPasses * rp);
+    GkChan<V> k;
+    float k2[V], k3[V];
+    gk_channel_constants<V>(q, n, v * V, k, coef, k2, k3);
+    const int64_t off = (n * S) * C + (int64_t)v * V;
+#pragma unroll 1
+    for (int h = 0; h < kGtPasses / kGkRows; ++h) {
+        uint4 rx[kGkRows], rd[kGkRows];
+#pragma unroll
+        for (int p = 0; p < kGkRows; ++p) {
+            const int64_t row = row0 + (h * kGkRows + p) * rp + r0;
+            const int64_t rc = row < S ? row : S - 1;
+            rx[p] = *reinterpret_cast<const uint4*>(x + off + rc * C);
+            rd[p] = *reinterpret_cast<const uint4*>(dy + off + rc * C);
+        }
+#pragma unroll
+        for (int p = 0; p < kGkRows; ++p) {
+            const int64_t row = row0 + (h * kGkRows + p) * rp + r0;
+            float xv[V], gv[V], ov[V];
+            Io<T>::load(reinterpret_cast<const T*>(&rx[p]), xv);
+            Io<T>::load(reinterpret_cast<const T*>(&rd[p]), gv);
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                const float xh = xv[i] * k.a[i] + k.b[i];
+                const float gg = q.silu ? gv[i] * silu_grad(k.w[i] * xh + k.bi[i]) : gv[i];
+                ov[i] = (k.a[i] * k.w[i]) * gg - k2[i] - xh * k3[i];
+            }
+            if (row < S) Io<T>::store(dx + off + row * C, ov);
+        }
+    }
+}
+
+struct GkPlan {
+    int vpr, rp, s_tiles;
+    size_t lds, part_floats, sums_floats, coef_floats;
+};
+
+// the forward's geometry (gt_geometry_ok: C a multiple of the groups (<= 64) and of the vector, at most 65535 samples), whole videos,
+// the reduce pass's LDS image within 64 KB, and grids / tables within 32 bits
+static bool gk_plan(int64_t N, int T, int C, int64_t S, int G, int dtype, GkPlan* p) {
+    if (dtype < 0 || dtype > 2 || T < 1 || !gt_geometry_ok(N, C, S, G, dtype) || N % T != 0) return false;
+    const int V = gb_elems_per_vec(dtype);
+    p->vpr = C / V; p->rp = gt_rows_per_pass(p->vpr);
+    const int64_t tile = (int64_t)kGtPasses * p->rp, st = (S + tile - 1) / tile;
+    p->lds = (size_t)3 * p->rp * C * sizeof(float);
+    if (p->lds > 64 * 1024 || st > 0x7FFFFFll || N * st > 0x7FFFFFFFll || N / T * G > 0x7FFFFFFFll) return false;
+    p->s_tiles = (int)st;
+    p->part_floats = (size_t)(N * st) * C * 3;
+    p->sums_floats = (size_t)N * C * 3;
+    p->coef_floats = (size_t)(N / T * G) * 2;
+    return true;
+}
+
+template <typename T>
+static int gk_run(const void* x, const void* dy, const GbGeom& q, const GkPlan& p, int64_t N, float* ws, float* dweight, float* dbias,
+                  float* dchan_bias, void* dx, hipStream_t st) {
+    float* part = ws;
+    float* sums = part + p.part_floats;
+    float* coef = sums + p.sums_floats;
+    const dim3 grid((unsigned)p.s_tiles, (unsigned)N), block((unsigned)(p.vpr * p.rp));
+    hipLaunchKernelGGL((gn_bwd_tok_reduce_kernel<T>), grid, block, p.lds, st, (const T*)x, (const T*)dy, q, part, p.vpr, p.rp);
+    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3((unsigned)(N / q.T * q.G)), dim3(kGbBlock), 0, st, part, q, sums, coef, dchan_bias);
+    if (dweight || dbias)
+        hipLaunchKernelGGL(gn_bwd_params_kernel, dim3((unsigned)((q.C + kGbBlock - 1) / kGbBlock)), dim3(kGbBlock), 0, st, sums, N, q.C,
+                           dweight, dbias);
+    if (dx) hipLaunchKernelGGL((gn_bwd_tok_apply_kernel<T>), grid, block, 0, st, (const T*)x, (const T*)dy, q, coef, (T*)dx, p.vpr, p.rp);
+    return hipGetLastError() == hipSuccess ? MVI_OK : MVI_EHIP;
+}
+
 }  // namespace mvi
+
+extern "C" int mvi_groupnorm_tok2tok_backward_supported(int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups,
+                                                        int32_t dtype) {
+    mvi::GkPlan p;
+    return mvi::gk_plan(N, frames, C, spatial, groups, dtype, &p) ? 1 : 0;
+}
+
+extern "C" size_t mvi_groupnorm_tok2tok_backward_workspace_bytes(int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups,
+                                                                 int32_t dtype) {
+    mvi::GkPlan p;
+    if (!mvi::gk_plan(N, frames, C, spatial, groups, dtype, &p)) return 0;
+    return (p.part_floats + p.sums_floats + p.coef_floats) * sizeof(float);
+}
+
+extern "C" int mvi_groupnorm_tok2tok_backward(const void* x, const void* dy, const float* stats, const float* weight, const float* bias,
+                                              const float* chan_bias, void* dx, float* dweight, float* dbias, float* dchan_bias, int64_t N,
+                                              int32_t frames, int32_t C, int64_t spatial, int32_t groups, int32_t fuse_silu, int32_t dtype,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+    if (N == 0 || spatial == 0) return MVI_OK;
+    mvi::GkPlan p;
+    if (!mvi::gk_plan(N, frames, C, spatial, groups, dtype, &p))
+        return mvi::unet_fail(MVI_EINVAL, "groupnorm_tok2tok backward: unsupported shape or dtype");
+    if (!x || !dy || !stats || !weight || !bias || !workspace) return mvi::unet_fail(MVI_EINVAL, "groupnorm_tok2tok backward: NULL pointer");
+    if (dchan_bias && !chan_bias) return mvi::unet_fail(MVI_EINVAL, "groupnorm_tok2tok backward: dchan_bias without chan_bias");
+    if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) % 16)
+        return mvi::unet_fail(MVI_EINVAL, "groupnorm_tok2tok backward: x / dy / dx must be 16-byte aligned");
+    if (workspace_bytes < (p.part_floats + p.sums_floats + p.coef_floats) * sizeof(float) || (uintptr_t)workspace % 4 != 0)
+        return mvi::unet_fail(MVI_ENOMEM, "groupnorm_tok2tok backward: workspace too small or misaligned");
+    mvi::GbGeom q;
+    q.S = spatial; q.C = C; q.Cg = C / groups; q.G = groups; q.T = frames;
+    q.s_tiles = p.s_tiles; q.c_tiles = 0; q.silu = fuse_silu ? 1 : 0;
+    q.weight = weight; q.bias = bias; q.chan_bias = chan_bias; q.stats = stats;
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    return mvi::dispatch_dtype(dtype, "groupnorm_tok2tok backward: unknown dtype", [&](auto t) {
+        return mvi::gk_run<typename decltype(t)::type>(x, dy, q, p, N, ws, dweight, dbias, dchan_bias, dx, st)
+                   ? mvi::unet_fail(MVI_EHIP, "groupnorm_tok2tok backward: kernel launch failed") : MVI_OK;
+    });
+}
 
 extern "C" int mvi_groupnorm_backward_supported(int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, int32_t dy_layout,
                                                 int32_t dtype) {

@@ -16,16 +16,13 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
+#include "groupnorm_tok.h"
 #include "unet_host.h"
 #include "unet_io.h"
 
 namespace mvi {
 
-constexpr int kGtPasses = 8;          // token rows per thread and chunk
-constexpr int kGtMaxGroups = 64;
 constexpr int kGtMergeThreads = 1024;
-
-__host__ __device__ inline int gt_rows_per_pass(int vpr) { int rp = 512 / vpr; return rp < 1 ? 1 : (rp > 8 ? 8 : rp); }
 
 // A block walks `sets` consecutive chunks of 8 rp tokens (a thread owns the SAME vec channels in every row it reads) and keeps, per
 // channel, the sums S1 = sum(x - x0) and S2 = sum((x - x0)^2) SHIFTED by the block's first token x0 of that channel — the shifted-data
@@ -230,9 +227,11 @@ __global__ __launch_bounds__(1024) void gt_fused_kernel(const T* __restrict__ a,
 // frames > 1: the temporal GroupNorm of VideoResBlock.time_stack (statistics over the `frames` consecutive samples of a video,
 // video_model.py:71-75): a block merges the chunks of all its frames — they are consecutive in `part` — and writes every frame's
 // scale / shift (the frames differ in chan_bias only).
+// stats (nullable; NULL on the inference path): [videos * G, 2] fp32 = (mean of x + chan_bias, rstd) per (video, group), the table
+// the backward reads (mvi_groupnorm_tok2tok_forward_stats); written by the block of the video's first frame.
 __global__ __launch_bounds__(kGtMergeThreads) void gt_merge_kernel(const float* __restrict__ part, const float* __restrict__ weight, const float* __restrict__ bias,
                                                        const float* __restrict__ chan_bias, float* __restrict__ scale_shift, int C, int G,
-                                                       int chunks_per_frame, float eps, int frames) {
+                                                       int chunks_per_frame, float eps, int frames, float* __restrict__ stats) {
     __shared__ float s_mean[kGtMaxGroups], s_rstd[kGtMaxGroups];
     __shared__ float s_p[kGtMergeThreads][3];
     // one block per FRAME: it merges the chunks of its whole video (redundantly with its frames - 1 siblings: a few hundred partials
@@ -281,6 +280,10 @@ __global__ __launch_bounds__(kGtMergeThreads) void gt_merge_kernel(const float* 
         }
         s_mean[tid] = mean;
         s_rstd[tid] = rsqrtf(m2 / cnt + eps);
+        if (stats && frame == n) {
+            stats[(n / frames * G + tid) * 2] = mean;
+            stats[(n / frames * G + tid) * 2 + 1] = s_rstd[tid];
+        }
     }
     __syncthreads();
     const int Cg = C / G;
@@ -400,7 +403,7 @@ static int gt_launch_split(const float* x, void* y2, const float* w, const float
         ss = ws + (size_t)N * chunks * G * 3;
         const size_t lds = ((size_t)2 * rp * C + C) * sizeof(float);
         hipLaunchKernelGGL((gt_stats_kernel<float>), dim3((unsigned)schunks, (unsigned)N), block, lds, st, x, cb, part, C, S, G, vpr, rp, schunks, sets);
-        hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, b, cb, ss, C, G, schunks, eps, frames);
+        hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, b, cb, ss, C, G, schunks, eps, frames, (float*)nullptr);
     }
     if (mode == 0) hipLaunchKernelGGL(gt_apply_split_kernel<0>, grid, block, 0, st, x, (uint16_t*)y2, ss, C, S, vpr, rp, silu);
     else if (mode == 1) hipLaunchKernelGGL(gt_apply_split_kernel<1>, grid, block, 0, st, x, (uint16_t*)y2, ss, C, S, vpr, rp, silu);
@@ -410,7 +413,7 @@ static int gt_launch_split(const float* x, void* y2, const float* w, const float
 
 template <typename T>
 static int gt_launch(const void* x, void* y, const float* w, const float* b, const float* cb, int64_t N, int C, int64_t S, int G, float eps,
-                     int silu, float* ws, hipStream_t st, int frames = 1) {
+                     int silu, float* ws, hipStream_t st, int frames = 1, float* stats = nullptr) {
     constexpr int V = Io<T>::kVec;
     const int vpr = C / V, rp = gt_rows_per_pass(vpr);
     const int chunks = (int)((S + kGtPasses * rp - 1) / (kGtPasses * rp));
@@ -423,7 +426,7 @@ static int gt_launch(const void* x, void* y, const float* w, const float* b, con
     const dim3 grid((unsigned)chunks, (unsigned)N), block((unsigned)(vpr * rp));
     const size_t lds = ((size_t)2 * rp * C + C) * sizeof(float);
     hipLaunchKernelGGL((gt_stats_kernel<T>), dim3((unsigned)schunks, (unsigned)N), block, lds, st, (const T*)x, cb, part, C, S, G, vpr, rp, schunks, sets);
-    hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, b, cb, ss, C, G, schunks, eps, frames);
+    hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, b, cb, ss, C, G, schunks, eps, frames, stats);
     hipLaunchKernelGGL((gt_apply_kernel<T>), grid, block, 0, st, (const T*)x, (T*)y, ss, C, S, vpr, rp, silu);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
@@ -438,21 +441,14 @@ static int gt_launch_pre(const void* x, void* y, const float* w, const float* b,
     const int chunks = (int)((S + kGtPasses * rp - 1) / (kGtPasses * rp));
     float* ss = ws;                                               // [N, C, 2]
     const dim3 grid((unsigned)chunks, (unsigned)N), block((unsigned)(vpr * rp));
-    hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, b, cb, ss, C, G, chunks_per_sample, eps, frames);
+    hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, b, cb, ss, C, G, chunks_per_sample, eps, frames, (float*)nullptr);
     hipLaunchKernelGGL((gt_apply_kernel<T>), grid, block, 0, st, (const T*)x, (T*)y, ss, C, S, vpr, rp, silu);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 
 }  // namespace mvi
 
-static int gt_geometry_ok(int64_t N, int32_t C, int64_t S, int32_t G, int32_t dtype) {
-    const int V = dtype == MVI_DT_F32 ? 4 : 8;
-    if (N <= 0 || C <= 0 || S <= 0 || G <= 0 || G > mvi::kGtMaxGroups || C % G || C % V) return 0;
-    const int vpr = C / V;
-    if (vpr > 1024 || N > 65535) return 0;
-    const int rp = mvi::gt_rows_per_pass(vpr);
-    return ((size_t)2 * rp * C + C) * sizeof(float) <= 64 * 1024;
-}
+using mvi::gt_geometry_ok;
 
 extern "C" size_t mvi_groupnorm_tok2tok_workspace_bytes(int64_t N, int32_t C, int64_t spatial, int32_t groups, int32_t dtype) {
     if (!gt_geometry_ok(N, C, spatial, groups, dtype)) return 0;
@@ -464,7 +460,7 @@ extern "C" size_t mvi_groupnorm_tok2tok_workspace_bytes(int64_t N, int32_t C, in
 
 static int tok2tok_impl(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias, int64_t N, int32_t C,
                         int64_t spatial, int32_t groups, float eps, int32_t fuse_silu, int32_t frames, int32_t dtype, void* workspace,
-                        size_t workspace_bytes, void* stream) {
+                        size_t workspace_bytes, void* stream, float* stats = nullptr) {
     if (N == 0 || spatial == 0) return MVI_OK;
     if (!gt_geometry_ok(N, C, spatial, groups, dtype))
         return mvi::unet_fail(MVI_EINVAL, "groupnorm_tok2tok: C must be a multiple of groups (<= 64) and of the 16-byte vector width");
@@ -475,7 +471,7 @@ static int tok2tok_impl(const void* x, void* y, const float* weight, const float
         return mvi::unet_fail(MVI_ENOMEM, "groupnorm_tok2tok: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     return mvi::dispatch_dtype(dtype, "groupnorm_tok2tok: unknown dtype", [&](auto t) {
-        return mvi::gt_launch<typename decltype(t)::type>(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, (float*)workspace, st, frames)
+        return mvi::gt_launch<typename decltype(t)::type>(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, (float*)workspace, st, frames, stats)
                    ? mvi::unet_fail(MVI_EHIP, "groupnorm_tok2tok: kernel launch failed") : MVI_OK;
     });
 }
@@ -508,6 +504,17 @@ extern "C" int mvi_groupnorm_silu_tok2tok_frames(const void* x, void* y, const f
                                                  int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups, float eps,
                                                  int32_t fuse_silu, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
     return tok2tok_impl(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, frames, dtype, workspace, workspace_bytes, stream);
+}
+
+// The forward for training: mvi_groupnorm_silu_tok2tok_frames (the same launches, y bit-identical) that also leaves
+// stats [N / frames * groups, 2] fp32 = (mean, rstd) for mvi_groupnorm_tok2tok_backward (csrc/groupnorm_bwd.hip).
+extern "C" int mvi_groupnorm_tok2tok_forward_stats(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
+                                                   float* stats, int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups,
+                                                   float eps, int32_t fuse_silu, int32_t dtype, void* workspace, size_t workspace_bytes,
+                                                   void* stream) {
+    if (!stats && N != 0 && spatial != 0) return mvi::unet_fail(MVI_EINVAL, "groupnorm_tok2tok_forward_stats: NULL stats");
+    return tok2tok_impl(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, frames, dtype, workspace, workspace_bytes, stream,
+                        stats);
 }
 
 // GroupNorm(+SiLU) of an fp32 token-major tensor x [N, S, C] written as split bf16 y2 [N, S, 2 C] = (hi | lo) (see gt_apply_split_kernel);

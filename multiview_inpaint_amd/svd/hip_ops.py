@@ -13,7 +13,8 @@ _ws = {}
 
 # Optional per-op timing for bench.py: when PROFILE is a list, every op appends
 # (kind, start_event, end_event, work) with events recorded on the stream the kernel runs on. GroupNorm under autograd shows as
-# "groupnorm_stats_fwd" and "groupnorm_bwd" ("groupnorm_bwd_params" when the call also launched the dweight / dbias kernel),
+# "groupnorm_stats_fwd" and "groupnorm_bwd" ("groupnorm_bwd_params" when the call also launched the dweight / dbias kernel), the
+# token-major norm as "groupnorm_tok2tok_stats_fwd" and "groupnorm_tok2tok_bwd" / "groupnorm_tok2tok_bwd_params",
 # GEGLU under autograd as "ff_geglu" + "ff_geglu_bwd" (the kernel alone) + "ff_geglu_dparams" (for trainable parameters: the library's
 # dweight GEMM and the dbias sum on the kernel's dh), or "geglu" + "geglu_bwd".
 PROFILE = None
@@ -1179,6 +1180,77 @@ def group_norm_silu_tok2tok(t, num_groups, weight, bias, eps, silu, chan_bias=No
                                                    int(frames), Cc, S, num_groups, float(eps), int(bool(silu)), _DT[t.dtype], ws.data_ptr(),
                                                    ws.numel(), _stream(tc.device)), "group_norm_tok2tok")
     return y
+
+
+def group_norm_tok2tok_backward_supported(N, C_, S, num_groups, frames, dtype):
+    """Whether group_norm_tok2tok_forward_stats / group_norm_tok2tok_backward compute t [N, S, C] with statistics over videos of
+    `frames` samples (mvi_groupnorm_tok2tok_backward_supported, a host-only function; the 16-byte alignment is checked at the call)."""
+    if dtype not in _DT or frames <= 0 or num_groups <= 0:
+        return False
+    return bool(_lib.lib().mvi_groupnorm_tok2tok_backward_supported(int(N), int(frames), int(C_), int(S), int(num_groups), _DT[dtype]))
+
+
+def _tok2tok_args(what, t, chan_bias):
+    if t.dtype not in _DT:
+        raise TypeError(f"{what}: unsupported dtype {t.dtype}")
+    if t.dim() != 3:
+        raise ValueError(f"{what}: token-major [N, S, C] expected, got {tuple(t.shape)}")
+    tc = _contig(t)
+    N, S, Cc = tc.shape
+    return tc, N, S, Cc, _chan_bias(what, chan_bias, N, Cc)
+
+
+def group_norm_tok2tok_forward_stats(t, num_groups, weight, bias, eps, silu, chan_bias=None, frames=1):
+    """The forward of group_norm_silu_tok2tok (same kernels, y bit-identical) that also returns the fp32 (mean, rstd) of every
+    (video, group) [N / frames * groups, 2] for group_norm_tok2tok_backward."""
+    L = _lib.lib()
+    tc, N, S, Cc, cb = _tok2tok_args("group_norm_tok2tok_forward_stats", t, chan_bias)
+    nbytes = L.mvi_groupnorm_tok2tok_workspace_bytes(N, Cc, S, num_groups, _DT[t.dtype])
+    if nbytes == 0 or frames < 1 or N % frames:
+        raise ValueError(f"group_norm_tok2tok_forward_stats: unsupported shape {tuple(t.shape)} / {num_groups} groups / {frames} frames")
+    y = torch.empty_like(tc)
+    stats = torch.empty((N // frames * num_groups, 2), dtype=torch.float32, device=t.device)
+    ws = _workspace(tc.device, nbytes)
+    with torch.cuda.device(tc.device), _Timed("groupnorm_tok2tok_stats_fwd", 3.0 * tc.numel() * tc.element_size(), tc.device):
+        _check(L.mvi_groupnorm_tok2tok_forward_stats(tc.data_ptr(), y.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(), _ptr(cb),
+                                                     stats.data_ptr(), N, int(frames), Cc, S, num_groups, float(eps), int(bool(silu)),
+                                                     _DT[t.dtype], ws.data_ptr(), ws.numel(), _stream(tc.device)),
+               "group_norm_tok2tok_forward_stats")
+    return y, stats
+
+
+def group_norm_tok2tok_backward(dy, t, stats, num_groups, weight, bias, silu, chan_bias=None, frames=1, need_dx=True, need_dparams=False,
+                                need_dchan_bias=False):
+    """(dx, dweight, dbias, dchan_bias) of the token-major GroupNorm(+SiLU) whose forward returned `stats` (csrc/groupnorm_bwd.hip,
+    gn_bwd_tok_*): dx in t's dtype and shape, the others fp32; outputs not asked for are None and cost nothing (need_dparams adds one
+    small launch; the PROFILE kind is then "groupnorm_tok2tok_bwd_params" instead of "groupnorm_tok2tok_bwd"). dy: contiguous, t's dtype
+    and shape. Deterministic."""
+    L = _lib.lib()
+    tc, N, S, Cc, cb = _tok2tok_args("group_norm_tok2tok_backward", t, chan_bias)
+    if dy.dtype != t.dtype or dy.shape != tc.shape or not dy.is_contiguous():
+        raise ValueError(f"group_norm_tok2tok_backward: dy must be contiguous {t.dtype} {tuple(tc.shape)}, got {dy.dtype} {tuple(dy.shape)}")
+    if frames < 1 or N % frames:
+        raise ValueError(f"group_norm_tok2tok_backward: {N} samples are not whole videos of {frames} frames")
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (N // frames * num_groups, 2) or not stats.is_contiguous():
+        raise ValueError("group_norm_tok2tok_backward: stats must be the fp32 [videos * groups, 2] table of group_norm_tok2tok_forward_stats")
+    if need_dchan_bias and cb is None:
+        raise ValueError("group_norm_tok2tok_backward: dchan_bias asked for without chan_bias")
+    nbytes = int(L.mvi_groupnorm_tok2tok_backward_workspace_bytes(N, int(frames), Cc, S, num_groups, _DT[t.dtype]))
+    if nbytes == 0:
+        raise ValueError(f"group_norm_tok2tok_backward: unsupported shape {tuple(t.shape)} / {num_groups} groups")
+    f32 = dict(dtype=torch.float32, device=t.device)
+    dx = torch.empty_like(tc) if need_dx else None
+    dw = torch.empty(Cc, **f32) if need_dparams else None
+    db = torch.empty(Cc, **f32) if need_dparams else None
+    dcb = torch.empty((N, Cc), **f32) if need_dchan_bias else None
+    ws = _workspace(t.device, nbytes)
+    work = (2.0 + 3.0 * bool(need_dx)) * tc.numel() * tc.element_size()           # reduce pass (+ apply pass) bytes
+    with torch.cuda.device(t.device), _Timed("groupnorm_tok2tok_bwd_params" if need_dparams else "groupnorm_tok2tok_bwd", work, t.device):
+        _check(L.mvi_groupnorm_tok2tok_backward(tc.data_ptr(), dy.data_ptr(), stats.data_ptr(), _f32(weight).data_ptr(),
+                                                _f32(bias).data_ptr(), _ptr(cb), _ptr(dx), _ptr(dw), _ptr(db), _ptr(dcb), N, int(frames), Cc, S,
+                                                num_groups, int(bool(silu)), _DT[t.dtype], ws.data_ptr(), ws.numel(), _stream(t.device)),
+               "group_norm_tok2tok_backward")
+    return dx, dw, db, dcb
 
 
 def attention_kernel_variant(Sq, Sk, D, dtype):

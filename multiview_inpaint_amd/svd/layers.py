@@ -738,14 +738,19 @@ def _resblock_forward_fused(self, x, emb, tokens_out=False):
     assert not tokens_out, "tokens_out is only offered on the channels-last route (_nhwc_path_ok)"
     if _conv_bwd_path_ok(self, x, emb):
         # under autograd with both convolutions on ops.conv3x3_tokens (HIP forward, dgrad and wgrad): the norms write tokens
-        # (ops.group_norm_tokens has a HIP backward), the turn back to planes between them is a plain copy autograd differentiates
+        # (ops.group_norm_tokens has a HIP backward); the norm between them stays token-major where ops.group_norm_tok2tok takes its
+        # HIP autograd route, else the turn back to planes is a plain copy autograd differentiates
         g1, g2 = self.in_layers[0], self.out_layers[0]
         N, _, H, W = x.shape
         t = ops.group_norm_tokens(x, g1.num_groups, g1.weight, g1.bias, g1.eps, silu=True)
         e = _emb_chan_bias(self.emb_layers, emb, conv1)
         t = ops.conv3x3_tokens(t, conv1.weight, H, W)
-        hp = t.transpose(1, 2).reshape(N, conv1.out_channels, H, W)
-        t = ops.group_norm_tokens(hp, g2.num_groups, g2.weight, g2.bias, g2.eps, silu=True, chan_bias=e)
+        if ops.group_norm_tok2tok_hip_autograd(t, g2.num_groups, e):
+            # the norm between the convolutions token-major on both sides, forward and backward: no copy, no transpose of the gradient
+            t = ops.group_norm_tok2tok(t, g2.num_groups, g2.weight, g2.bias, g2.eps, silu=True, chan_bias=e)
+        else:
+            hp = t.transpose(1, 2).reshape(N, conv1.out_channels, H, W)
+            t = ops.group_norm_tokens(hp, g2.num_groups, g2.weight, g2.bias, g2.eps, silu=True, chan_bias=e)
         t = ops.conv3x3_tokens(self.out_layers[2](t), conv2.weight, H, W)
         if isinstance(self.skip_connection, nn.Identity):
             return ops.tokens_to_planes_add(t, x, conv2.bias)

@@ -6,7 +6,8 @@ reference's own CPU-runnable case, not a fallback for the GPU.
 
 Under autograd (ControlNet training — SURVEY.md §2 row 21) attention stays on the HIP path, forward and backward
 (csrc/attn_bwd.hip: `attention` for bf16 / f16 with D = 64 and more than 32 keys, `attention_temporal` for every shape its
-forward takes), and so do GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip: `group_norm`, `group_norm_frames`, `group_norm_tokens`) and GEGLU
+forward takes), and so do GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip: `group_norm`, `group_norm_frames`, `group_norm_tokens`, and the
+token-major `group_norm_tok2tok` where `group_norm_tok2tok_backward_pays` says so) and GEGLU
 (csrc/ff_geglu_bwd.hip: `linear_geglu` at K = 320 in bf16 / f16, the projection recomputed, never stored; csrc/geglu.hip: `geglu`;
 from the sizes at which they were measured faster, `linear_geglu_backward_pays` / `geglu_backward_pays`), and the residual add(s) +
 LayerNorm of the transformer blocks (csrc/layernorm_bwd.hip: `add_layer_norm` for every width its forward takes, where
@@ -16,7 +17,7 @@ implicit-GEMM kernel with the transposed weight, the weight gradient on csrc/con
 so; the ResBlock reaches it through the opt-in layers.RESBLOCK_CONV_BWD.
 Every other kernel is forward-only: a GPU tensor that requires grad goes through PyTorch-ROCm's differentiable ops there
 (the projections, the strided, upsampling and frame convolutions — `linear_add_layer_norm` under grad is `linear_module` +
-`add_layer_norm` —, `add_lerp`, the token-major `group_norm_tok2tok`).
+`add_layer_norm` —, `add_lerp`).
 
 Reference ops: GroupNorm32 + SiLU (sgm/modules/diffusionmodules/util.py:259-276,
 openaimodel.py:257-261,292-305), Normalize (sgm/modules/attention.py:125-128),
@@ -165,15 +166,82 @@ def group_norm_tokens(x, num_groups, weight, bias, eps, silu=False, chan_bias=No
     return group_norm(x, num_groups, weight, bias, eps, silu=silu, chan_bias=chan_bias).flatten(2).transpose(1, 2).contiguous()
 
 
+# The HIP backward of the token-major GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip, gn_bwd_tok_*). MVI_GN_TOK2TOK_BWD=0 (or
+# ops.GROUPNORM_TOK2TOK_BACKWARD = False): group_norm_tok2tok takes PyTorch-ROCm's differentiable ops under autograd again.
+GROUPNORM_TOK2TOK_BACKWARD = os.environ.get("MVI_GN_TOK2TOK_BWD", "1") != "0"
+GROUPNORM_TOK2TOK_BACKWARD_MIN_ELEMENTS = None      # None: no class has been measured faster yet, nothing is routed by default
+
+
+def group_norm_tok2tok_backward_pays(N, C, S, frames, dtype):
+    """Whether forward + backward of the token-major norm on the HIP kernels is faster than the routes it replaces — the routing's second
+    question after hip_ops.group_norm_tok2tok_backward_supported. The rule (tools/bench_groupnorm_tok2tok_bwd.py ->
+    profiles/groupnorm_tok2tok_bwd_bench.json; DESIGN.md 'GroupNorm under autograd'): a class goes to HIP only where the HIP route's
+    median beats the faster of the PyTorch fallback and the ResBlock's transposing-copy + ops.group_norm_tokens middle by more than
+    that route's spread. The bench has NOT been run on a GPU yet (profiles/HISTORY.md says what is owed), so no class has won and the
+    line is None: every shape stays on the route it had. The tests lift the decision (a line of 0 elements)."""
+    line = GROUPNORM_TOK2TOK_BACKWARD_MIN_ELEMENTS
+    return line is not None and N * C * S >= line
+
+
+class _GroupNormTok2TokFn(torch.autograd.Function):
+    """Token-major GroupNorm(+SiLU) on the HIP kernels with a deterministic HIP backward, behind group_norm_tok2tok. Holds t, weight,
+    bias, chan_bias and the (mean, rstd) table — not y, nothing tensor-sized in fp32; nothing is cached outside ctx, so
+    torch.utils.checkpoint may re-run the forward."""
+
+    @staticmethod
+    def forward(ctx, t, weight, bias, chan_bias, num_groups, eps, silu, frames):
+        from . import hip_ops
+        tc = t if t.is_contiguous() else t.contiguous()
+        y, stats = hip_ops.group_norm_tok2tok_forward_stats(tc, num_groups, weight, bias, eps, silu, chan_bias=chan_bias, frames=frames)
+        ctx.save_for_backward(tc, weight, bias, chan_bias, stats)
+        ctx.cfg = (num_groups, bool(silu), frames)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        t, weight, bias, chan_bias, stats = ctx.saved_tensors
+        num_groups, silu, frames = ctx.cfg
+        n = ctx.needs_input_grad
+        dx, dw, db, dcb = hip_ops.group_norm_tok2tok_backward(dy.contiguous(), t, stats, num_groups, weight, bias, silu, chan_bias=chan_bias,
+                                                              frames=frames, need_dx=n[0], need_dparams=n[1] or n[2], need_dchan_bias=n[3])
+        return (dx, dw.to(weight.dtype) if n[1] else None, db.to(bias.dtype) if n[2] else None,
+                dcb.to(chan_bias.dtype).reshape(chan_bias.shape) if n[3] else None, None, None, None, None)
+
+
+def group_norm_tok2tok_hip_autograd(t, num_groups, chan_bias=None, frames=1):
+    """Under autograd: does group_norm_tok2tok run _GroupNormTok2TokFn for this tensor? (switch on, kernels compute the shape, 16-byte
+    aligned, and it pays) — layers asks before it keeps the ResBlock's middle token-major."""
+    if not (t.is_cuda and GROUPNORM_TOK2TOK_BACKWARD and t.dim() == 3 and t.numel() > 0 and frames >= 1):
+        return False
+    from . import hip_ops
+    N, S, C = t.shape
+    if chan_bias is not None and tuple(chan_bias.shape) != (N, C):
+        return False
+    if t.is_contiguous() and t.data_ptr() % 16 != 0:
+        return False
+    return (hip_ops.group_norm_tok2tok_backward_supported(N, C, S, num_groups, frames, t.dtype)
+            and group_norm_tok2tok_backward_pays(N, C, S, frames, t.dtype))
+
+
 def group_norm_tok2tok(t, num_groups, weight, bias, eps, silu=False, chan_bias=None, frames=1, partials=None):
     """GroupNorm(+SiLU) of token-major t [N, S, C] with token-major output (statistics per sample and group over (S, C/G));
     chan_bias [N, C] is added first. The norm between two convolutions that run on channels-last tensors. frames > 1: the temporal
-    layers' norm — statistics over the `frames` consecutive samples of a video (video_model.py:71-75), chan_bias still per sample."""
+    layers' norm — statistics over the `frames` consecutive samples of a video (video_model.py:71-75), chan_bias still per sample.
+    Under autograd `partials` is ignored: the norm runs its own statistics pass."""
     if t.is_cuda and not _needs_autograd(t, weight, bias, chan_bias):
         from . import hip_ops
         return hip_ops.group_norm_silu_tok2tok(t, num_groups, weight, bias, eps, silu, chan_bias=chan_bias, frames=frames, partials=partials)
+    if group_norm_tok2tok_hip_autograd(t, num_groups, chan_bias, frames):
+        return _GroupNormTok2TokFn.apply(t, weight, bias, chan_bias, num_groups, eps, silu, int(frames))
     _fallback(t, "group_norm_tok2tok", _why(t, weight, bias, chan_bias))
     N, S, C = t.shape
+    if t.dtype == torch.float64:
+        # fp64 (validation on the CPU) stays fp64: group_norm below computes in fp32
+        u = t if chan_bias is None else t + chan_bias.to(t.dtype).reshape(N, 1, C)
+        y = F.group_norm(u.reshape(N // frames, frames * S, C).transpose(1, 2), num_groups, weight.to(t.dtype), bias.to(t.dtype), eps)
+        return (F.silu(y) if silu else y).transpose(1, 2).reshape(N, S, C).contiguous()
     tf = t.float() if chan_bias is None else t.float() + chan_bias.float().reshape(N, 1, C)
     y = group_norm(tf.reshape(N // frames, frames * S, C).transpose(1, 2), num_groups, weight, bias, eps, silu=silu)
     return y.transpose(1, 2).reshape(N, S, C).to(t.dtype).contiguous()
