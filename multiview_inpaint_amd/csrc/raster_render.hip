@@ -380,8 +380,11 @@ int launch_wave_sum9_probe(const float* in, float* out, int n_waves, hipStream_t
 // pixels are summed in the lane before the wave reduction, and the reduction cost is paid once per 128 pixels.
 // Block = 128 threads = one tile; 128 list entries are staged per round. Decisions (alpha, active) use the same
 // operation order as the forward kernel (products rounded, one fma per sum), element-wise.
+// Registers decide the occupancy (LDS: 10.5 KB per block, 12 blocks per CU fit). The entry loop keeps ONE entry in registers,
+// read from LDS at the top of its iteration: 76 VGPRs and no scratch at five AND at six waves per SIMD. Five is the default:
+// on the MI355X six measured the same kernel time and did not pass the keep rule (profiles/render_backward_six_waves_ab.txt).
 #ifndef MVI_RB_WAVES
-#define MVI_RB_WAVES 5             // waves per SIMD the register allocation aims at (A/B builds: -DMVI_RB_WAVES=4; HISTORY.md round 5)
+#define MVI_RB_WAVES 5             // waves per SIMD the register allocation aims at (A/B builds: -DMVI_RB_WAVES=6)
 #endif
 __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVES, MVI_RB_WAVES))) void render_backward_kernel(
     Frame f, const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ point_list,
@@ -392,11 +395,9 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
     // the dense gradient outputs of the per-Gaussian chain rule are zeroed HERE (this kernel is bound by vector issue, its
     // memory pipes are idle): preprocess_backward then only writes the few per cent of rows that received a gradient
     zero_share(zero, threadIdx.x, kB2);
-    __shared__ uint32_t s_id[kB2];
-    __shared__ float2 s_xy[kB2];
-    __shared__ float s_t2[kB2];
-    __shared__ float4 s_co[kB2];
-    __shared__ float4 s_rgb[kB2];
+    // a staged entry is ONE record in one array: [0] (x, y, t2, Gaussian id), [1] conic + opacity, [2] colour — the reads of an
+    // entry share one address register with constant offsets (the forward's w_s layout)
+    __shared__ float4 s_ent[3][kB2];
     __shared__ float s_acc[kB2][9];                                   // raw moment sums per staged entry
     __shared__ uint32_t s_blast[2];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -433,7 +434,10 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
     const int total = (int)max(s_blast[0], s_blast[1]);
     const int rounds = (total + kB2 - 1) / kB2;
     const bool owner = wave_sum9_owner(lane);
-    const int my_mom = wave_sum9_moment(lane);
+    // LDS byte address of this lane's moment in accumulator row 0; the row of entry j lies 36 j further, and j is wave-uniform:
+    // one scalar multiply and one 32-bit vector add per entry (a generic pointer cost a 64-bit multiply-add on the vector unit)
+    typedef __attribute__((address_space(3))) float lds_float;
+    const uint32_t acc_lane = (uint32_t)(uintptr_t)(lds_float*)&s_acc[0][wave_sum9_moment(lane)];
 
     uint32_t n_id = 0;
     float2 n_xy = make_float2(0.f, 0.f);
@@ -450,44 +454,41 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
         const int hi = total - r * kB2;
         const int n = hi < kB2 ? hi : kB2;
         __syncthreads();
-        s_id[tid] = n_id;
-        s_xy[tid] = n_xy;
-        s_co[tid] = n_co;
-        s_t2[tid] = active_t2(n_co);
-        s_rgb[tid] = n_cd;
+        s_ent[0][tid] = make_float4(n_xy.x, n_xy.y, active_t2(n_co), __uint_as_float(n_id));
+        s_ent[1][tid] = n_co;
+        s_ent[2][tid] = n_cd;
 #pragma unroll
         for (int c = 0; c < 9; ++c) s_acc[tid][c] = 0.0f;
         __syncthreads();
         if (r + 1 < rounds) fetch(r + 1);
         for (int c = 0; c < n; c += 64) {
             const int e = c + lane;
+            const float4 ce = s_ent[0][e];
             const bool keep = e < n && (uint32_t)(hi - 1 - e) < wave_last &&
-                              quad_overlap(s_xy[e], s_co[e], s_t2[e], (float)hx0, (float)hy0, 15.0f, 7.0f);
+                              quad_overlap(make_float2(ce.x, ce.y), s_ent[1][e], ce.z, (float)hx0, (float)hy0, 15.0f, 7.0f);
             unsigned long long mask = ballot64(keep);
-            if (mask == 0ull) continue;
-            int j = c + __builtin_ctzll(mask);                  // wave-uniform
-            auto entry = [&](const int jc, const float2 p, const float4 co, const float4 col, float2& nx_p, float4& nx_co,
-                             float4& nx_col, int& jn) -> bool {
+            // The entry is read at the top of its iteration, as in the forward kernel: the other waves of the SIMD cover the LDS
+            // latency, and a second entry held in registers (18 of them, the loop body emitted twice) bought nothing measurable.
+            while (mask != 0ull) {
+                const int jc = c + __builtin_ctzll(mask);           // wave-uniform
                 mask &= mask - 1;
-                const bool more = mask != 0ull;
-                jn = more ? c + __builtin_ctzll(mask) : jc;
-                nx_p = s_xy[jn];
-                nx_co = s_co[jn];
-                nx_col = s_rgb[jn];
+                const float4* rec = &s_ent[0][jc];
+                const float2 p = *reinterpret_cast<const float2*>(rec);
+                const float4 co = rec[kB2], col = rec[2 * kB2];
                 const uint32_t pos = (uint32_t)(hi - 1 - jc);
                 const float dx = p.x - pfx;
                 const f2 dy = splat(p.y) - pfy;
                 const f2 power = gauss_power(co, dx, dy);          // the forward's rounding recipe
                 const f2 G = {__expf(power.x), __expf(power.y)};    // power > 0 (inf, NaN) is never active: selected away
                 const f2 oG = co.w * G;
-                const f2 alpha = __builtin_elementwise_min(splat(kAlphaMax), oG);
-                const bool act0 = pos < last0 && power.x <= 0.0f && alpha.x >= kAlphaMin;
-                const bool act1 = pos < last1 && power.y <= 0.0f && alpha.y >= kAlphaMin;
-                const f2 am = {act0 ? alpha.x : 0.0f, act1 ? alpha.y : 0.0f};          // alpha, o G of the ACTIVE pixels, else 0
-                const f2 gm = {act0 ? oG.x : 0.0f, act1 ? oG.y : 0.0f};
+                // alpha = min(0.99, o G) >= 1/255 iff o G >= 1/255, and min(0.99, 0) = 0: one select per pixel instead of two
+                const bool act0 = pos < last0 && power.x <= 0.0f && oG.x >= kAlphaMin;
+                const bool act1 = pos < last1 && power.y <= 0.0f && oG.y >= kAlphaMin;
+                const f2 gm = {act0 ? oG.x : 0.0f, act1 ? oG.y : 0.0f};                // o G of the ACTIVE pixels, else 0
+                const f2 am = __builtin_elementwise_min(splat(kAlphaMax), gm);         // alpha of the active pixels, else 0
                 // (an active alpha is >= 1/255: nonzero bits. Asking the two lane predicates themselves made the compiler
                 // materialise them as 0 / 1 and compare again: four vector instructions per entry)
-                const unsigned long long any_active = ballot64((__float_as_uint(am.x) | __float_as_uint(am.y)) != 0u);
+                const unsigned long long any_active = ballot64((__float_as_uint(gm.x) | __float_as_uint(gm.y)) != 0u);
                 const f2 om = splat(1.0f) - am;                      // in [0.01, 1]; exactly 1 for an inactive pixel
                 const f2 inv = {__builtin_amdgcn_rcpf(om.x), __builtin_amdgcn_rcpf(om.y)};
                 const f2 Tn = T * inv;                               // (= T for an inactive pixel)
@@ -503,16 +504,11 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
                     float m_w = mw.x + mw.y, m_x = vx.x + vx.y, m_y = vy.x + vy.y, m_xx = vxx.x + vxx.y,
                           m_xy = vxy.x + vxy.y, m_yy = vyy.x + vyy.y, m_r = vr.x + vr.y, m_g = vg.x + vg.y, m_b = vb.x + vb.y;
                     const float sum = wave_sum9(m_w, m_x, m_y, m_xx, m_xy, m_yy, m_r, m_g, m_b);
-                    if (owner) atomicAdd(&s_acc[0][0] + (__mul24(jc, 9) + my_mom), sum);   // both waves add into the same rows; nobody waits for it
+                    // both waves add into the same rows; nobody waits for it
+                    uint32_t row = 36u * (uint32_t)jc;
+                    asm("" : "+s"(row));                     // the product stays on the scalar unit
+                    if (owner) __hip_atomic_fetch_add((lds_float*)(uintptr_t)(acc_lane + row), sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
-                return more;
-            };
-            float2 pA = s_xy[j], pB;
-            float4 coA = s_co[j], coB, colA = s_rgb[j], colB;
-            int jB = j;
-            while (true) {
-                if (!entry(j, pA, coA, colA, pB, coB, colB, jB)) break;
-                if (!entry(jB, pB, coB, colB, pA, coA, colA, j)) break;
             }
         }
         __syncthreads();
@@ -531,7 +527,7 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
                                    (__float_as_uint(a3) | __float_as_uint(a4) | __float_as_uint(a5)) |
                                    (__float_as_uint(a6) | __float_as_uint(a7) | __float_as_uint(a8))) & 0x7FFFFFFFu) != 0u;
                 if (any) {
-                    const float4 co = s_co[e1];
+                    const float4 co = s_ent[1][e1];
                     a[0] = -0.5f * (float)f.W * (co.x * a1 + co.y * a2);       // dL/dmean2D.x (NDC-scaled)
                     a[1] = -0.5f * (float)f.H * (co.z * a2 + co.y * a1);       // dL/dmean2D.y
                     a[2] = -0.5f * a3;                                         // dL/dA
@@ -539,7 +535,7 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
                     a[4] = -0.5f * a5;                                         // dL/dC
                     a[5] = a0 / co.w;                                          // dL/dopacity = sum G dL/dalpha
                 } else {
-                    s_id[e1] = 0xFFFFFFFFu;                                    // never evaluated by either half tile
+                    s_ent[0][e1].w = __uint_as_float(0xFFFFFFFFu);                                   // never evaluated by either half tile
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -548,7 +544,7 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
 #pragma unroll 4
             for (int it = 0; it < 16; ++it) {
                 const int e = wave * 64 + it * 4 + (lane >> 4);
-                const uint32_t id = e < n ? s_id[e] : 0xFFFFFFFFu;
+                const uint32_t id = e < n ? __float_as_uint(s_ent[0][e].w) : 0xFFFFFFFFu;
                 if (id == 0xFFFFFFFFu || comp >= 9) continue;
                 atomicAdd(&grad_rows[(size_t)id * kRow + comp], s_acc[e][comp]);
                 if (comp == 0) touched[id] = 1;                // gradient support (idempotent store)
