@@ -179,7 +179,7 @@ int mvi_raster_backward_geom(const mvi_raster_settings* s, int32_t P, int32_t M,
                              float* dL_dshs, float* dL_dcolors, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
                              void* stream);
 
-/* mvi_raster_backward_geom for the Gaussians [first, first + count) only (first a multiple of 64): every pointer is the
+/* mvi_raster_backward_geom for the Gaussians [first, first + count) only (any first row): every pointer is the
  * base of the FULL [P, ...] array, as in mvi_raster_backward_geom; only rows of the range are read and written. Lets a
  * view-parallel trainer run the chain rule in a few ranges and start the all-reduce of a finished range's gradients
  * while the next range is computed (multiview_inpaint_amd/dist.py: RangedGradExchange). Ranges are independent: the
@@ -194,14 +194,15 @@ int mvi_raster_backward_geom_range(const mvi_raster_settings* s, int32_t P, int3
 /* Introspection used by the parity tests: copies of intermediate device arrays' addresses.
  * Pointers alias the caller's scratch buffers; valid while those are. */
 typedef struct mvi_raster_views {
-    const float* depths;          /* [P] */
+    const float* depths;          /* [P] valid after mvi_raster_materialize_geom_views (every kernel reads rgbd[.][3]) */
     const float* means2D;         /* [P,2] pixel centres */
-    const float* cov3D_a;         /* [P,4] xx, xy, xz, yy */
-    const float* cov3D_b;         /* [P,2] yz, zz */
+    const float* cov3D_a;         /* [P,4] xx, xy, xz, yy   valid after mvi_raster_materialize_geom_views: the forward does */
+    const float* cov3D_b;         /* [P,2] yz, zz           not store cov3D, the backward derives it from scale / rotation */
     const float* conic_opacity;   /* [P,4] */
     const float* rgbd;            /* [P,4] r, g, b, depth; deferred SH colours (the default): (-1, -1, -1, depth) for a visible
                                    * Gaussian no tile has staged yet — see mvi_raster_color_mode / mvi_raster_resolve_colors */
-    const uint32_t* tiles_touched;/* [P] */
+    const uint32_t* tiles_touched;/* [P] valid after mvi_raster_materialize_geom_views (grids above 256 x 256 tiles and
+                                   * mvi_raster_binning_version(1): written by the forward as well) */
     const uint8_t* clamped;       /* [P] bit c = colour channel c clamped at 0 (0 while the colour is pending) */
     const void* tile_ids_sorted;  /* [D] high word of the sort key, tile_id_bytes (2 or 4) per entry; the full key of
                                    * pair i is tile_ids_sorted[i] << 32 | bits(depths[point_list[i]]). No kernel reads it and
@@ -219,6 +220,15 @@ typedef struct mvi_raster_views {
 int mvi_raster_get_views(int32_t P, int64_t num_rendered, int32_t image_width, int32_t image_height,
                          const void* geom, const void* binning, const void* image,
                          mvi_raster_views* out);
+/* Fills the views depths, cov3D_a, cov3D_b and tiles_touched of a finished forward, which no kernel reads and the forward
+ * therefore leaves unwritten, with exactly what it would have stored: cov3D of every Gaussian in front of the near plane
+ * (view-space z > 0.2), depths = rgbd[.][3] of every Gaussian with radii > 0, tiles_touched = area of the tile rectangle of
+ * every Gaussian. means3D, scales / rotations or cov3D_precomp, radii and geom are the forward's own arguments (after
+ * mvi_raster_forward_geom_raw: xyz, raw_scaling, raw_rotation, NULL; the scratch remembers that they are raw). Enqueued on
+ * `stream`; touches nothing else, so it may run before or after the backward. */
+int mvi_raster_materialize_geom_views(const mvi_raster_settings* s, int32_t P, const float* means3D, const float* scales,
+                                      const float* rotations, const float* cov3D_precomp, const int32_t* radii, void* geom,
+                                      void* stream);
 /* Fills tile_ids_sorted of a finished forward (same P, num_rendered, size and scratch buffers) from its tile ranges: pair
  * positions [ranges[t][0], ranges[t][1]) get tile id t; empty tiles write nothing. Enqueued on `stream`; touches nothing else,
  * so it may run before or after the backward. A no-op when num_rendered is 0. */

@@ -121,6 +121,8 @@ def lib():
     L.mvi_raster_mark_visible.argtypes = [i32, vp, vp, vp, vp, vp]
     L.mvi_raster_get_views.restype = C.c_int
     L.mvi_raster_get_views.argtypes = [i32, i64, i32, i32, vp, vp, vp, C.POINTER(RasterViews)]
+    L.mvi_raster_materialize_geom_views.restype = C.c_int
+    L.mvi_raster_materialize_geom_views.argtypes = [C.POINTER(RasterSettings), i32] + [vp] * 7
     L.mvi_raster_materialize_tile_ids.restype = C.c_int
     L.mvi_raster_materialize_tile_ids.argtypes = [i32, i64, i32, i32, vp, vp, vp]
     L.mvi_raster_timing_enable.restype = C.c_int

@@ -440,7 +440,6 @@ static int backward_render_impl(mvi::Frame& f, int32_t P, int64_t D, const int32
         mvi::ZeroRegions z;
         z.add(grad_rows, (size_t)mvi::kGradRow * (size_t)P);
         z.add(g.touched, ((size_t)P + 15) / 16 * 4);
-        z.add(g.touched_count, 1);
         if (mvi::launch_zero_regions(z, st)) return hip_fail("zero grad rows", hipGetLastError());
     }
     {
@@ -470,8 +469,8 @@ static int backward_geom_range_impl(const mvi_raster_settings* s, int32_t P, int
                                     void* stream) {
     mvi::Frame f;
     if (int rc = make_frame(s, P, M, f)) return rc;
-    if (first < 0 || count < 0 || (int64_t)first + count > P || (first % 64) != 0)
-        return fail(MVI_EINVAL, "backward range out of bounds or not 64-aligned%s: first %lld count %lld", "", (long long)first, (long long)count);
+    if (first < 0 || count < 0 || (int64_t)first + count > P)
+        return fail(MVI_EINVAL, "backward range out of bounds%s: first %lld count %lld", "", (long long)first, (long long)count);
     if (P == 0 || count == 0) return MVI_OK;
     if ((shs == nullptr) == (colors_precomp == nullptr))
         return fail(MVI_EINVAL, "Please provide excatly one of either SHs or precomputed colors!%s");
@@ -487,8 +486,7 @@ static int backward_geom_range_impl(const mvi_raster_settings* s, int32_t P, int
     // per-Gaussian views of the scratch (carved for the full P) and every caller array, moved to the range's first row
     mvi::GeomView g = mvi::carve_geom(const_cast<void*>(geom), P);
     const size_t o = (size_t)first;
-    g.depths += o; g.xy += o; g.cov_a += o; g.cov_b += o; g.conic_opacity += o; g.rgbd += o; g.tiles_touched += o; g.rect += o;
-    g.clamped += o;
+    g.xy += o; g.conic_opacity += o; g.rgbd += o; g.rect += o; g.clamped += o;
     auto at = [o](auto* p, size_t w) { return p ? p + o * w : p; };
     f.P = count;
     hipStream_t st = (hipStream_t)stream;
@@ -567,6 +565,21 @@ int mvi_raster_get_views(int32_t P, int64_t D, int32_t W, int32_t H, const void*
         mvi::ImageView im = mvi::carve_image(const_cast<void*>(image), W, H);
         out->ranges = im.ranges; out->final_T = im.final_T; out->n_contrib = im.n_contrib;
     }
+    return MVI_OK;
+}
+
+int mvi_raster_materialize_geom_views(const mvi_raster_settings* s, int32_t P, const float* means3D, const float* scales,
+                                      const float* rotations, const float* cov3D_precomp, const int32_t* radii, void* geom,
+                                      void* stream) {
+    mvi::Frame f;
+    if (int rc = make_frame(s, P, 0, f)) return rc;
+    if (P == 0) return MVI_OK;
+    if (!means3D || !radii || !geom) return fail(MVI_EINVAL, "NULL means3D/radii/geom in materialize_geom_views%s");
+    if (((scales == nullptr) || (rotations == nullptr)) == (cov3D_precomp == nullptr))
+        return fail(MVI_EINVAL, "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!%s");
+    mvi::GeomView g = mvi::carve_geom(geom, P);
+    if (mvi::launch_materialize_geom_views(f, means3D, scales, rotations, cov3D_precomp, radii, g, (hipStream_t)stream))
+        return hip_fail("materialize_geom_views", hipGetLastError());
     return MVI_OK;
 }
 

@@ -88,20 +88,18 @@ struct ColorSource {
 
 // ---- scratch layouts (all offsets 256-B aligned) ---------------------------------------------
 struct GeomView {
-    float* depths;            // [P]
+    float* depths;            // [P] view only: written by launch_materialize_geom_views (every kernel reads rgbd.w)
     float2* xy;               // [P]
-    float4* cov_a;            // [P] cov3D xx, xy, xz, yy   (16-byte and 8-byte records: every lane's
-    float2* cov_b;            // [P] cov3D yz, zz           store/load is one whole aligned access)
+    float4* cov_a;            // [P] cov3D xx, xy, xz, yy   views only, written by launch_materialize_geom_views: the
+    float2* cov_b;            // [P] cov3D yz, zz           backward derives cov3D again from scale and rotation
     float4* conic_opacity;    // [P]
     float4* rgbd;             // [P] r, g, b, view-space depth (one gather per staged list entry)
-    uint32_t* tiles_touched;  // [P]
+    uint32_t* tiles_touched;  // [P] binning version 1 (its pair offsets); version 2: a view, launch_materialize_geom_views
     uint2* rect;              // [P] tile rectangle (x0 | y0 << 16, w | h << 16); w * h = tiles touched, 0 when culled:
                               //     pair emission gathers this one 8-byte record per depth-ordered Gaussian
     uint8_t* clamped;         // [P] bit c set = colour channel c was clamped at 0
     uint8_t* front;           // [P] deferred colours: 1 = named by a leading entry of some tile's list (zeroed by the preprocess)
     struct ColorSource* color_src;   // [1] where the SH colours of this forward come from (deferred evaluation, see ColorSource)
-    uint32_t* touched_list;   // [P] the touched Gaussians, compacted (any order); touched_count[0] of them
-    uint32_t* touched_count;  // [1]
     uint8_t* touched;         // [P] 1 = the render backward added something to this Gaussian's accumulation row (gradient
                               //     support: ~3 % of the Gaussians of the bench scene; the others are occluded). Zeroed with the rows.
     uint32_t* block_sums;     // [npre]   tiles touched per preprocess block (kPB Gaussians)
@@ -174,8 +172,7 @@ inline GeomView carve_geom(void* base, int P) {
     g.rect = (uint2*)take(8 * n);
     g.clamped = (uint8_t*)take(n);
     g.touched = (uint8_t*)take(n);
-    g.touched_list = (uint32_t*)take(4 * n);
-    g.touched_count = (uint32_t*)take(4);
+    take(4 * n); take(4);     // formerly the compacted support list and its length: kept so that the scratch sizes stay
     g.front = (uint8_t*)take(n);
     g.color_src = (ColorSource*)take(sizeof(ColorSource));
     const size_t npre = (n + kPB - 1) / kPB;
@@ -573,6 +570,9 @@ int launch_binning2(const Frame& f, GeomView g, BinningView b, ImageView im, int
 int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D,
                           float* out_color, float* out_depth, hipStream_t st, float* zero_rows = nullptr);
 int launch_resolve_colors(const Frame& f, GeomView g, hipStream_t st);      // evaluates every colour still pending
+// fills g.depths, g.cov_a / g.cov_b and g.tiles_touched, which the forward leaves unwritten, from the forward's inputs
+int launch_materialize_geom_views(const Frame& f, const float* means3D, const float* scales, const float* rotations,
+                                  const float* cov3D_precomp, const int32_t* radii, GeomView g, hipStream_t st);
 int launch_render_backward(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D,
                            const float* dL_dpix, float* grad_rows, hipStream_t st, const ZeroRegions* zero = nullptr);
 int launch_wave_sum9_probe(const float* in, float* out, int n_waves, hipStream_t st);   // diagnostics: wave_sum9 on its own

@@ -14,6 +14,10 @@
 #include "raster_common.h"
 #include "raster_scan.h"
 
+#ifndef MVI_SPARSE_FLAGS
+#define MVI_SPARSE_FLAGS 1024
+#endif
+
 namespace mvi {
 
 // Copies the block's `n_rec` records of `rec` floats each from `src` (contiguous) into LDS rows of
@@ -123,6 +127,37 @@ __device__ __forceinline__ void quat_to_rot(float r, float x, float y, float z, 
     R[2][2] = __builtin_fmaf(-2.0f, __builtin_fmaf(x, x, y * y), 1.0f);
 }
 
+// raw mode: y = q / max(|q|, 1e-12) (F.normalize, gaussian_model.py:44-59); returns the norm for the chain rule. One form for
+// the forward and the backward kernels, so that both see the same rotation bits.
+__device__ __forceinline__ float quat_normalize(float4& q) {
+#pragma clang fp contract(off)
+    const float nq = fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-12f);
+    q = make_float4(q.x / nq, q.y / nq, q.z / nq, q.w / nq);
+    return nq;
+}
+
+// cov3D (xx, xy, xz, yy, yz, zz) = (R S)(R S)^T from the quaternion `q` (raw mode: already normalised) and the scale
+// (raw mode: its logarithm). The forward derives the conic from it; the backward kernels call it again for the few Gaussians
+// that received a gradient instead of reading 24 bytes per visible Gaussian back (same inputs, same bits).
+__device__ __forceinline__ void cov3d_from_scale_rot(const Frame& f, float4 q, const float* scale_in, float* c6) {
+#pragma clang fp contract(off)
+    float R[3][3], Mx[3][3];
+    quat_to_rot(q.x, q.y, q.z, q.w, R);
+    float sa[3] = {scale_in[0], scale_in[1], scale_in[2]};
+    if (f.raw) { sa[0] = expf(sa[0]); sa[1] = expf(sa[1]); sa[2] = expf(sa[2]); }
+    float s[3] = {f.scale_modifier * sa[0], f.scale_modifier * sa[1], f.scale_modifier * sa[2]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Mx[r][j] = R[r][j] * s[j];
+    c6[0] = dot3(Mx[0][0], Mx[0][1], Mx[0][2], Mx[0][0], Mx[0][1], Mx[0][2]);
+    c6[1] = dot3(Mx[0][0], Mx[0][1], Mx[0][2], Mx[1][0], Mx[1][1], Mx[1][2]);
+    c6[2] = dot3(Mx[0][0], Mx[0][1], Mx[0][2], Mx[2][0], Mx[2][1], Mx[2][2]);
+    c6[3] = dot3(Mx[1][0], Mx[1][1], Mx[1][2], Mx[1][0], Mx[1][1], Mx[1][2]);
+    c6[4] = dot3(Mx[1][0], Mx[1][1], Mx[1][2], Mx[2][0], Mx[2][1], Mx[2][2]);
+    c6[5] = dot3(Mx[2][0], Mx[2][1], Mx[2][2], Mx[2][0], Mx[2][1], Mx[2][2]);
+}
+
 struct Ewa {
     float Tm[2][3];
     float tx, ty, tz, xmul, ymul;
@@ -194,8 +229,7 @@ __global__ __launch_bounds__(kPB) void preprocess_forward_kernel(
         if (!cov3D_precomp) q = *reinterpret_cast<const float4*>(rotations + 4 * (size_t)i);
         opac = opacities[i];
         if (f.raw) {                                        // gaussian_model.py:44-59: sigmoid, F.normalize (eps 1e-12)
-            const float nq = fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-12f);
-            q = make_float4(q.x / nq, q.y / nq, q.z / nq, q.w / nq);
+            quat_normalize(q);
             opac = sigmoidf_(opac);
         }
     }
@@ -226,24 +260,10 @@ __global__ __launch_bounds__(kPB) void preprocess_forward_kernel(
 #pragma unroll
                 for (int k = 0; k < 6; ++k) c6[k] = cov3D_precomp[6 * (size_t)i + k];
             } else {
-                float R[3][3], Mx[3][3];
-                quat_to_rot(q.x, q.y, q.z, q.w, R);
-                float sa[3] = {s_scale[3 * tid], s_scale[3 * tid + 1], s_scale[3 * tid + 2]};
-                if (f.raw) { sa[0] = expf(sa[0]); sa[1] = expf(sa[1]); sa[2] = expf(sa[2]); }
-                float s[3] = {f.scale_modifier * sa[0], f.scale_modifier * sa[1], f.scale_modifier * sa[2]};
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) Mx[r][j] = R[r][j] * s[j];
-                c6[0] = dot3(Mx[0][0], Mx[0][1], Mx[0][2], Mx[0][0], Mx[0][1], Mx[0][2]);
-                c6[1] = dot3(Mx[0][0], Mx[0][1], Mx[0][2], Mx[1][0], Mx[1][1], Mx[1][2]);
-                c6[2] = dot3(Mx[0][0], Mx[0][1], Mx[0][2], Mx[2][0], Mx[2][1], Mx[2][2]);
-                c6[3] = dot3(Mx[1][0], Mx[1][1], Mx[1][2], Mx[1][0], Mx[1][1], Mx[1][2]);
-                c6[4] = dot3(Mx[1][0], Mx[1][1], Mx[1][2], Mx[2][0], Mx[2][1], Mx[2][2]);
-                c6[5] = dot3(Mx[2][0], Mx[2][1], Mx[2][2], Mx[2][0], Mx[2][1], Mx[2][2]);
+                cov3d_from_scale_rot(f, q, s_scale + 3 * tid, c6);
             }
-            g.cov_a[i] = make_float4(c6[0], c6[1], c6[2], c6[3]);
-            g.cov_b[i] = make_float2(c6[4], c6[5]);
+            // cov3D is not stored: nothing of the forward reads it, and the backward derives it again for the Gaussians that
+            // received a gradient (mvi_raster_materialize_geom_views fills the view for whoever asks)
 
             Ewa e;
             ewa_setup(f, V, vx, vy, vz, e);
@@ -278,8 +298,7 @@ __global__ __launch_bounds__(kPB) void preprocess_forward_kernel(
                 r0 = r1 = r2 = -1.0f;                    // pending: evaluated by the render kernel when it first stages this Gaussian
             }
             g.clamped[i] = (uint8_t)clamp_bits;
-            g.rgbd[i] = make_float4(r0, r1, r2, vz);
-            g.depths[i] = vz;
+            g.rgbd[i] = make_float4(r0, r1, r2, vz);        // .w is the depth every kernel reads (the `depths` view: on demand)
             depth_key = vz;
             g.xy[i] = make_float2(pix_x, pix_y);
             g.conic_opacity[i] = make_float4(c * det_inv, -b * det_inv, a * det_inv, opac);
@@ -289,7 +308,7 @@ __global__ __launch_bounds__(kPB) void preprocess_forward_kernel(
         } while (false);
         radii[i] = rad_out;
         if (defer_colors) g.front[i] = 0;
-        g.tiles_touched[i] = touched;
+        if (!f.bin_v2) g.tiles_touched[i] = touched;         // version 1's pair offsets; version 2 takes the rectangle
         g.rect[i] = rect;
         // level-1 sort input (binning): depth bits (monotonic for depth > 0.2), culled Gaussians last
         g.dkeys[0][i] = touched ? __float_as_uint(depth_key) : 0xFFFFFFFFu;
@@ -357,16 +376,16 @@ __device__ __forceinline__ void sh_basis_grad(int deg, float x, float y, float z
 // dL/dA, dL/dB, dL/dC of power = -0.5(A dx^2 + C dy^2) - B dx dy, dL/dopacity, dL/drgb).
 // Outputs are written for every Gaussian (zeros where radii == 0).
 // Chain rule from the 2-D gradients of one Gaussian (gr: dL/dmean2D (NDC-scaled) 2, dL/dconic 3, ...) to dL/dcov3D (g6)
-// and the covariance / projection part of dL/dmean3D (dm). Shared by the dense and the sparse backward kernel.
+// and the covariance / projection part of dL/dmean3D (dm). c6: the Gaussian's cov3D, as the forward had it (the caller's
+// cov3D_precomp row, or cov3d_from_scale_rot again). Shared by the dense and the sparse backward kernel.
 __device__ __forceinline__ void backward_cov_and_mean(const Frame& f, float px, float py, float pz, const float* gr,
-                                                  float4 ca, float2 cb, float* dm, float* g6) {
+                                                  const float* c6, float* dm, float* g6) {
     float V[16], PM[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) { V[k] = f.view[k]; PM[k] = f.proj[k]; }
     float vx = affine3(V[0], V[4], V[8], V[12], px, py, pz);
     float vy = affine3(V[1], V[5], V[9], V[13], px, py, pz);
     float vz = affine3(V[2], V[6], V[10], V[14], px, py, pz);
-    float c6[6] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y};
     Ewa e;
     ewa_setup(f, V, vx, vy, vz, e);
     float a, b, c;
@@ -424,15 +443,10 @@ __device__ __forceinline__ void backward_cov_and_mean(const Frame& f, float px, 
 
 }
 
-// dL/dcov3D (g6) -> dL/dscale (ds), dL/dquaternion (dq); raw mode: through exp and the normalisation as well
-__device__ __forceinline__ void backward_scale_rot(const Frame& f, const float* g6, float4 qrot, const float* sa_in, float* ds,
+// dL/dcov3D (g6) -> dL/dscale (ds), dL/dquaternion (dq); raw mode: through exp and the normalisation as well (q: the
+// normalised quaternion that cov3d_from_scale_rot took, nq: the norm quat_normalize returned; 1 outside raw mode)
+__device__ __forceinline__ void backward_scale_rot(const Frame& f, const float* g6, float4 q, float nq, const float* sa_in, float* ds,
                                                    float* dq) {
-    float4 q = qrot;
-    float nq = 1.0f;
-    if (f.raw) {
-        nq = fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-12f);
-        q = make_float4(q.x / nq, q.y / nq, q.z / nq, q.w / nq);
-    }
     float R[3][3];
     quat_to_rot(q.x, q.y, q.z, q.w, R);
     float sa[3] = {sa_in[0], sa_in[1], sa_in[2]};
@@ -497,19 +511,23 @@ __global__ __launch_bounds__(kPB) void preprocess_backward_kernel(
     const float raw_o = (f.raw && in_range) ? rawx.raw_opacity[i] : 0.0f;
     const bool live = in_range && radii[i] > 0;
     float gr[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    float4 ca = make_float4(0.f, 0.f, 0.f, 0.f), qrot = make_float4(1.f, 0.f, 0.f, 0.f);
-    float2 cb = make_float2(0.f, 0.f);
+    float4 qrot = make_float4(1.f, 0.f, 0.f, 0.f);
+    float c6[6] = {0, 0, 0, 0, 0, 0};
     uint32_t cl_bits = 0;
     if (live) {
         const float4* row = reinterpret_cast<const float4*>(grad_rows + (size_t)i * kGradRow);
         float4 a = row[0], b4 = row[1];
         gr[0] = a.x; gr[1] = a.y; gr[2] = a.z; gr[3] = a.w; gr[4] = b4.x; gr[5] = b4.y; gr[6] = b4.z; gr[7] = b4.w;
         gr[8] = grad_rows[(size_t)i * kGradRow + 8];
-        ca = g.cov_a[i];
-        cb = g.cov_b[i];
-        if (!cov3D_precomp) qrot = *reinterpret_cast<const float4*>(rotations + 4 * (size_t)i);
+        if (cov3D_precomp) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) c6[k] = cov3D_precomp[6 * (size_t)i + k];
+        } else {
+            qrot = *reinterpret_cast<const float4*>(rotations + 4 * (size_t)i);
+        }
         if (shs) cl_bits = g.clamped[i];
     }
+    const float nq = (f.raw && live) ? quat_normalize(qrot) : 1.0f;
     __syncthreads();
     s_dm2d[3 * tid] = gr[0]; s_dm2d[3 * tid + 1] = gr[1]; s_dm2d[3 * tid + 2] = 0.0f;
     if (in_range) {
@@ -530,7 +548,8 @@ __global__ __launch_bounds__(kPB) void preprocess_backward_kernel(
     const int nb = (f.deg + 1) * (f.deg + 1);
     if (live) {
         const float px = s_mean[3 * tid], py = s_mean[3 * tid + 1], pz = s_mean[3 * tid + 2];
-        backward_cov_and_mean(f, px, py, pz, gr, ca, cb, dm, g6);
+        if (!cov3D_precomp) cov3d_from_scale_rot(f, qrot, s_scale + 3 * tid, c6);     // the forward's cov3D again: same inputs, same bits
+        backward_cov_and_mean(f, px, py, pz, gr, c6, dm, g6);
 
         if (shs) {
             float ox = px - f.campos[0], oy = py - f.campos[1], oz = pz - f.campos[2];
@@ -574,7 +593,7 @@ __global__ __launch_bounds__(kPB) void preprocess_backward_kernel(
         float ds[3] = {0, 0, 0}, dq[4] = {0, 0, 0, 0};
         if (live) {
             const float sa_in[3] = {s_scale[3 * tid], s_scale[3 * tid + 1], s_scale[3 * tid + 2]};
-            backward_scale_rot(f, g6, qrot, sa_in, ds, dq);
+            backward_scale_rot(f, g6, qrot, nq, sa_in, ds, dq);
         }
         s_dscale[3 * tid] = ds[0]; s_dscale[3 * tid + 1] = ds[1]; s_dscale[3 * tid + 2] = ds[2];
         if (in_range) *reinterpret_cast<float4*>(dL_drots + 4 * (size_t)i) = make_float4(dq[0], dq[1], dq[2], dq[3]);
@@ -594,12 +613,18 @@ __global__ __launch_bounds__(kPB) void preprocess_backward_kernel(
 }
 
 // The per-Gaussian chain rule for the Gaussians whose accumulation row the render backward TOUCHED (g.touched), one lane per
-// Gaussian, no LDS: in the bench scene 3 % of the Gaussians receive a gradient (the rest are occluded), and an untouched row
-// is exactly zero, so its outputs are exactly zero — the caller zeroed every output array beforehand (the render backward does
-// it on the side) and this kernel reads and writes the touched rows only, with per-lane accesses. Same expressions as
-// preprocess_backward_kernel (shared helpers), which stays the form for dense outputs (split / ranged backward).
-constexpr int kSparseBlock = 64;          // one-wave blocks: ~750 of them for the 48 k touched Gaussians of the bench scene, spread over
-                                          // every CU (256-thread blocks: 188 blocks, most CUs idle behind a 4-round-trip latency chain)
+// Gaussian, no staging of rows through LDS: in the bench scene 3 % of the Gaussians receive a gradient (the rest are occluded),
+// and an untouched row is exactly zero, so its outputs are exactly zero — the caller zeroed every output array beforehand (the
+// render backward does it on the side) and this kernel reads and writes the touched rows only, with per-lane accesses. Same
+// expressions as preprocess_backward_kernel (shared helpers), which stays the form for dense outputs (split / ranged backward).
+//
+// The compaction of the flags is part of the kernel: a one-wave block owns FLAGS consecutive flags (FLAGS / 64 per lane, read
+// as 16-byte words), scans the lanes' counts, writes the indices of its touched Gaussians into LDS and then takes them from
+// there in rounds of 64. No list in memory, no count word, no atomic: a Gaussian's loads wait for this block's own flag load
+// and LDS, not for a compaction launch, the list length and the list slot (three dependent trips to memory).
+constexpr int kSparseBlock = 64;
+constexpr int kSparseFlags = MVI_SPARSE_FLAGS;     // flags per block: 1024 and 4096 were measured (profiles/HISTORY.md)
+template <int FLAGS>
 __global__ __launch_bounds__(kSparseBlock) void preprocess_backward_sparse_kernel(
     Frame f, const float* __restrict__ means3D, const float* __restrict__ shs, const float* __restrict__ scales,
     const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp, GeomView g,
@@ -607,11 +632,33 @@ __global__ __launch_bounds__(kSparseBlock) void preprocess_backward_sparse_kerne
     float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolors, float* __restrict__ dL_dshs,
     float* __restrict__ dL_dcov3D, float* __restrict__ dL_dscales, float* __restrict__ dL_drots, RawBackwardExtra rawx,
     int vec_ok) {   // bit 0: the shs / dL_dshs rows are 16-byte aligned, bit 1: the rotations are (else: the same widths at dword alignment / per word)
-    // a fixed, moderate grid walks the list with a grid stride: the list's length is only known on the device, and a grid
-    // sized for P would be 23 k blocks of which a few hundred find work
-    const uint32_t n_touched = *g.touched_count;
-    for (uint32_t slot = blockIdx.x * (uint32_t)kSparseBlock + threadIdx.x; slot < n_touched; slot += gridDim.x * (uint32_t)kSparseBlock) {
-    const int i = (int)g.touched_list[slot];
+    static_assert(FLAGS % 1024 == 0 && FLAGS <= 4096, "16-byte flag words per lane, one 64-bit mask per lane");
+    constexpr int kPer = FLAGS / kSparseBlock, kVec = kPer / 16;
+    __shared__ uint32_t s_list[FLAGS];
+    const int lane = threadIdx.x;
+    const int first = blockIdx.x * FLAGS + lane * kPer;        // < P + FLAGS: the grid covers P
+    uint4 w[kVec];
+#pragma unroll
+    for (int v = 0; v < kVec; ++v)          // the flag array is padded to 256 bytes and zeroed in 16-byte units: whole words below P
+        w[v] = first + 16 * v < f.P ? *reinterpret_cast<const uint4*>(g.touched + first + 16 * v) : make_uint4(0u, 0u, 0u, 0u);
+    unsigned long long mask = 0ull;         // bit b: flag first + b is set (and below P)
+#pragma unroll
+    for (int v = 0; v < kVec; ++v) {
+        const uint32_t ww[4] = {w[v].x, w[v].y, w[v].z, w[v].w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (((ww[q] >> (8 * k)) & 0xFFu) && first + 16 * v + 4 * q + k < f.P) mask |= 1ull << (16 * v + 4 * q + k);
+    }
+    const uint32_t mine = (uint32_t)__popcll(mask);
+    const uint32_t incl = wave_incl_scan(mine, lane);
+    const uint32_t n_touched = (uint32_t)__shfl((int)incl, 63);   // <= FLAGS
+    if (n_touched == 0) return;                                 // uniform
+    for (uint32_t dst = incl - mine; mask; mask &= mask - 1ull) s_list[dst++] = (uint32_t)(first + __builtin_ctzll(mask));
+    __syncthreads();
+    for (uint32_t slot = lane; slot < n_touched; slot += kSparseBlock) {
+    const int i = (int)s_list[slot];
     const size_t si = (size_t)i;
     float gr[9];
     {
@@ -620,10 +667,26 @@ __global__ __launch_bounds__(kSparseBlock) void preprocess_backward_sparse_kerne
         gr[0] = a.x; gr[1] = a.y; gr[2] = a.z; gr[3] = a.w; gr[4] = b4.x; gr[5] = b4.y; gr[6] = b4.z; gr[7] = b4.w;
         gr[8] = grad_rows[si * kGradRow + 8];
     }
-    const float4 ca = g.cov_a[i];
-    const float2 cb = g.cov_b[i];
+    // the covariance inputs, requested with the row: cov3D itself (the caller's), or rotation and scale, which give the
+    // forward's cov3D again and feed backward_scale_rot below (one load of each)
+    float c6[6];
+    float4 qrot = make_float4(1.f, 0.f, 0.f, 0.f);
+    float sa_in[3] = {0.f, 0.f, 0.f};
+    if (cov3D_precomp) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) c6[k] = cov3D_precomp[6 * si + k];
+    } else {
+        qrot = (vec_ok & 2) ? *reinterpret_cast<const float4*>(rotations + 4 * si)
+                            : make_float4(rotations[4 * si], rotations[4 * si + 1], rotations[4 * si + 2], rotations[4 * si + 3]);
+        sa_in[0] = scales[3 * si]; sa_in[1] = scales[3 * si + 1]; sa_in[2] = scales[3 * si + 2];
+    }
     const uint32_t cl = shs ? g.clamped[i] : 0u;
     const float px = means3D[3 * si], py = means3D[3 * si + 1], pz = means3D[3 * si + 2];
+    float nq = 1.0f;
+    if (!cov3D_precomp) {
+        if (f.raw) nq = quat_normalize(qrot);
+        cov3d_from_scale_rot(f, qrot, sa_in, c6);
+    }
     dL_dmeans2D[3 * si] = gr[0];
     dL_dmeans2D[3 * si + 1] = gr[1];
     {
@@ -638,7 +701,7 @@ __global__ __launch_bounds__(kSparseBlock) void preprocess_backward_sparse_kerne
     }
     float dm[3] = {0, 0, 0};
     float g6[6] = {0, 0, 0, 0, 0, 0};
-    backward_cov_and_mean(f, px, py, pz, gr, ca, cb, dm, g6);
+    backward_cov_and_mean(f, px, py, pz, gr, c6, dm, g6);
     if (shs) {
         const int M = f.M, nb = (f.deg + 1) * (f.deg + 1);
         float ox = px - f.campos[0], oy = py - f.campos[1], oz = pz - f.campos[2];
@@ -747,45 +810,12 @@ __global__ __launch_bounds__(kSparseBlock) void preprocess_backward_sparse_kerne
 #pragma unroll
         for (int k = 0; k < 6; ++k) dL_dcov3D[6 * si + k] = g6[k];
     } else {
-        const float4 qrot = (vec_ok & 2) ? *reinterpret_cast<const float4*>(rotations + 4 * si)
-                                         : make_float4(rotations[4 * si], rotations[4 * si + 1], rotations[4 * si + 2], rotations[4 * si + 3]);
-        const float sa_in[3] = {scales[3 * si], scales[3 * si + 1], scales[3 * si + 2]};
         float ds[3] = {0, 0, 0}, dq[4] = {0, 0, 0, 0};
-        backward_scale_rot(f, g6, qrot, sa_in, ds, dq);
+        backward_scale_rot(f, g6, qrot, nq, sa_in, ds, dq);
         dL_dscales[3 * si] = ds[0]; dL_dscales[3 * si + 1] = ds[1]; dL_dscales[3 * si + 2] = ds[2];
         dL_drots[4 * si] = dq[0]; dL_drots[4 * si + 1] = dq[1]; dL_drots[4 * si + 2] = dq[2]; dL_drots[4 * si + 3] = dq[3];
     }
-    }   // grid-stride loop over the touched list
-}
-
-// touched flags -> compact list of Gaussian indices (any order) + their number: the chain rule then runs full waves.
-// 16 flags per thread, 16384 per block, ONE returning atomic per block: a returning atomic on a single word completes at
-// ~88 per microsecond on this chip (MI355X_MICROARCH.md, dequeue), so one per wave of a 1.5 M-flag pass cost 67 us.
-constexpr int kCompactThreads = 1024, kCompactPer = 16;
-__global__ __launch_bounds__(kCompactThreads) void compact_touched_kernel(int P, const uint8_t* __restrict__ touched,
-                                                                         uint32_t* __restrict__ list, uint32_t* __restrict__ count) {
-    __shared__ uint32_t s_wave[kCompactThreads / 64];
-    __shared__ uint32_t s_base;
-    const int tid = threadIdx.x;
-    const int i0 = (blockIdx.x * kCompactThreads + tid) * kCompactPer;
-    uint4 w = make_uint4(0u, 0u, 0u, 0u);
-    if (i0 < P) w = *reinterpret_cast<const uint4*>(touched + i0);      // bytes past P are padding of the segment, never set
-    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
-    uint32_t mine = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        mine += ((ww[q] & 0xFFu) != 0) + ((ww[q] & 0xFF00u) != 0) + ((ww[q] & 0xFF0000u) != 0) + ((ww[q] >> 24) != 0);
-    uint32_t total;
-    const uint32_t off = block_excl_scan<kCompactThreads / 64>(mine, tid, s_wave, &total);
-    if (total == 0) return;
-    if (tid == 0) s_base = atomicAdd(count, total);
-    __syncthreads();
-    uint32_t dst = s_base + off;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (((ww[q] >> (8 * k)) & 0xFFu) && i0 + 4 * q + k < P) list[dst++] = (uint32_t)(i0 + 4 * q + k);
+    }   // rounds of 64 over the block's touched Gaussians
 }
 
 int launch_preprocess_backward_sparse(const Frame& f, const float* means3D, const float* shs, const float* scales,
@@ -794,15 +824,12 @@ int launch_preprocess_backward_sparse(const Frame& f, const float* means3D, cons
                                       float* dL_dshs, float* dL_dcov3D, float* dL_dscales, float* dL_drots, hipStream_t st,
                                       RawBackwardExtra rawx) {
     if (f.P <= 0) return 0;
-    constexpr int kPerBlock = kCompactThreads * kCompactPer;
-    hipLaunchKernelGGL(compact_touched_kernel, dim3((f.P + kPerBlock - 1) / kPerBlock), dim3(kCompactThreads), 0, st, f.P, g.touched,
-                       g.touched_list, g.touched_count);
-    const int sparse_blocks = min((f.P + kSparseBlock - 1) / kSparseBlock, 2048);
+    const int sparse_blocks = (f.P + kSparseFlags - 1) / kSparseFlags;
     // the caller's arrays may sit at any 4-byte offset (e.g. inside dist.GradBucket, where dL_dshs starts 12 P bytes in):
     // the 16-byte row accesses are taken only when every row is 16-byte aligned, else the per-word form
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
     const int vec_ok = ((al16(shs) && al16(dL_dshs)) ? 1 : 0) | (al16(rotations) ? 2 : 0);
-    hipLaunchKernelGGL(preprocess_backward_sparse_kernel, dim3(sparse_blocks), dim3(kSparseBlock), 0, st, f, means3D, shs, scales,
+    hipLaunchKernelGGL(preprocess_backward_sparse_kernel<kSparseFlags>, dim3(sparse_blocks), dim3(kSparseBlock), 0, st, f, means3D, shs, scales,
                        rotations, cov3D_precomp, g, grad_rows, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dcolors, dL_dshs,
                        dL_dcov3D, dL_dscales, dL_drots, rawx, vec_ok);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
@@ -911,13 +938,56 @@ __global__ __launch_bounds__(256) void resolve_colors_kernel(Frame f, GeomView g
     const ColorSource cs = *g.color_src;
     if (!cs.deferred) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= f.P || g.tiles_touched[i] == 0) return;
+    if (i >= f.P) return;
+    const uint32_t wh = g.rect[i].y;                      // w | h << 16: the area is 0 for a culled Gaussian
+    if ((wh & 0xFFFFu) * (wh >> 16) == 0) return;
     const float4 cd = g.rgbd[i];
     if (color_pending(cd)) resolve_color(cs, f.campos, (uint32_t)i, cd.w, g.rgbd, g.clamped);
 }
 int launch_resolve_colors(const Frame& f, GeomView g, hipStream_t st) {
     if (f.P <= 0) return 0;
     hipLaunchKernelGGL(resolve_colors_kernel, dim3((f.P + 255) / 256), dim3(256), 0, st, f, g);
+    return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
+}
+
+// The views of mvi_raster_views that no kernel reads and the forward therefore does not write (depths, cov3D_a / cov3D_b, and
+// under binning version 2 tiles_touched), filled for whoever asks (the parity tests) with what the forward would have stored:
+// cov3D for every Gaussian in front of the near plane (the forward's own expressions on the forward's own inputs), the depth
+// of every visible Gaussian (rgbd.w), the area of every tile rectangle. Whether the inputs are raw parameters is read from the
+// record the forward left in the scratch (ColorSource).
+__global__ __launch_bounds__(256) void materialize_geom_views_kernel(Frame f, const float* __restrict__ means3D,
+                                                                     const float* __restrict__ scales,
+                                                                     const float* __restrict__ rotations,
+                                                                     const float* __restrict__ cov3D_precomp,
+                                                                     const int32_t* __restrict__ radii, GeomView g) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= f.P) return;
+    const size_t si = (size_t)i;
+    f.raw = g.color_src->raw;
+    const uint32_t wh = g.rect[i].y;
+    g.tiles_touched[i] = (wh & 0xFFFFu) * (wh >> 16);
+    if (radii[i] > 0) g.depths[i] = g.rgbd[i].w;
+    const float vz = affine3(f.view[2], f.view[6], f.view[10], f.view[14], means3D[3 * si], means3D[3 * si + 1], means3D[3 * si + 2]);
+    if (vz <= kNearZ) return;
+    float c6[6];
+    if (cov3D_precomp) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) c6[k] = cov3D_precomp[6 * si + k];
+    } else {
+        float4 q = make_float4(rotations[4 * si], rotations[4 * si + 1], rotations[4 * si + 2], rotations[4 * si + 3]);
+        if (f.raw) quat_normalize(q);
+        const float sa_in[3] = {scales[3 * si], scales[3 * si + 1], scales[3 * si + 2]};
+        cov3d_from_scale_rot(f, q, sa_in, c6);
+    }
+    g.cov_a[i] = make_float4(c6[0], c6[1], c6[2], c6[3]);
+    g.cov_b[i] = make_float2(c6[4], c6[5]);
+}
+int launch_materialize_geom_views(const Frame& f, const float* means3D, const float* scales, const float* rotations,
+                                  const float* cov3D_precomp, const int32_t* radii, GeomView g, hipStream_t st) {
+    if (f.P <= 0) return 0;
+    hipLaunchKernelGGL(materialize_geom_views_kernel, dim3((f.P + 255) / 256), dim3(256), 0, st, f, means3D, scales, rotations,
+                       cov3D_precomp, radii, g);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 

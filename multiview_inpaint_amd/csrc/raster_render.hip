@@ -261,7 +261,6 @@ int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView i
         z.add(zero_rows, (size_t)f.P * kGradRow);
         z.add(g.touched, ((size_t)f.P + 15) / 16 * 4);           // bytes, rounded up to the 16 the compaction reads at once
                                                                   // (inside the scratch segment's 256-byte padding)
-        z.add(g.touched_count, 1);
     }
     if (f.W <= 0 || f.H <= 0) return launch_zero_regions(z, st);
     const uint32_t* plist = b.vals[b.passes & 1];

@@ -64,7 +64,23 @@ class _Frame:
 
 class RasterState:
     """Scratch buffers one forward leaves behind for its backward (and for the parity tests)."""
-    __slots__ = ("P", "M", "D", "W", "H", "geom", "binning", "image", "radii", "grad_rows", "rows_clean", "frame", "sources")
+    __slots__ = ("P", "M", "D", "W", "H", "geom", "binning", "image", "radii", "grad_rows", "rows_clean", "frame", "sources",
+                 "cov_sources")
+    # views no kernel reads: the forward leaves them unwritten and tensor() has them filled on demand
+    ON_DEMAND_GEOM_VIEWS = ("depths", "cov3D_a", "cov3D_b", "tiles_touched")
+
+    def materialize_geom_views(self):
+        """Fills the `depths`, `cov3D_a`, `cov3D_b` and `tiles_touched` views from the forward's inputs (kept alive in
+        `sources` / `cov_sources`: means3D, then scales, rotations, cov3D_precomp). Tests and introspection only."""
+        if self.P == 0:
+            return
+        dev = self.geom.device
+        scales, rotations, cov3D_precomp = self.cov_sources
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mvi_raster_materialize_geom_views(
+                C.byref(self.frame.c), self.P, _ptr(self.sources[0]), _ptr(scales), _ptr(rotations), _ptr(cov3D_precomp),
+                _ptr(self.radii), _ptr(self.geom), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                "materialize_geom_views")
 
     def resolve_colors(self):
         """Evaluates the SH colours no tile needed (deferred colours, include/mvi_raster.h: mvi_raster_color_mode), so that
@@ -97,6 +113,8 @@ class RasterState:
         """Copy of one intermediate array as a torch tensor (tests only)."""
         v = self.views()
         addr = getattr(v, name)
+        if _derive and name in self.ON_DEMAND_GEOM_VIEWS:
+            self.materialize_geom_views()
         if _derive and name == "tile_ids_sorted" and self.D > 0 and self.binning is not None and self.image is not None:
             # the forward leaves the array unwritten (no kernel reads it): derived from the tile ranges here
             dev = self.binning.device
@@ -152,6 +170,7 @@ def rasterize_forward(rs: GaussianRasterizationSettings, means3D, opacities, shs
     st = RasterState()
     st.P, st.M, st.W, st.H = P, M, W, H
     st.frame, st.sources = fr, (means3D, shs)        # deferred SH colours read these until the render kernel has run
+    st.cov_sources = (scales, rotations, cov3D_precomp)
     u8 = dict(dtype=torch.uint8, device=dev)
     st.geom = torch.empty(L.mvi_raster_geom_bytes(P), **u8)
     st.image = torch.empty(L.mvi_raster_image_bytes(W, H), **u8)
@@ -347,6 +366,7 @@ def rasterize_forward_raw(rs: GaussianRasterizationSettings, xyz, features_dc, f
     st = RasterState()
     st.P, st.M, st.W, st.H = P, M, W, H
     st.frame, st.sources = fr, (xyz, features_dc, features_rest)
+    st.cov_sources = (raw_scaling, raw_rotation, None)
     u8 = dict(dtype=torch.uint8, device=dev)
     st.geom = torch.empty(L.mvi_raster_geom_bytes(P), **u8)
     st.image = torch.empty(L.mvi_raster_image_bytes(W, H), **u8)
