@@ -272,6 +272,20 @@ int mvi_conv3t_n320(const void* x, const void* weight, const float* bias, void* 
                     int32_t C_out, int64_t out_rows_capacity, int64_t out_row_stride, int32_t dtype, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* Weight gradient of that (3, 1, 1) / padding (1, 0, 0) frame convolution (training: csrc/conv3t_wgrad.hip):
+ *     dweight[co][ci][kt] = sum over (b, t, p) of dy[b, t, p, co] * x[b, t + kt - 1, p, ci], frames outside [0, T) 0.
+ * x [B T, pixels, C_in] and dy [B T, pixels, C_out] token-major with the T frames of a video consecutive, in one 16-bit dtype,
+ * contiguous, 16-byte aligned; dweight fp32 in the module's own [C_out, C_in, 3] (= [C_out, C_in, 3, 1, 1]) order, every element
+ * written once (B = 0: zeros). C_in and C_out multiples of 64, bf16 / f16 (fp32 is declined with the invalid-argument status); any
+ * T >= 1 and pixels >= 1. No atomics: where the output tiles alone would not fill the chip the (video, 64-pixel chunk) units are split
+ * over blocks — a pure function of the shape —, fp32 partials go to `workspace` (..._workspace_bytes(); 0 = this shape is not split)
+ * and a second launch adds them in a fixed order. workspace NULL or too small: the unsplit launch. Two runs give the same bits. The
+ * input gradient needs no kernel of its own: it is mvi_conv3t_n320 of dy with the weight W'[ci][co][kt] = W[co][ci][2 - kt]. */
+int mvi_conv3t_wgrad_supported(int32_t C_in, int32_t C_out, int32_t dtype);
+size_t mvi_conv3t_wgrad_workspace_bytes(int64_t B, int32_t T, int32_t pixels, int32_t C_in, int32_t C_out);
+int mvi_conv3t_wgrad(const void* x, const void* dy, float* dweight, int64_t B, int32_t T, int32_t pixels, int32_t C_in, int32_t C_out,
+                     int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* y = act(conv2d(x, weight, padding = 1) + bias) for a 3x3, stride-1 convolution with 16 output channels and at most 16 input
  * channels, 32 and at most 32, or 320 and at most 8 (the networks' input convolution), on NCHW bf16 / f16 tensors (csrc/stem_conv.hip) — the stride-1 layers of ControlNet.input_hint_block
  * at its two finest resolutions

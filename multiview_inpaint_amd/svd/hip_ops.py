@@ -819,16 +819,65 @@ def conv3x3_wgrad(tok, dy_tok, H, W, split=True):
     return dw
 
 
-def conv3t_n320(tok, weight_taps, bias, T, split=True, gn=None):
+def conv3t_n320(tok, weight_taps, bias, T, split=True, gn=None, kind="conv3t_n320"):
     """(3, 1, 1) / padding (1, 0, 0) convolution over the frame axis of token-major activations tok [(b T), S, C_in] (frames of a video
-    consecutive) -> [(b T), S, C_out]; weight_taps from conv3t_n320_weight. gn: as conv3x3_n320 (a sample = a frame)."""
+    consecutive) -> [(b T), S, C_out]; weight_taps from conv3t_n320_weight. gn: as conv3x3_n320 (a sample = a frame).
+    kind: the PROFILE kind of the launch ("conv3t_dgrad" when it computes an input gradient, conv3t_dgrad below)."""
     BT, S, C = tok.shape
     if BT % T:
         raise ValueError("conv3t_n320: tok [(b T), S, C_in] expected")
-    r = _conv_taps_n320("conv3t_n320", tok, weight_taps, bias, BT // T, T, S, 3, 1, split, gn=gn)
+    r = _conv_taps_n320(kind, tok, weight_taps, bias, BT // T, T, S, 3, 1, split, gn=gn)
     if gn is not None:
         return r[0].view(BT, S, -1), r[1]
     return r.view(BT, S, -1)
+
+
+# ---- the (3,1,1) frame convolution under autograd (ops._Conv3tTokensFn): dgrad on the forward kernel, wgrad in csrc/conv3t_wgrad.hip ----
+
+CONV3T_WGRAD_CHUNK = 64                         # csrc/conv3t_wgrad.hip (kKc): pixels of one video a block stages per frame
+
+
+def conv3t_transposed_weight(weight):
+    """The weight whose (3, 1, 1) / padding (1, 0, 0) convolution of dy is the input gradient of conv(x, weight):
+    W'[ci, co, kt] = W[co, ci, 2 - kt], as a view [C_in, C_out, 3, 1, 1]. Pure torch; loads no library."""
+    return weight.flip(2).transpose(0, 1)
+
+
+def conv3t_dgrad(dy_tok, weight_t_taps, T, split=True):
+    """dx [(b T), S, C_in] of the frame convolution from dy [(b T), S, C_out]: the forward kernel on the packed transposed weight
+    (conv3t_n320_weight(conv3t_transposed_weight(weight))), channel roles swapped. PROFILE kind conv3t_dgrad."""
+    return conv3t_n320(dy_tok, weight_t_taps, None, T, split=split, kind="conv3t_dgrad")
+
+
+def conv3t_wgrad_supported(C_in, C_out, dtype):
+    return dtype in (torch.bfloat16, torch.float16) and bool(_lib.lib().mvi_conv3t_wgrad_supported(int(C_in), int(C_out), _DT[dtype]))
+
+
+def conv3t_wgrad_workspace_bytes(B, T, S, C_in, C_out):
+    """> 0: csrc/conv3t_wgrad.hip splits the (video, pixel chunk) units of this shape over blocks (a pure host function of the shape)."""
+    return int(_lib.lib().mvi_conv3t_wgrad_workspace_bytes(int(B), int(T), int(S), int(C_in), int(C_out)))
+
+
+def conv3t_wgrad(tok, dy_tok, T, split=True):
+    """dweight, fp32 [C_out, C_in, 3, 1, 1], of the (3, 1, 1) / padding (1, 0, 0) frame convolution from its input tok [(b T), S, C_in]
+    and the output gradient dy_tok [(b T), S, C_out] (one 16-bit dtype): csrc/conv3t_wgrad.hip, deterministic. split = False withholds
+    the workspace (the unsplit launch). PROFILE kind conv3t_wgrad."""
+    L = _lib.lib()
+    T = int(T)
+    if tok.dim() != 3 or dy_tok.dim() != 3 or tok.shape[:2] != dy_tok.shape[:2] or tok.dtype != dy_tok.dtype or T < 1 or tok.shape[0] % T:
+        raise ValueError("conv3t_wgrad: tok [(b T), S, C_in] and dy_tok [(b T), S, C_out] of one dtype expected")
+    BT, S, C = tok.shape
+    B = BT // T
+    Co = dy_tok.shape[2]
+    xc = tok if tok.is_contiguous() and tok.data_ptr() % 16 == 0 else tok.contiguous().clone()
+    dc = dy_tok if dy_tok.is_contiguous() and dy_tok.data_ptr() % 16 == 0 else dy_tok.contiguous().clone()
+    dw = torch.empty(Co, C, 3, 1, 1, dtype=torch.float32, device=tok.device)
+    ws_bytes = int(L.mvi_conv3t_wgrad_workspace_bytes(B, T, S, C, Co)) if split else 0
+    ws = _workspace(tok.device, ws_bytes) if ws_bytes else None
+    with torch.cuda.device(tok.device), _Timed("conv3t_wgrad", 2.0 * BT * S * 3 * C * Co, tok.device):
+        _check(L.mvi_conv3t_wgrad(xc.data_ptr(), dc.data_ptr(), dw.data_ptr(), B, T, S, C, Co, _DT.get(tok.dtype, -1), _ptr(ws), ws_bytes,
+                                  _stream(tok.device)), "conv3t_wgrad")
+    return dw
 
 
 def stem_conv3x3_supported(conv, x):

@@ -680,6 +680,12 @@ def _nhwc_path_ok(self, x):
 RESBLOCK_CONV_BWD = os.environ.get("MVI_RESBLOCK_CONV_BWD", "0") == "1"
 
 
+# The temporal ResBlock under autograd on tokens, its two (3,1,1) convolutions on ops.conv3t_tokens (MVI_TIME_STACK_CONV_BWD=1, or
+# layers.TIME_STACK_CONV_BWD = True; VideoResBlock._time_stack_tokens_autograd). Off by default — a tested opt-in
+# (tests/test_conv3t_bwd_gpu.py); ops.conv3t_backward_pays routes nothing yet (no class won tools/bench_conv3t_bwd.py), so neither does this.
+TIME_STACK_CONV_BWD = os.environ.get("MVI_TIME_STACK_CONV_BWD", "0") == "1"
+
+
 def _conv_bwd_path_ok(self, x, emb):
     """Under autograd: do both convolutions of this block pass ops.conv3x3_tokens' conditions (switches, the three kernels' gates, the
     speed decision)?"""
@@ -813,6 +819,46 @@ class VideoResBlock(ResBlock):
             return ops.bias_residual_blend(h, c2.bias, x, blend)
         return ops.bias_residual_add(h, c2.bias, x)
 
+    def _time_stack_conv_bwd_ok(self, x, emb, T):
+        """Under autograd with TIME_STACK_CONV_BWD on: do both frame convolutions pass ops.conv3t_tokens' conditions (switch, the three
+        kernels' gates, the speed decision) and the norms' token-major geometry?"""
+        if not (TIME_STACK_CONV_BWD and ops.CONV3T_BACKWARD and torch.is_grad_enabled() and x.is_cuda and x.dim() == 4
+                and x.dtype in (torch.bfloat16, torch.float16) and x.shape[0] % T == 0 and self._frames_path_ok()):
+            return False
+        ts = self.time_stack
+        g0, g1 = ts.in_layers[0], ts.out_layers[0]
+        c1, c2 = ts.in_layers[2], ts.out_layers[3]
+        if not (c1.weight.dtype == x.dtype and c2.weight.dtype == x.dtype and c1.in_channels == x.shape[1] and c1.groups == 1 and c2.groups == 1):
+            return False
+        if not (x.requires_grad or emb.requires_grad or any(p.requires_grad for p in ts.parameters())):
+            return False
+        bt, c, h, w = x.shape
+        return (_tok2tok_ok(bt, c, h * w, g0.num_groups, x.dtype) and _tok2tok_ok(bt, c1.out_channels, h * w, g1.num_groups, x.dtype)
+                and all(ops.conv3t_tokens_gates(bt // T, T, h * w, ci, cv.out_channels, x.dtype)
+                        and ops.conv3t_backward_pays(bt // T, T, h * w, ci, cv.out_channels, x.dtype, cv.weight.requires_grad)
+                        for cv, ci in ((c1, c), (c2, c1.out_channels))))
+
+    def _time_stack_tokens_autograd(self, x, emb, T, blend=None):
+        """_time_stack_frames under autograd on tokens (TIME_STACK_CONV_BWD): a plain permute copy to [(b T), S, c], the temporal norms
+        token-major on both sides (ops.group_norm_tok2tok chooses between its HIP Function and its differentiable fallback), the two
+        frame convolutions on ops.conv3t_tokens (HIP forward, dgrad and wgrad), a plain copy back, the same differentiable tail. No
+        channel-stacked 3 c tensor, forward or backward."""
+        ts = self.time_stack
+        g0, g1 = ts.in_layers[0], ts.out_layers[0]
+        c1, c2 = ts.in_layers[2], ts.out_layers[3]
+        bt, c, hh, ww = x.shape
+        xt = x.flatten(2).transpose(1, 2).contiguous()
+        h = ops.group_norm_tok2tok(xt, g0.num_groups, g0.weight, g0.bias, g0.eps, silu=True, frames=T)
+        h = ops.conv3t_tokens(h, c1.weight, T)
+        e = _emb_chan_bias(ts.emb_layers, emb, c1)                 # [(b T), c] fp32 incl. the first convolution's bias
+        e = e if e.is_contiguous() else e.contiguous()
+        h = ops.group_norm_tok2tok(h, g1.num_groups, g1.weight, g1.bias, g1.eps, silu=True, chan_bias=e, frames=T)
+        h = ops.conv3t_tokens(ts.out_layers[2](h), c2.weight, T)
+        h = h.transpose(1, 2).reshape(bt, c2.out_channels, hh, ww).contiguous()
+        if blend is not None:
+            return ops.bias_residual_blend(h, c2.bias, x, blend)
+        return ops.bias_residual_add(h, c2.bias, x)
+
     def _tokens_path_ok(self, x, t):
         """The whole block on tokens (spatial ResBlock ending token-major, temporal ResBlock on tokens with the (3,1,1) convolutions
         in csrc/linear_n320.hip, b c h w restored by the blending tail): the channels-last route of the spatial block must apply, the
@@ -906,12 +952,14 @@ class VideoResBlock(ResBlock):
         x = super().forward(x, emb)
         bt, c, h, w = x.shape
         if self._frames_path_ok():
+            # (opt-in, under autograd: the temporal block on tokens with the HIP backward of its frame convolutions)
+            time_stack = self._time_stack_tokens_autograd if self._time_stack_conv_bwd_ok(x, emb, t) else self._time_stack_frames
             a = self.time_mixer.get_alpha(image_only_indicator)           # [b, 1, t, 1, 1] (or a scalar)
             if a.ndim == 5:
                 if a.size(0) != bt // t:
                     a = self.time_mixer.get_alpha(image_only_indicator, rows=bt // t)   # CFG-doubled batch (util.py:365-367)
-                return self._time_stack_frames(x, emb, t, blend=a.reshape(bt))    # (b, t) order = frame-major rows
-            xt = self._time_stack_frames(x, emb, t)
+                return time_stack(x, emb, t, blend=a.reshape(bt))    # (b, t) order = frame-major rows
+            xt = time_stack(x, emb, t)
             return torch.lerp(xt, x, a.to(x.dtype))
         xs = x.reshape(bt // t, t, c, h, w).transpose(1, 2)          # b c t h w (view)
         xt = self.time_stack(xs, emb.reshape(bt // t, t, *emb.shape[1:]))

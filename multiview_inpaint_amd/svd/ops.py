@@ -14,9 +14,11 @@ LayerNorm of the transformer blocks (csrc/layernorm_bwd.hip: `add_layer_norm` fo
 `add_layer_norm_backward_pays` says so).
 The 3x3 convolution of token-major activations has a HIP backward too (`conv3x3_tokens`: the input gradient on the forward's
 implicit-GEMM kernel with the transposed weight, the weight gradient on csrc/conv3x3_wgrad.hip), where `conv3x3_backward_pays` says
-so; the ResBlock reaches it through the opt-in layers.RESBLOCK_CONV_BWD.
+so; the ResBlock reaches it through the opt-in layers.RESBLOCK_CONV_BWD. So has the (3,1,1) frame convolution of the temporal
+ResBlocks (`conv3t_tokens`: the same kernel's three-tap form for forward and input gradient, csrc/conv3t_wgrad.hip for the weight
+gradient), where `conv3t_backward_pays` says so; VideoResBlock reaches it through the opt-in layers.TIME_STACK_CONV_BWD.
 Every other kernel is forward-only: a GPU tensor that requires grad goes through PyTorch-ROCm's differentiable ops there
-(the projections, the strided, upsampling and frame convolutions — `linear_add_layer_norm` under grad is `linear_module` +
+(the projections, the strided and upsampling convolutions — `linear_add_layer_norm` under grad is `linear_module` +
 `add_layer_norm` —, `add_lerp`).
 
 Reference ops: GroupNorm32 + SiLU (sgm/modules/diffusionmodules/util.py:259-276,
@@ -952,3 +954,120 @@ def conv3x3_tokens(tok, weight, H, W):
     x = tok.view(N, H, W, C).permute(0, 3, 1, 2)                  # [N, C, H, W] with channels-last strides: no copy
     y = F.conv2d(x, weight, None, 1, 1)
     return y.permute(0, 2, 3, 1).reshape(N, S, Co)
+
+
+# The (3, 1, 1) / padding (1, 0, 0) frame convolution of token-major activations under autograd (VideoResBlock.time_stack): forward and
+# input gradient on csrc/linear_n320.hip's three-tap implicit GEMM, weight gradient on csrc/conv3t_wgrad.hip. MVI_CONV3T_BWD=0 (or
+# ops.CONV3T_BACKWARD = False): a frame convolution that requires grad takes PyTorch-ROCm's F.conv3d again.
+CONV3T_BACKWARD = os.environ.get("MVI_CONV3T_BWD", "1") != "0"
+CONV3T_MIN_BLOCKS = 128                  # the forward's fill-the-chip line (layers.CONV_N320_MIN_BLOCKS)
+CONV3T_BACKWARD_MIN_ROWS = None          # None: no measured class won (profiles/conv3t_bwd_bench.json), nothing is routed by default
+
+
+def conv3t_backward_pays(B, T, S, C_in, C_out, dtype, need_dweight):
+    """Whether forward + backward on the HIP kernels is faster than the channel-stacked 1x1 library convolution under autograd
+    (layers.temporal_conv3_stacked, what the training path runs today) for this shape class — the routing's second question after
+    conv3t_tokens_gates. Measured by tools/bench_conv3t_bwd.py (profiles/conv3t_bwd_bench.json; DESIGN.md '(3,1,1) frame convolution
+    under autograd'): forward + backward by device events, the two routes alternating in one process, 9 pairs, medians; a class goes to
+    HIP only where its median beats the PyTorch route's by more than that route's spread. ms HIP / PyTorch (spread), dx only | all
+    gradients, (B, T) = (1, 14), C -> C, the PyTorch side on an already stacked input (its stack's cost left out):
+      bf16  S 3072  C  320   0.235 / 0.188 (0.023) | 0.366 / 0.395 (0.029)    loses | inside the spread
+      bf16  S  768  C  640   0.255 / 0.186 (0.029) | 0.373 / 0.368 (0.051)    loses | loses
+      bf16  S  192  C 1280   0.248 / 0.184 (0.017) | 0.372 / 0.379 (0.030)    loses | inside the spread
+      bf16  S   48  C 1280   0.250 / 0.173 (0.019) | 0.334 / 0.329 (0.018)    loses | loses
+      f16   S 3072  C  320   0.235 / 0.192 (0.018) | 0.381 / 0.403 (0.032)    loses | inside the spread
+      f16   S  768  C  640   0.255 / 0.182 (0.016) | 0.377 / 0.338 (0.080)    loses | loses
+      f16   S  192  C 1280   0.252 / 0.186 (0.020) | 0.367 / 0.330 (0.021)    loses | loses
+      f16   S   48  C 1280   0.251 / 0.174 (0.020) | 0.332 / 0.322 (0.029)    loses | loses
+    No class won: the HIP route's forward + input gradient cost 0.24 - 0.26 ms whatever the shape (two launches of the forward kernel
+    whose own work is far shorter: the time is the host's), the library's 0.17 - 0.19; the weight-gradient kernel (0.030 - 0.094 ms)
+    takes 0.03 - 0.08 ms less of the step than the library's and does not make up for it by more than the spread. So the line is None and every
+    shape stays on the route it had; the tests lift the decision. One run on one machine."""
+    line = CONV3T_BACKWARD_MIN_ROWS
+    return line is not None and B * T * S >= line
+
+
+def conv3t_tokens_gates(B, T, S, C_in, C_out, dtype):
+    """Do the three launches of _Conv3tTokensFn take this shape? The forward's conditions (layers.VideoResBlock._tokens_path_ok: the
+    kernel's channel gate, 32-bit byte offsets, enough blocks or a K split), the same with the channel roles swapped for the input
+    gradient, and csrc/conv3t_wgrad.hip's gate."""
+    from . import hip_ops
+    rows = B * T * S
+    return (dtype in (torch.bfloat16, torch.float16) and rows > 0
+            and hip_ops.conv3x3_n320_supported(C_in, C_out, dtype) and hip_ops.conv3x3_n320_supported(C_out, C_in, dtype)
+            and rows * max(C_in, C_out) * 2 < 2 ** 32
+            and hip_ops.conv3t_n320_fills_chip(B, T, S, C_in, C_out, CONV3T_MIN_BLOCKS)
+            and hip_ops.conv3t_n320_fills_chip(B, T, S, C_out, C_in, CONV3T_MIN_BLOCKS)
+            and hip_ops.conv3t_wgrad_supported(C_in, C_out, dtype))
+
+
+def _conv3t_packed(weight):
+    """The weight in the forward kernel's order, once per parameter version (the entry layers._tap_major_weight keeps)."""
+    from . import hip_ops
+    from .derived import derived1
+    return derived1("tap_major", weight, lambda w: hip_ops.conv3t_n320_weight(w.detach()))
+
+
+def _conv3t_packed_transposed(weight):
+    """The transposed weight of the input gradient in the forward kernel's order: kept in svd/derived.py's table while the weight is
+    frozen, built from the live tensor while it trains (it changes every step)."""
+    from . import hip_ops
+    from .derived import derived1
+
+    def build(w):
+        return hip_ops.conv3t_n320_weight(hip_ops.conv3t_transposed_weight(w.detach()))
+    if weight.requires_grad:
+        return build(weight)
+    return derived1("tap_major_transposed", weight, build)
+
+
+class _Conv3tTokensFn(torch.autograd.Function):
+    """conv3t_tokens on the three-tap implicit-GEMM kernel with a deterministic HIP backward: dx is the same kernel on the transposed
+    weight (W'[ci, co, kt] = W[co, ci, 2 - kt]), dweight is csrc/conv3t_wgrad.hip. No bias (the blocks fold it elsewhere). Holds tok and
+    weight only; nothing is cached outside ctx, so torch.utils.checkpoint may re-run the forward."""
+
+    @staticmethod
+    def forward(ctx, tok, weight, T):
+        from . import hip_ops
+        ctx.save_for_backward(tok, weight)
+        ctx.frames = T
+        return hip_ops.conv3t_n320(tok, _conv3t_packed(weight), None, T)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        tok, weight = ctx.saved_tensors
+        T = ctx.frames
+        n = ctx.needs_input_grad
+        dy = dy if dy.is_contiguous() else dy.contiguous()
+        dx = hip_ops.conv3t_dgrad(dy, _conv3t_packed_transposed(weight), T) if n[0] else None
+        dw = hip_ops.conv3t_wgrad(tok, dy, T).to(weight.dtype) if n[1] else None
+        return dx, dw, None
+
+
+def conv3t_tokens(tok, weight, T):
+    """(3, 1, 1) / padding (1, 0, 0) convolution over the frame axis of token-major activations tok [(b T), S, C_in] (the T frames of a
+    video consecutive) with weight [C_out, C_in, 3, 1, 1], no bias -> [(b T), S, C_out]. Without autograd: the three-tap implicit-GEMM
+    kernel. Under autograd: _Conv3tTokensFn where the switch is on, the three launches take the shape (conv3t_tokens_gates) and
+    conv3t_backward_pays says so; anything else is F.conv3d on the b c t s 1 view (a recorded fallback; strict mode raises) — also the
+    CPU path."""
+    BT, S, C = tok.shape
+    T = int(T)
+    Co = weight.shape[0]
+    if T < 1 or BT % T or tuple(weight.shape[1:]) != (C, 3, 1, 1):
+        raise ValueError("conv3t_tokens: tok [(b T), S, C_in] and weight [C_out, C_in, 3, 1, 1] expected")
+    B = BT // T
+    if tok.is_cuda and tok.dtype == weight.dtype:
+        from . import hip_ops
+        if not _needs_autograd(tok, weight):
+            if (tok.dtype in (torch.bfloat16, torch.float16) and BT * S > 0 and hip_ops.conv3x3_n320_supported(C, Co, tok.dtype)
+                    and BT * S * C * 2 < 2 ** 32 and hip_ops.conv3t_n320_fills_chip(B, T, S, C, Co, CONV3T_MIN_BLOCKS)):
+                return hip_ops.conv3t_n320(tok, _conv3t_packed(weight), None, T)
+        elif CONV3T_BACKWARD and conv3t_tokens_gates(B, T, S, C, Co, tok.dtype) \
+                and conv3t_backward_pays(B, T, S, C, Co, tok.dtype, weight.requires_grad):
+            return _Conv3tTokensFn.apply(tok, weight, T)
+    _fallback(tok, "conv3t_tokens", _why(tok, weight))
+    x = tok.reshape(B, T, S, C).permute(0, 3, 1, 2).unsqueeze(-1)              # b c t s 1 (a view)
+    y = F.conv3d(x, weight, None, 1, (1, 0, 0))
+    return y.squeeze(-1).permute(0, 2, 3, 1).reshape(BT, S, Co)
