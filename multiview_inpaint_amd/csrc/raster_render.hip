@@ -372,15 +372,21 @@ int launch_wave_sum9_probe(const float* in, float* out, int n_waves, hipStream_t
 // W dy^2, alpha T dL/dC); wave totals in registers (wave_sum9), added into the block's per-entry accumulator by nine
 // lanes; per (tile, Gaussian) the block converts raw sums into gradients once and flushes them with float atomics
 // shaped as whole 64-byte rows (grad_rows [P][16]).
-// The kernel sits at the fp32 VALU issue roof. With one pixel per lane it needed ~90 vector
+// The kernel's time is its vector instructions at their issue prices (about 0.65 of that roof: DESIGN.md §8 item 3). With one
+// pixel per lane it needed ~90 vector
 // instructions per (wave, Gaussian), about a third of them (the cross-lane sums) independent of how many pixels the wave
 // covers. Here a wave covers a 16x8 half tile, lane l owning the vertically adjacent pixels (x = l & 15, y = 2 (l >> 4) + {0, 1}):
 // the per-pixel math runs on packed fp32 (v_pk_mul/add/fma_f32: two pixels per instruction at full rate), the two
-// pixels are summed in the lane before the wave reduction, and the reduction cost is paid once per 128 pixels.
+// pixels are summed in the lane before the wave reduction, and the reduction cost is paid once per 128 pixels. The moments
+// are factored: the two pixels are added before they meet dx, which they share (14 vector instructions, one of them packed, where
+// the products per pixel took 18, eight of them packed, and a v_mov for the (dx, dx) pair). On a SIMD that has other waves to issue
+// from, a packed fp32 instruction costs 4.1 cycles against 2.3 for a plain one (tools/experiments/valu_issue_probe.cpp): packed
+// pays only where both halves do work that cannot be shared.
 // Block = 128 threads = one tile; 128 list entries are staged per round. Decisions (alpha, active) use the same
 // operation order as the forward kernel (products rounded, one fma per sum), element-wise.
 // Registers decide the occupancy (LDS: 10.5 KB per block, 12 blocks per CU fit). The entry loop keeps ONE entry in registers,
-// read from LDS at the top of its iteration: 76 VGPRs and no scratch at five AND at six waves per SIMD. Five is the default:
+// read from LDS at the top of its iteration: 67 VGPRs and no scratch at five waves per SIMD (76 before the moments were factored,
+// at five AND at six). Five is the default:
 // on the MI355X six measured the same kernel time and did not pass the keep rule (profiles/render_backward_six_waves_ab.txt).
 #ifndef MVI_RB_WAVES
 #define MVI_RB_WAVES 5             // waves per SIMD the register allocation aims at (A/B builds: -DMVI_RB_WAVES=6)
@@ -497,11 +503,19 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
                 T = Tn;
                 A_dot = pk_fma(am, c_dot, om * A_dot);
                 if (any_active != 0ull) {                       // wave-uniform
-                    const f2 vr = dch * dp0, vg = dch * dp1, vb = dch * dp2;
-                    const f2 vx = mw * dx, vy = mw * dy;
-                    const f2 vxx = vx * dx, vxy = vx * dy, vyy = vy * dy;
-                    float m_w = mw.x + mw.y, m_x = vx.x + vx.y, m_y = vy.x + vy.y, m_xx = vxx.x + vxx.y,
-                          m_xy = vxy.x + vxy.y, m_yy = vyy.x + vyy.y, m_r = vr.x + vr.y, m_g = vg.x + vg.y, m_b = vb.x + vb.y;
+                    // the lane's two pixels share dx: they are added FIRST and what they share is multiplied once (dx never
+                    // meets a pixel's own weight); a sum over the two pixels is one product and one fma (contraction is off:
+                    // the fma is written out). No packed operand but W dy, no (dx, dx) register pair
+                    const float wy0 = mw.x * dy.x, wy1 = mw.y * dy.y;
+                    float m_w = mw.x + mw.y;                                         // W
+                    float m_x = m_w * dx;                                            // W dx
+                    float m_y = wy0 + wy1;                                           // W dy
+                    float m_xx = m_x * dx;                                           // W dx^2
+                    float m_xy = m_y * dx;                                           // W dx dy
+                    float m_yy = __builtin_fmaf(wy1, dy.y, wy0 * dy.x);              // W dy^2
+                    float m_r = __builtin_fmaf(dch.y, dp0.y, dch.x * dp0.x);         // alpha T dL/dC
+                    float m_g = __builtin_fmaf(dch.y, dp1.y, dch.x * dp1.x);
+                    float m_b = __builtin_fmaf(dch.y, dp2.y, dch.x * dp2.x);
                     const float sum = wave_sum9(m_w, m_x, m_y, m_xx, m_xy, m_yy, m_r, m_g, m_b);
                     // both waves add into the same rows; nobody waits for it
                     uint32_t row = 36u * (uint32_t)jc;
