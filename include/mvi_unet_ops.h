@@ -303,6 +303,25 @@ int mvi_stem_conv3x3_pack(const void* weight, void* packed_weight, int32_t Cin, 
 int mvi_stem_conv3x3_silu(const void* x, const void* packed_weight, const float* bias, void* y, int64_t N, int32_t Cin, int32_t Cout,
                           int32_t H, int32_t W, int32_t stride, int32_t fuse_silu, int32_t dtype, void* stream);
 
+/* The backward of those layers for ControlNet training (the 16- and 32-output forms; not the 320-output input convolution), every pass
+ * deterministic, no atomics. Nothing but x is kept from the forward.
+ *   mvi_stem_conv3x3_dz: the forward kernel once more with a second epilogue: z = conv(x) + bias is recomputed in fp32 and
+ *     dz = dy * s * (1 + z (1 - s)), s = sigmoid(z), is stored (fuse_silu == 0: dz = dy). dy, dz [N, C_out, H_out, W_out] in the activation
+ *     type, 16-byte aligned; y NULL, or the forward's output written beside dz (the same bits as mvi_stem_conv3x3_silu).
+ *   mvi_stem_conv3x3_wgrad (csrc/stem_conv_bwd.hip): dweight[co][ci][ky][kx] = sum over (n, oy, ox) of dz[n, co, oy, ox] *
+ *     x[n, ci, s oy + ky - 1, s ox + kx - 1] (out-of-image pixels 0) and dbias[co] = sum of dz (dbias may be NULL), fp32, every element
+ *     written once (N = 0: zeros). A bounded grid of blocks writes fp32 partials to the caller's `workspace` (16-byte aligned, at least
+ *     ..._wgrad_workspace_bytes(), a pure function of the shape), a second launch adds them in block order. A workspace that is NULL or too
+ *     small is declined with the invalid-argument status; nothing is launched.
+ * The input gradient of a stride-1 layer with C_in == C_out needs no kernel of its own: it is mvi_stem_conv3x3_silu of dz (no bias, no SiLU)
+ * with the packed weight W'[ci][co][ky][kx] = W[co][ci][2 - ky][2 - kx]. */
+int mvi_stem_conv3x3_bwd_supported(int32_t Cin, int32_t Cout, int32_t W, int32_t stride, int32_t dtype);
+int mvi_stem_conv3x3_dz(const void* x, const void* packed_weight, const float* bias, const void* dy, void* dz, void* y, int64_t N, int32_t Cin,
+                        int32_t Cout, int32_t H, int32_t W, int32_t stride, int32_t fuse_silu, int32_t dtype, void* stream);
+size_t mvi_stem_conv3x3_wgrad_workspace_bytes(int64_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t stride);
+int mvi_stem_conv3x3_wgrad(const void* x, const void* dz, float* dweight, float* dbias, int64_t N, int32_t Cin, int32_t Cout, int32_t H,
+                           int32_t W, int32_t stride, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* out[n, c, p] = h[n, c, p] + bias[c] + x[n, c, p] over [N, C, spatial] activations in one pass; x and bias are
  * optional (NULL). Folds a convolution's bias (PyTorch-ROCm adds it in a separate kernel) and the ResBlock skip
  * add `self.skip_connection(x) + h` (svd_inpaint1/sgm/modules/diffusionmodules/openaimodel.py:354). out may alias h. */

@@ -11,6 +11,10 @@
 //     A fragment of a k-step is ONE ds_read_b128 per lane: 8 consecutive channels of pixel (p + dx, row + dy);
 //   * the weights are the B operand, built once per wave in registers (20 or 12 registers);
 //   * the accumulator starts from the bias; a lane ends with 4 consecutive pixels of one output channel: SiLU, pack, one 8-byte store.
+//
+// Under autograd (ops._StemConvSiluFn) the same kernel runs once more with its second epilogue (DZ): the accumulator holds
+// z = conv(x) + b again, the lane loads dy at its 4 pixels (8 bytes) and stores dz = dy s (1 + z (1 - s)), s = sigmoid(z) — nothing but
+// x is kept from the forward. y is stored too where the caller asks for it (the tests compare it with the forward's bits).
 #include <cstdint>
 
 #include "mfma_common.h"
@@ -25,9 +29,10 @@ constexpr int kTHMax = 8;              // tile rows = waves: 8 for the 16-output
 
 template <typename T> using Mma = MmaBuiltin16<T>;
 
-template <typename T, int CINP, int COUT, int kTH, int STRIDE>
+template <typename T, int CINP, int COUT, int kTH, int STRIDE, bool DZ = false>
 __global__ __launch_bounds__(64 * kTH) void stem_conv3x3_kernel(const T* __restrict__ x, const T* __restrict__ wp, const float* __restrict__ bias,
-                                                                T* __restrict__ y, int Cin, int H, int W, int Ho, int Wo, int silu) {
+                                                                T* __restrict__ y, int Cin, int H, int W, int Ho, int Wo, int silu,
+                                                                const T* __restrict__ dy = nullptr, T* __restrict__ dz = nullptr) {
     using M = Mma<T>;
     using frag = typename M::frag;
     constexpr int kTapsPerStep = 32 / CINP;                       // 1 (32 channels), 2 (16) or 4 (8)
@@ -119,14 +124,32 @@ __global__ __launch_bounds__(64 * kTH) void stem_conv3x3_kernel(const T* __restr
             if (gy < Ho && gx < Wo) {
 #pragma unroll
                 for (int nt = 0; nt < NTC; ++nt) {
+                    const int64_t at = ((img * COUT + 16 * (nc + nt) + n) * Ho + gy) * (int64_t)Wo + gx;
                     float o[4];
+                    if constexpr (DZ) {
+                        // dz = dy silu'(z), silu'(z) = s (1 + z (1 - s)); the forward's y beside it where asked for
+                        const u32x2 g2 = *reinterpret_cast<const u32x2*>(dy + at);
+                        const float d[4] = {M::lo(g2[0]), M::hi(g2[0]), M::lo(g2[1]), M::hi(g2[1])};
+                        float q[4];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float t = acc[nt][i];
-                        o[i] = silu ? t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * -1.4426950408889634f)) : t;
+                        for (int i = 0; i < 4; ++i) {
+                            const float t = acc[nt][i];
+                            const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * -1.4426950408889634f));
+                            o[i] = silu ? t * sg : t;
+                            q[i] = silu ? d[i] * sg * (1.0f + t * (1.0f - sg)) : d[i];
+                        }
+                        const u32x2 pq = {M::pack2(q[0], q[1]), M::pack2(q[2], q[3])};
+                        *reinterpret_cast<u32x2*>(dz + at) = pq;
+                        if (!y) continue;
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const float t = acc[nt][i];
+                            o[i] = silu ? t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * -1.4426950408889634f)) : t;
+                        }
                     }
                     const u32x2 pk = {M::pack2(o[0], o[1]), M::pack2(o[2], o[3])};
-                    *reinterpret_cast<u32x2*>(y + ((img * COUT + 16 * (nc + nt) + n) * Ho + gy) * (int64_t)Wo + gx) = pk;
+                    *reinterpret_cast<u32x2*>(y + at) = pk;
                 }
             }
         }
@@ -182,6 +205,27 @@ static void stem_conv_launch(const void* x, const void* w, const float* bias, vo
                            bias, (T*)y, Cin, H, W, Ho, Wo, silu);
 }
 
+// the DZ epilogue of the four forms of ControlNet.input_hint_block (not the 320-output input convolution)
+template <typename T>
+static void stem_conv_dz_launch(const void* x, const void* w, const float* bias, const void* dy, void* dz, void* y, int64_t N, int Cin, int Cout,
+                                int H, int W, int stride, int silu, hipStream_t st) {
+    using namespace mvi::sc;
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const unsigned gx = (unsigned)((Wo + kTW - 1) / kTW);
+    if (stride == 2)
+        hipLaunchKernelGGL((stem_conv3x3_kernel<T, 16, 32, 4, 2, true>), dim3(gx, (unsigned)((Ho + 3) / 4), (unsigned)N), dim3(256), 0, st, (const T*)x,
+                           (const T*)w, bias, (T*)y, Cin, H, W, Ho, Wo, silu, (const T*)dy, (T*)dz);
+    else if (Cout == 32)
+        hipLaunchKernelGGL((stem_conv3x3_kernel<T, 32, 32, 4, 1, true>), dim3(gx, (unsigned)((Ho + 3) / 4), (unsigned)N), dim3(256), 0, st, (const T*)x,
+                           (const T*)w, bias, (T*)y, Cin, H, W, Ho, Wo, silu, (const T*)dy, (T*)dz);
+    else if (Cin <= 8)
+        hipLaunchKernelGGL((stem_conv3x3_kernel<T, 8, 16, 8, 1, true>), dim3(gx, (unsigned)((Ho + 7) / 8), (unsigned)N), dim3(512), 0, st, (const T*)x,
+                           (const T*)w, bias, (T*)y, Cin, H, W, Ho, Wo, silu, (const T*)dy, (T*)dz);
+    else
+        hipLaunchKernelGGL((stem_conv3x3_kernel<T, 16, 16, 8, 1, true>), dim3(gx, (unsigned)((Ho + 7) / 8), (unsigned)N), dim3(512), 0, st, (const T*)x,
+                           (const T*)w, bias, (T*)y, Cin, H, W, Ho, Wo, silu, (const T*)dy, (T*)dz);
+}
+
 extern "C" size_t mvi_stem_conv3x3_packed_bytes(int32_t Cin, int32_t Cout, int32_t stride) {
     if (Cin < 1 || Cout < 16 || Cout % 16) return 0;
     return (size_t)(Cout / 16) * mvi::sc::stem_ksteps(mvi::sc::stem_cinp(Cin, Cout, stride)) * 64 * 8 * 2;
@@ -210,4 +254,23 @@ extern "C" int mvi_stem_conv3x3_silu(const void* x, const void* weight, const fl
     if (dtype == MVI_DT_BF16) stem_conv_launch<__hip_bfloat16>(x, weight, bias, y, N, Cin, Cout, H, W, stride, fuse_silu, st);
     else stem_conv_launch<__half>(x, weight, bias, y, N, Cin, Cout, H, W, stride, fuse_silu, st);
     return hipGetLastError() == hipSuccess ? MVI_OK : mvi::unet_fail(MVI_EHIP, "stem_conv3x3: kernel launch failed");
+}
+
+extern "C" int mvi_stem_conv3x3_bwd_supported(int32_t Cin, int32_t Cout, int32_t W, int32_t stride, int32_t dtype) {
+    return Cout != 320 && mvi_stem_conv3x3_supported(Cin, Cout, W, stride, dtype);
+}
+
+extern "C" int mvi_stem_conv3x3_dz(const void* x, const void* weight, const float* bias, const void* dy, void* dz, void* y, int64_t N, int32_t Cin,
+                                   int32_t Cout, int32_t H, int32_t W, int32_t stride, int32_t fuse_silu, int32_t dtype, void* stream) {
+    if (N < 0 || H <= 0 || W <= 0 || !mvi_stem_conv3x3_bwd_supported(Cin, Cout, W, stride, dtype))
+        return mvi::unet_fail(MVI_EINVAL, "stem_conv3x3_dz: needs stride 1 with (C_out 16, C_in <= 16) or (C_out 32, C_in <= 32) and W % 8 == 0, or stride 2 with "
+                                          "C_out 32, C_in <= 16 and W % 16 == 0; bf16 or f16");
+    if (N == 0) return MVI_OK;
+    if (!x || !weight || !dy || !dz) return mvi::unet_fail(MVI_EINVAL, "stem_conv3x3_dz: NULL pointer");
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)dy | (uintptr_t)dz | (uintptr_t)weight) % 16 || N > 65535 || (H + 3) / 4 > 65535)
+        return mvi::unet_fail(MVI_EINVAL, "stem_conv3x3_dz: x / dy / dz / y / weight must be 16-byte aligned, N and H / 4 at most 65535");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MVI_DT_BF16) stem_conv_dz_launch<__hip_bfloat16>(x, weight, bias, dy, dz, y, N, Cin, Cout, H, W, stride, fuse_silu, st);
+    else stem_conv_dz_launch<__half>(x, weight, bias, dy, dz, y, N, Cin, Cout, H, W, stride, fuse_silu, st);
+    return hipGetLastError() == hipSuccess ? MVI_OK : mvi::unet_fail(MVI_EHIP, "stem_conv3x3_dz: kernel launch failed");
 }

@@ -917,6 +917,101 @@ def stem_conv3x3_silu(x, weight, bias, silu=True, stride=1):
     return y
 
 
+# ---- the hint-stem layers under autograd (ops._StemConvSiluFn): dz on the forward kernel's second epilogue, wgrad + dbias in
+# csrc/stem_conv_bwd.hip, the stride-1 C -> C input gradient on the forward kernel with the transposed weight --------------------------
+
+def stem_conv3x3_bwd_supported(C_in, C_out, W, stride, dtype):
+    """The shapes csrc/stem_conv.hip's dz epilogue and csrc/stem_conv_bwd.hip take: the forward's 16- and 32-output forms."""
+    return dtype in (torch.bfloat16, torch.float16) and bool(
+        _lib.lib().mvi_stem_conv3x3_bwd_supported(int(C_in), int(C_out), int(W), int(stride), _DT[dtype]))
+
+
+def stem_conv3x3_transposed_weight(weight):
+    """The weight whose 3x3 / padding 1 / stride 1 convolution of dz is the input gradient of conv(x, weight):
+    W'[ci, co, ky, kx] = W[co, ci, 2 - ky, 2 - kx], as a view [C_in, C_out, 3, 3]. Pure torch; loads no library."""
+    return weight.flip(2, 3).transpose(0, 1)
+
+
+def _stem_out_shape(x, weight, stride):
+    N, _, H, W = x.shape
+    return N, weight.shape[0], (H - 1) // stride + 1, (W - 1) // stride + 1
+
+
+def _stem_aligned(t):
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def stem_conv3x3_dz(x, weight, bias, dy, silu=True, stride=1, with_y=False):
+    """dz = dy * silu'(conv2d(x, weight, bias, stride, padding=1)) with z recomputed in the forward kernel (silu=False: dz = dy);
+    x [N, C_in, H, W], dy [N, C_out, H_out, W_out] -> dz like dy. with_y: (dz, y), y the forward's output from the same launch.
+    PROFILE kind stem_conv_dz."""
+    L = _lib.lib()
+    N, Cin, H, W = x.shape
+    if dy.dtype != x.dtype or tuple(dy.shape) != _stem_out_shape(x, weight, stride):
+        raise ValueError("stem_conv3x3_dz: dy [N, C_out, H_out, W_out] in x's dtype expected")
+    wc = _stem_packed_weight(weight, W, stride)
+    b = None if bias is None else _f32(bias)
+    xc, dc = _stem_aligned(x), _stem_aligned(dy)
+    dz = torch.empty_like(dc)
+    y = torch.empty_like(dc) if with_y else None
+    with torch.cuda.device(x.device), _Timed("stem_conv_dz", float(x.numel() + 2 * dz.numel()) * x.element_size(), x.device):
+        _check(L.mvi_stem_conv3x3_dz(xc.data_ptr(), wc.data_ptr(), _ptr(b), dc.data_ptr(), dz.data_ptr(), _ptr(y), N, Cin, weight.shape[0], H, W,
+                                     int(stride), int(bool(silu)), _DT.get(x.dtype, -1), _stream(x.device)), "stem_conv3x3_dz")
+    return (dz, y) if with_y else dz
+
+
+def stem_conv3x3_wgrad_workspace_bytes(N, C_in, C_out, H, W, stride=1):
+    """Bytes of fp32 partials csrc/stem_conv_bwd.hip writes for this shape: a pure host function of the shape, bounded by its grid."""
+    return int(_lib.lib().mvi_stem_conv3x3_wgrad_workspace_bytes(int(N), int(C_in), int(C_out), int(H), int(W), int(stride)))
+
+
+def stem_conv3x3_wgrad(x, dz, stride=1, need_dbias=True):
+    """(dweight fp32 [C_out, C_in, 3, 3], dbias fp32 [C_out] or None) of conv2d(x, weight, bias, stride, padding=1) from its input
+    x [N, C_in, H, W] and the pre-activation gradient dz [N, C_out, H_out, W_out] (one 16-bit dtype): csrc/stem_conv_bwd.hip,
+    deterministic. PROFILE kind stem_conv_wgrad."""
+    L = _lib.lib()
+    if x.dim() != 4 or dz.dim() != 4 or x.dtype != dz.dtype or x.shape[0] != dz.shape[0]:
+        raise ValueError("stem_conv3x3_wgrad: x [N, C_in, H, W] and dz [N, C_out, H_out, W_out] of one dtype expected")
+    N, Cin, H, W = x.shape
+    Co = dz.shape[1]
+    if tuple(dz.shape[2:]) != ((H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise ValueError("stem_conv3x3_wgrad: dz does not have the convolution's output size")
+    xc, dc = _stem_aligned(x), _stem_aligned(dz)
+    dw = torch.empty(Co, Cin, 3, 3, dtype=torch.float32, device=x.device)
+    db = torch.empty(Co, dtype=torch.float32, device=x.device) if need_dbias else None
+    ws_bytes = int(L.mvi_stem_conv3x3_wgrad_workspace_bytes(N, Cin, Co, H, W, int(stride)))
+    ws = _workspace(x.device, ws_bytes) if ws_bytes else None
+    with torch.cuda.device(x.device), _Timed("stem_conv_wgrad", float(x.numel() + dz.numel()) * x.element_size(), x.device):
+        _check(L.mvi_stem_conv3x3_wgrad(xc.data_ptr(), dc.data_ptr(), dw.data_ptr(), _ptr(db), N, Cin, Co, H, W, int(stride), _DT.get(x.dtype, -1),
+                                        _ptr(ws), ws_bytes, _stream(x.device)), "stem_conv3x3_wgrad")
+    return dw, db
+
+
+def stem_conv3x3_dgrad(dz, weight):
+    """dx [N, C, H, W] of the stride-1 convolution with C_in == C_out = C in (16, 32) from dz [N, C, H, W]: the forward kernel on the
+    packed transposed weight, no bias, no SiLU. The packed weight is kept in svd/derived.py's table while the weight is frozen and built
+    from the live tensor while it trains. PROFILE kind stem_conv_dgrad."""
+    L = _lib.lib()
+    N, C_, H, W = dz.shape
+    if tuple(weight.shape) != (C_, C_, 3, 3) or C_ not in (16, 32) or weight.dtype != dz.dtype:
+        raise ValueError("stem_conv3x3_dgrad: dz [N, C, H, W] and weight [C, C, 3, 3] of one dtype, C in (16, 32), expected")
+
+    def pack(w):
+        wt = stem_conv3x3_transposed_weight(w.detach()).contiguous()
+        packed = torch.empty(int(L.mvi_stem_conv3x3_packed_bytes(C_, C_, 1)), dtype=torch.uint8, device=w.device)
+        with torch.cuda.device(w.device):
+            _check(L.mvi_stem_conv3x3_pack(wt.data_ptr(), packed.data_ptr(), C_, C_, int(W), 1, _DT[w.dtype], _stream(w.device)), "stem_conv3x3_pack")
+        return packed
+    wp = pack(weight) if weight.requires_grad else derived1(("stem_packed_transposed", 1), weight, pack)
+    dc = _stem_aligned(dz)
+    dx = torch.empty_like(dc)
+    with torch.cuda.device(dz.device), _Timed("stem_conv_dgrad", 2.0 * dz.numel() * dz.element_size(), dz.device):
+        _check(L.mvi_stem_conv3x3_silu(dc.data_ptr(), wp.data_ptr(), None, dx.data_ptr(), N, C_, C_, H, W, 1, 0, _DT.get(dz.dtype, -1),
+                                       _stream(dz.device)), "stem_conv3x3_dgrad")
+    return dx
+
+
 def bias_residual_add(h, bias, x):
     L = _lib.lib()
     if h.dtype not in _DT:

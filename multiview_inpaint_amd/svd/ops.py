@@ -17,6 +17,9 @@ implicit-GEMM kernel with the transposed weight, the weight gradient on csrc/con
 so; the ResBlock reaches it through the opt-in layers.RESBLOCK_CONV_BWD. So has the (3,1,1) frame convolution of the temporal
 ResBlocks (`conv3t_tokens`: the same kernel's three-tap form for forward and input gradient, csrc/conv3t_wgrad.hip for the weight
 gradient), where `conv3t_backward_pays` says so; VideoResBlock reaches it through the opt-in layers.TIME_STACK_CONV_BWD.
+The 16- / 32-channel conv + SiLU layers of the ControlNet hint stem have one as well (`stem_conv3x3_silu`: dz on csrc/stem_conv.hip's second
+epilogue, weight / bias gradient on csrc/stem_conv_bwd.hip), where `stem_conv_backward_pays` says so; ControlNet._hint_stem reaches it
+through the opt-in unet.HINT_STEM_BWD.
 Every other kernel is forward-only: a GPU tensor that requires grad goes through PyTorch-ROCm's differentiable ops there
 (the projections, the strided and upsampling convolutions — `linear_add_layer_norm` under grad is `linear_module` +
 `add_layer_norm` —, `add_lerp`).
@@ -1071,3 +1074,105 @@ def conv3t_tokens(tok, weight, T):
     x = tok.reshape(B, T, S, C).permute(0, 3, 1, 2).unsqueeze(-1)              # b c t s 1 (a view)
     y = F.conv3d(x, weight, None, 1, (1, 0, 0))
     return y.squeeze(-1).permute(0, 2, 3, 1).reshape(BT, S, Co)
+
+
+# The 16- / 32-channel 3x3 convolution + SiLU layers of ControlNet.input_hint_block under autograd: forward on csrc/stem_conv.hip, dz on its
+# second epilogue (z recomputed from x), weight / bias gradient on csrc/stem_conv_bwd.hip, the stride-1 C -> C input gradient on the forward
+# kernel with the transposed weight. MVI_STEM_CONV_BWD=0 (or ops.STEM_CONV_BACKWARD = False): such a layer takes F.conv2d + F.silu under
+# autograd again.
+STEM_CONV_BACKWARD = os.environ.get("MVI_STEM_CONV_BWD", "1") != "0"
+# (stride, C_out, smallest measured N H_o W_o) of every class that won (profiles/stem_bwd_bench.json); nothing below those sizes is routed
+STEM_CONV_BACKWARD_ROUTED = ((1, 16, 14 * 288 * 512), (2, 32, 14 * 144 * 256), (1, 32, 14 * 144 * 256))
+
+
+def stem_conv_backward_pays(N, C_in, C_out, H, W, stride, dtype, need_dx):
+    """Whether forward + backward of one stem layer on the HIP kernels is faster than F.silu(F.conv2d(...)) under autograd for this shape
+    class — the routing's second question after stem_conv_gates. Measured by tools/bench_stem_bwd.py (profiles/stem_bwd_bench.json;
+    DESIGN.md 'Hint stem under autograd'): forward + backward by device events, the two routes alternating in one process, 9 pairs,
+    medians; a class goes to HIP only where its median beats the PyTorch route's by more than that route's spread. ms HIP / PyTorch
+    (spread), every parameter trainable, the input's gradient too except in the 7 -> 16 layer, N = 14; bf16 | f16:
+      576x1024   7 -> 16      0.644 / 1.724 (0.069) | 0.645 / 1.712 (0.038)    wins
+      576x1024  16 -> 16      0.991 / 2.843 (0.043) | 1.027 / 2.730 (0.070)    wins
+      576x1024  16 -> 32 s2   0.980 / 1.467 (0.052) | 0.844 / 1.254 (0.078)    wins
+      288x512   32 -> 32      0.663 / 1.311 (0.075) | 0.605 / 1.235 (0.115)    wins
+      288x512    7 -> 16      0.352 / 0.491 (0.045) | 0.316 / 0.466 (0.009)    wins
+      288x512   16 -> 16      0.436 / 0.775 (0.031) | 0.345 / 0.697 (0.038)    wins
+      288x512   16 -> 32 s2   0.443 / 0.564 (0.042) | 0.310 / 0.501 (0.020)    wins
+      144x256   32 -> 32      0.346 / 0.522 (0.018) | 0.244 / 0.471 (0.012)    wins
+    Every measured class won in both types, so each class is routed from its smallest measured size (in output pixels N H_o W_o) up.
+    Nothing smaller was measured and nothing smaller is routed. One run on one machine.
+    A class is (stride, C_out), the kernel form's own split. C_in, dtype and need_dx are deliberately unused: the table holds the widest
+    C_in of each class with the input gradient and both types, and a narrower C_in or a layer without an input gradient does less work on
+    the HIP route than the measured shape (the arguments stay in the signature for a later table that needs them)."""
+    px = N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1)
+    return any(stride == s and C_out == co and px >= line for s, co, line in STEM_CONV_BACKWARD_ROUTED)
+
+
+def stem_conv_gates(N, C_in, C_out, H, W, stride, dtype, need_dx):
+    """Do the launches of _StemConvSiluFn take this shape? The forward's and the backward kernels' gate, and for a layer whose input needs
+    a gradient one of the two built cases: stride 1 with C_in == C_out in (16, 32) (the forward kernel on the transposed weight), or the
+    stride-2 layer (aten's convolution_backward on dz)."""
+    from . import hip_ops
+    if not (N > 0 and H > 0 and W > 0 and hip_ops.stem_conv3x3_bwd_supported(C_in, C_out, W, stride, dtype)):
+        return False
+    return not need_dx or stride == 2 or (C_in == C_out and C_in in (16, 32))
+
+
+class _StemConvSiluFn(torch.autograd.Function):
+    """act(conv2d(x, weight, bias, stride, padding=1)), act = SiLU or nothing, on csrc/stem_conv.hip with a deterministic HIP backward. Holds
+    x, weight and bias only — z is recomputed by the dz pass, y is never kept — and caches nothing outside ctx, so torch.utils.checkpoint
+    may re-run the forward. Without SiLU dy is dz and no dz pass runs."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, silu, stride):
+        from . import hip_ops
+        ctx.save_for_backward(x, weight, bias)
+        ctx.cfg = (bool(silu), int(stride))
+        return hip_ops.stem_conv3x3_silu(x, weight, bias, silu=silu, stride=stride)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        x, weight, bias = ctx.saved_tensors
+        silu, stride = ctx.cfg
+        nx, nw, nb = ctx.needs_input_grad[:3]
+        nb = nb and bias is not None
+        dy = dy if dy.is_contiguous() else dy.contiguous()
+        dz = hip_ops.stem_conv3x3_dz(x, weight, bias, dy, silu=True, stride=stride) if silu else dy
+        dx = dw = db = None
+        if nw or nb:
+            dw, db = hip_ops.stem_conv3x3_wgrad(x, dz, stride=stride, need_dbias=nb)
+            dw = dw.to(weight.dtype) if nw else None
+            db = db.to(bias.dtype) if nb else None
+        if nx:
+            if stride == 1:
+                dx = hip_ops.stem_conv3x3_dgrad(dz, weight)
+            else:
+                # the stride-2 input gradient has no HIP kernel yet (four parity classes of 1, 2, 2 and 4 taps): the library's
+                dx = torch.ops.aten.convolution_backward(dz, x, weight, None, [stride, stride], [1, 1], [1, 1], False, [0, 0], 1,
+                                                         (True, False, False))[0]
+        return dx, dw, db, None, None
+
+
+def stem_conv3x3_silu(x, weight, bias, silu=True, stride=1):
+    """act(conv2d(x, weight, bias, stride, padding=1)) for the 16- / 32-output layers of the hint stem; x [N, C_in, H, W] NCHW. Without
+    autograd: hip_ops.stem_conv3x3_silu. Under autograd: _StemConvSiluFn where the switch is on, the launches take the shape
+    (stem_conv_gates) and stem_conv_backward_pays says so; anything else is F.conv2d (+ F.silu) (a recorded fallback; strict mode
+    raises) — also the CPU path."""
+    if (x.is_cuda and x.dim() == 4 and x.dtype == weight.dtype and x.is_contiguous() and weight.dim() == 4
+            and tuple(weight.shape[1:]) == (x.shape[1], 3, 3) and stride in (1, 2)):
+        from . import hip_ops
+        N, Ci, H, W = x.shape
+        Co = weight.shape[0]
+        if not _needs_autograd(x, weight, bias):
+            if hip_ops.stem_conv3x3_bwd_supported(Ci, Co, W, stride, x.dtype) and N > 0:
+                return hip_ops.stem_conv3x3_silu(x, weight, bias, silu=silu, stride=stride)
+        else:
+            need_dx = x.requires_grad
+            if STEM_CONV_BACKWARD and stem_conv_gates(N, Ci, Co, H, W, stride, x.dtype, need_dx) \
+                    and stem_conv_backward_pays(N, Ci, Co, H, W, stride, x.dtype, need_dx):
+                return _StemConvSiluFn.apply(x, weight, bias, silu, stride)
+    _fallback(x, "stem_conv3x3_silu", _why(x, weight, bias))
+    z = F.conv2d(x, weight, bias, stride, 1)
+    return F.silu(z) if silu else z

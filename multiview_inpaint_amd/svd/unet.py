@@ -22,6 +22,10 @@ from .transformer import SpatialVideoTransformer, prepare_single_token_rows
 from . import ops
 
 STEM_CONV = os.environ.get("MVI_SVD_STEM_CONV", "1") != "0"     # csrc/stem_conv.hip for the 16-channel layers of the hint stem
+# MVI_HINT_STEM_BWD=1 (or unet.HINT_STEM_BWD = True): under autograd the leading 16- / 32-channel conv + SiLU pairs of the hint stem run
+# through ops.stem_conv3x3_silu (HIP forward and backward, only x kept per layer). Off by default: a tested opt-in like
+# layers.RESBLOCK_CONV_BWD.
+HINT_STEM_BWD = os.environ.get("MVI_HINT_STEM_BWD", "0") == "1"
 
 
 def _input_conv(blk, x):
@@ -278,6 +282,9 @@ class ControlNet(_Encoder):
         without its bias and `silu(h + bias)` is one fused pass (the tensors are up to 528 MB at 576x1024)."""
         layers_ = list(self.input_hint_block)
         plain = all(isinstance(m, (nn.Conv2d, nn.SiLU)) for m in layers_)
+        if plain and hint.is_cuda and torch.is_grad_enabled() and HINT_STEM_BWD and hint.dtype in (torch.bfloat16, torch.float16):
+            g = self._hint_stem_autograd(hint, layers_)
+            return to_tok(g) if tokens else g
         if not (plain and hint.is_cuda and not torch.is_grad_enabled()):
             g = self.input_hint_block(hint, emb, context)
             return to_tok(g) if tokens else g
@@ -298,6 +305,28 @@ class ControlNet(_Encoder):
                 h = conv(h) if y is None else y
                 i += 1
         return to_tok(h) if tokens else h
+
+    @staticmethod
+    def _hint_stem_autograd(hint, layers_):
+        """The stem under autograd with HINT_STEM_BWD on: the leading conv + SiLU pairs that pass ops.stem_conv3x3_silu's conditions
+        (its switch, its gates and its speed decision) run through it; from the first pair that does not, every module is called as it
+        is."""
+        from . import hip_ops
+        h, i = hint.contiguous(), 0
+        while i + 1 < len(layers_) and isinstance(layers_[i], nn.Conv2d) and isinstance(layers_[i + 1], nn.SiLU):
+            conv = layers_[i]
+            need = ops._needs_autograd(h, conv.weight, conv.bias)
+            N, C, H, W = h.shape
+            s = conv.stride[0]
+            if not (need and ops.STEM_CONV_BACKWARD and hip_ops.stem_conv3x3_supported(conv, h)
+                    and ops.stem_conv_gates(N, C, conv.out_channels, H, W, s, h.dtype, h.requires_grad)
+                    and ops.stem_conv_backward_pays(N, C, conv.out_channels, H, W, s, h.dtype, h.requires_grad)):
+                break
+            h = ops.stem_conv3x3_silu(h, conv.weight, conv.bias, silu=True, stride=s)
+            i += 2
+        for m in layers_[i:]:
+            h = m(h)
+        return h
 
     @contextlib.contextmanager
     def hint_cache(self):
