@@ -262,6 +262,30 @@ size_t mvi_conv3x3_wgrad_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_
 int mvi_conv3x3_wgrad(const void* x, const void* dy, float* dweight, int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out,
                       int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The 3x3 / STRIDE 2 / padding 1 convolution y = conv(x, W) under autograd (training: Downsample.op), H and W even. With z = dy
+ * zero-stuffed to H x W (z[2 r, 2 c] = dy[r, c], 0 elsewhere; never in memory) and W'[ci][co][ky][kx] = W[co][ci][2 - ky][2 - kx]:
+ *   mvi_conv3x3_s2_dgrad: dx = conv3x3(z, W', padding 1, stride 1) on csrc/linear_n320.hip (the upsampling form's half-size source
+ *     addressing plus the zero rule). dy [N, (H / 2)(W / 2), C_out], weight_t = W' packed like mvi_conv3x3_n320's weight
+ *     ([C_in][9 C_out] in the order of mvi_conv3x3_n320_k_order), dx [N H W, C_in] in rows of out_row_stride elements with room for
+ *     mvi_ff_geglu_out_rows(N H W) rows. C_in a multiple of 320, C_out a multiple of 64, bf16 / f16, no bias, no K split.
+ *   mvi_conv3x3_s2_wgrad: dweight[co][ci][ky][kx] = sum z[n, u, v, co] * x[n, u + ky - 1, v + kx - 1, ci], fp32 [C_out, C_in, 3, 3], from
+ *     x [N, H W, C_in] and dy [N, (H / 2)(W / 2), C_out]: csrc/conv3x3_wgrad.hip with x staged as four parity planes. Everything else is
+ *     mvi_conv3x3_wgrad's contract: every element written once (N = 0: zeros), deterministic without atomics, pixel-axis split with
+ *     fp32 partials in `workspace` (a pure function of the shape; NULL or short: the unsplit launch), C_in and C_out multiples of 64,
+ *     W <= 256; odd H or W and fp32 are declined with the invalid-argument status. */
+int mvi_conv3x3_s2_dgrad_supported(int32_t C_in, int32_t C_out, int32_t dtype);
+int mvi_conv3x3_s2_dgrad(const void* dy, const void* weight_t, void* dx, int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out,
+                         int64_t out_rows_capacity, int64_t out_row_stride, int32_t dtype, void* stream);
+int mvi_conv3x3_s2_wgrad_supported(int32_t C_in, int32_t C_out, int32_t dtype);
+size_t mvi_conv3x3_s2_wgrad_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out);
+int mvi_conv3x3_s2_wgrad(const void* x, const void* dy, float* dweight, int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out,
+                         int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/* out[n, y, x, :] = the sum of the four rows of g's 2x2 cell (2 y .., 2 x ..): g [N, (2 h)(2 w), C] -> out [N, h w, C] token-major, fp32
+ * sum, one rounding, 16-byte accesses; C a multiple of 8, bf16 / f16. The adjoint of the nearest-neighbour 2x upsampling: the input
+ * gradient of conv3x3(upsample2(x), W) is mvi_rows_pool2x2_sum of mvi_conv3x3_n320(dy, W') at 2 h x 2 w. */
+int mvi_rows_pool2x2_sum(const void* g, void* out, int64_t N, int32_t h, int32_t w, int32_t C, int32_t dtype, void* stream);
+
 /* conv3x3(F.interpolate(x, scale_factor=2, mode="nearest")) of token-major x [N, h w, C_in] -> out [N, (2 h)(2 w), C_out]: Upsample.conv
  * (openaimodel.py:107-150) with the upsampling in the kernel's addressing (round 6: the token-major residual stream). Conditions and
  * out capacity as mvi_conv3x3_n320 at (N, 2 h, 2 w), stride 1. */

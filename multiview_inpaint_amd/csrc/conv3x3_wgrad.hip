@@ -28,6 +28,20 @@
 //   conv3x3_wgrad_kernel<bf16> and <f16>: 196 VGPRs, 0 AGPRs, 69 SGPRs, no scratch, occupancy 2 waves per SIMD;
 //   LDS dynamic, 160 (2 kKc + 2 P + 2) bytes: 72 640 at W = 64 (two blocks per CU), 56 000 at W = 12; W <= 256 (134 400).
 //   conv3x3_wgrad_reduce_kernel: 12 VGPRs, no LDS, no scratch.
+//
+// kS2: the weight gradient of the STRIDE-2 convolution (mvi_conv3x3_s2_wgrad; H, W even, dy [N, (H / 2)(W / 2), C_out]):
+//     dweight[co][ci][ky][kx] = sum over (n, r, c) of dy[n, r, c, co] * x[n, 2 r + ky - 1, 2 c + kx - 1, ci]      (outside the image: 0)
+// (the stride-1 formula with the zero-stuffed dy, the zeros left out). The stride, like the border rule, lives in the LDS images: dy
+// is walked in its OWN padded position space with rows of P = W / 2 + 1 positions (position q = r P + c is dy[n, r, c] for c < W / 2
+// and 0 at the one pad position), and x is staged as FOUR PARITY PLANES in the same space: plane (pr, pc) at position rr P + cc is
+// x[n, 2 rr - pr, 2 cc - pc], 0 outside the image — the odd planes carry the border's zero row / column at rr = 0 / cc = 0, the even-
+// column planes a zero at the pad position cc = W / 2. Tap ky reads row 2 r - 1 (odd plane, rr = r), 2 r (even plane, rr = r) or
+// 2 r + 1 (odd plane, rr = r + 1), columns likewise: every tap is a (plane, constant offset) pair — offset (ky == 2) P + (kx == 2) —
+// and the inner loop is the stride-1 kernel's: no mask, no wasted step, every transposed read with EXEC all ones on initialised LDS.
+// The other staging considered — the dy image zero-stuffed in the stride-1 position space, the smallest change — multiplies three
+// zeros for every value and measured 0.04 - 0.08 of the matrix peak; this one costs four x images, two of them a row
+// longer than the chunk, so its chunk is kKcS2 = 64 positions: 160 (5 kKcS2 + 2 P + 8) bytes = 73 280 at W = 128, two blocks per CU.
+//   conv3x3_wgrad_kernel<bf16, true> and <f16, true>: 196 VGPRs, 0 AGPRs, 88 SGPRs, no scratch, occupancy 2 waves per SIMD.
 #include <atomic>
 #include <cstdint>
 
@@ -42,6 +56,7 @@ constexpr int kBN = 64;                         // C_in per block (16 per wave)
 constexpr int kWaves = 4;
 constexpr int kKc = 160;                        // padded pixel positions per chunk
 constexpr int kSteps = kKc / 32;
+constexpr int kKcS2 = 64;                       // kS2: dy positions per chunk (the four x planes have to fit beside them)
 constexpr int kRow = 160;                       // LDS row stride in bytes: 64 channels + 32 bytes of padding
 constexpr int kMaxW = 256;
 constexpr int kMaxSplit = 64;
@@ -50,8 +65,12 @@ constexpr int kTargetBlocks = 512;              // two blocks on each of the 256
 template <typename T> using Mma = MmaBuiltin16<T>;
 
 __host__ __device__ constexpr int x_rows(int W) { return kKc + 2 * (W + 2) + 2; }
+// kS2: rows of an even-row plane (taps reach one position past the chunk) and of an odd-row plane (one row of P = W / 2 + 1 more)
+__host__ __device__ constexpr int s2_even_rows() { return kKcS2 + 2; }
+__host__ __device__ constexpr int s2_odd_rows(int W) { return kKcS2 + (W / 2 + 1) + 2; }
+__host__ __device__ constexpr int s2_lds_rows(int W) { return kKcS2 + 2 * s2_even_rows() + 2 * s2_odd_rows(W); }
 
-template <typename T>
+template <typename T, bool kS2 = false>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void conv3x3_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ out, int H, int W, int C_in, int C_out,
                           int chunks_per_image, int64_t chunks, int splits) {
@@ -59,7 +78,8 @@ void conv3x3_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, flo
     using frag = typename M::frag;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     MVI_AS3 char* const ldy = (MVI_AS3 char*)smem;
-    MVI_AS3 char* const lx = ldy + kKc * kRow;
+    constexpr int KC = kS2 ? kKcS2 : kKc, STEPS = KC / 32;         // positions per chunk, 32-position steps
+    MVI_AS3 char* const lx = ldy + KC * kRow;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -68,8 +88,11 @@ void conv3x3_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, flo
     const int co0 = ((int)blockIdx.x / ci_tiles) * kBM, ci0 = ((int)blockIdx.x % ci_tiles) * kBN;
     const int s = blockIdx.y;
     const int64_t ch_begin = chunks * s / splits, ch_end = chunks * (s + 1) / splits;
-    const int P = W + 2;
+    const int P = kS2 ? (W >> 1) + 1 : W + 2;
     const int XR = x_rows(W);
+    // kS2: first LDS row of plane 2 pr + pc behind lx — (even, even) | (even, odd) | (odd, even) | (odd, odd)
+    const int pl_rows[4] = {s2_even_rows(), s2_even_rows(), s2_odd_rows(W), s2_odd_rows(W)};
+    const int pl_base[4] = {0, s2_even_rows(), 2 * s2_even_rows(), 2 * s2_even_rows() + s2_odd_rows(W)};
 
     // transposed read of a 4-row x 16-column block: lane 4 q + p of a 16-lane group addresses row q, columns 4 p .. 4 p + 3
     const uint32_t tr = (uint32_t)((4 * g + (c16 >> 2)) * kRow + 8 * (c16 & 3));
@@ -84,20 +107,38 @@ void conv3x3_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, flo
     const int piece = tid & 7, row0 = tid >> 3;                    // 16-byte piece of a 64-channel row; 32 rows per pass of the block
     for (int64_t ch = ch_begin; ch < ch_end; ++ch) {
         const int64_t n = ch / chunks_per_image;
-        const int q0 = (int)(ch - n * chunks_per_image) * kKc;
-        const T* const dyn = dy + n * H * W * (int64_t)C_out + co0 + 8 * piece;
+        const int q0 = (int)(ch - n * chunks_per_image) * KC;
+        const T* const dyn = (kS2 ? dy + n * (H >> 1) * (W >> 1) * (int64_t)C_out : dy + n * H * W * (int64_t)C_out) + co0 + 8 * piece;
         const T* const xn = x + n * H * W * (int64_t)C_in + ci0 + 8 * piece;
         __syncthreads();                                           // the previous chunk's reads are done
-        u32x4 v[kKc / 32];
+        u32x4 v[STEPS];
 #pragma unroll
-        for (int i = 0; i < kKc / 32; ++i) {
+        for (int i = 0; i < STEPS; ++i) {
             const int q = q0 + row0 + 32 * i;
             const int r = q / P, c = q - r * P;
             v[i] = u32x4{0u, 0u, 0u, 0u};
+            if (kS2) {                                             // dy's own (H / 2) x (W / 2) image, one pad position per row
+                if (r < (H >> 1) && c < (W >> 1)) v[i] = *reinterpret_cast<const u32x4*>(dyn + (int64_t)(r * (W >> 1) + c) * C_out);
+            } else
             if (r < H && c < W) v[i] = *reinterpret_cast<const u32x4*>(dyn + (int64_t)(r * W + c) * C_out);
         }
 #pragma unroll
-        for (int i = 0; i < kKc / 32; ++i) *reinterpret_cast<MVI_AS3 u32x4*>(ldy + (row0 + 32 * i) * kRow + 16 * piece) = v[i];
+        for (int i = 0; i < STEPS; ++i) *reinterpret_cast<MVI_AS3 u32x4*>(ldy + (row0 + 32 * i) * kRow + 16 * piece) = v[i];
+        if (kS2) {
+#pragma unroll
+            for (int pl = 0; pl < 4; ++pl) {
+                const int pr = pl >> 1, pc = pl & 1;
+#pragma unroll 2
+                for (int row = row0; row < pl_rows[pl]; row += 32) {
+                    const int q = q0 + row;
+                    const int rr = q / P, cc = q - rr * P;
+                    const int y = 2 * rr - pr, xc = 2 * cc - pc;                     // (-1: the border's zero row / column; xc = W: the pad)
+                    u32x4 w = u32x4{0u, 0u, 0u, 0u};
+                    if (y >= 0 && y < H && xc >= 0 && xc < W) w = *reinterpret_cast<const u32x4*>(xn + (int64_t)(y * W + xc) * C_in);
+                    *reinterpret_cast<MVI_AS3 u32x4*>(lx + (pl_base[pl] + row) * kRow + 16 * piece) = w;
+                }
+            }
+        } else
 #pragma unroll 4
         for (int row = row0; row < XR; row += 32) {
             const int q = q0 + row;
@@ -109,7 +150,7 @@ void conv3x3_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, flo
         __syncthreads();
 
 #pragma unroll 1
-        for (int st = 0; st < kSteps; ++st) {
+        for (int st = 0; st < STEPS; ++st) {
             const uint32_t so = (uint32_t)(32 * st * kRow);
             frag a[4];
 #pragma unroll
@@ -121,7 +162,9 @@ void conv3x3_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, flo
             }
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
-                const uint32_t to = so + (uint32_t)(((t / 3) * P + t % 3) * kRow) + tr_b;
+                // kS2: tap (ky, kx) = plane (ky != 1, kx != 1) at offset (ky == 2) P + (kx == 2)
+                const uint32_t to = so + tr_b + (kS2 ? (uint32_t)((pl_base[2 * (t / 3 != 1) + (t % 3 != 1)] + (t / 3 == 2 ? P : 0) + (t % 3 == 2)) * kRow)
+                                                     : (uint32_t)(((t / 3) * P + t % 3) * kRow));
                 s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(lx + to));
                 s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(lx + to + 16 * kRow));
                 const u32x2 l = *reinterpret_cast<u32x2*>(&lo4), h = *reinterpret_cast<u32x2*>(&hi4);
@@ -158,8 +201,8 @@ static bool shape_ok(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_ou
 }
 
 // The split policy: a pure function of the shape.
-static int split_of(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out, int* chunks_per_image) {
-    const int cpi = (int)(((int64_t)H * (W + 2) + kKc - 1) / kKc);
+static int split_of(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out, int* chunks_per_image, bool s2 = false) {
+    const int cpi = s2 ? (int)(((int64_t)(H / 2) * (W / 2 + 1) + kKcS2 - 1) / kKcS2) : (int)(((int64_t)H * (W + 2) + kKc - 1) / kKc);
     const int64_t chunks = N * cpi, tiles = (int64_t)(C_in / kBN) * (C_out / kBM);
     int64_t S = kTargetBlocks / tiles;
     if (S > kMaxSplit) S = kMaxSplit;
@@ -168,18 +211,18 @@ static int split_of(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out
     return S < 2 ? 1 : (int)S;
 }
 
-template <typename T>
+template <typename T, bool kS2 = false>
 static int launch(const void* x, const void* dy, float* dweight, int64_t N, int H, int W, int C_in, int C_out, void* ws, size_t ws_bytes,
                   hipStream_t st) {
     int cpi = 0;
-    int S = split_of(N, H, W, C_in, C_out, &cpi);
+    int S = split_of(N, H, W, C_in, C_out, &cpi, kS2);
     const int64_t total = (int64_t)C_out * C_in * 9;
     if (S > 1 && (!ws || ws_bytes < (size_t)S * total * sizeof(float))) S = 1;          // no workspace: the unsplit launch
-    const int lds_bytes = (kKc + x_rows(W)) * kRow;
+    const int lds_bytes = (kS2 ? s2_lds_rows(W) : kKc + x_rows(W)) * kRow;
     static std::atomic<unsigned long long> attr_set{0};          // per device and instantiation: the opt-in for > 64 KiB of dynamic LDS
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MVI_EHIP;
-    auto kern = &conv3x3_wgrad_kernel<T>;
+    auto kern = &conv3x3_wgrad_kernel<T, kS2>;
     if (!(attr_set.load(std::memory_order_acquire) >> dev & 1ull)) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return MVI_EHIP;
@@ -224,4 +267,29 @@ extern "C" int mvi_conv3x3_wgrad(const void* x, const void* dy, float* dweight, 
         return mvi::cwg::launch<typename decltype(t)::type>(x, dy, dweight, N, H, W, C_in, C_out, workspace, workspace_bytes, st);
     });
     return rc == MVI_EHIP ? mvi::unet_fail(rc, "conv3x3 wgrad: kernel launch failed") : rc;
+}
+
+// The stride-2 form (kS2 at the kernel): x [N, H W, C_in], dy [N, (H / 2)(W / 2), C_out], H and W even; gate, split policy (a pure function
+// of (N, H, W, C_in, C_out): the stride-1 kernel's over dy's own position space), workspace and determinism as mvi_conv3x3_wgrad.
+extern "C" int mvi_conv3x3_s2_wgrad_supported(int32_t C_in, int32_t C_out, int32_t dtype) { return mvi_conv3x3_wgrad_supported(C_in, C_out, dtype); }
+
+extern "C" size_t mvi_conv3x3_s2_wgrad_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out) {
+    if (!mvi::cwg::shape_ok(N, H, W, C_in, C_out) || N == 0 || (H & 1) || (W & 1)) return 0;
+    const int S = mvi::cwg::split_of(N, H, W, C_in, C_out, nullptr, true);
+    return S > 1 ? (size_t)S * (size_t)C_out * C_in * 9 * sizeof(float) : 0;
+}
+
+extern "C" int mvi_conv3x3_s2_wgrad(const void* x, const void* dy, float* dweight, int64_t N, int32_t H, int32_t W, int32_t C_in,
+                                    int32_t C_out, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!mvi_conv3x3_wgrad_supported(C_in, C_out, dtype) || !mvi::cwg::shape_ok(N, H, W, C_in, C_out) || (H & 1) || (W & 1))
+        return mvi::unet_fail(MVI_EINVAL, "conv3x3 s2 wgrad: needs C_in and C_out multiples of 64, bf16 or f16, even H and W, W <= 256");
+    if (!x || !dy || !dweight) return mvi::unet_fail(MVI_EINVAL, "conv3x3 s2 wgrad: NULL pointer");
+    if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dweight | (uintptr_t)workspace) % 16)
+        return mvi::unet_fail(MVI_EINVAL, "conv3x3 s2 wgrad: x, dy, dweight and workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) return hipMemsetAsync(dweight, 0, (size_t)C_out * C_in * 9 * sizeof(float), st) == hipSuccess ? MVI_OK : MVI_EHIP;
+    const int rc = mvi::dispatch_dtype16(dtype, "conv3x3 s2 wgrad: unknown dtype", [&](auto t) {
+        return mvi::cwg::launch<typename decltype(t)::type, true>(x, dy, dweight, N, H, W, C_in, C_out, workspace, workspace_bytes, st);
+    });
+    return rc == MVI_EHIP ? mvi::unet_fail(rc, "conv3x3 s2 wgrad: kernel launch failed") : rc;
 }

@@ -92,6 +92,10 @@ struct ConvGeom {
 // kUps (round 6, the token stream's Upsample.conv: openaimodel.py:107-150): cg.H, cg.W are those of the nearest-neighbour 2x UPSAMPLED image, x
 // holds the (H / 2) x (W / 2) source — pixel (y, x) reads source (y >> 1, x >> 1): the convolution of F.interpolate(x, scale_factor=2)
 // without the 4x tensor ever existing. An instantiation of its own (3 launches per step): the other convolutions carry none of its registers.
+// kZs (with kUps; the input gradient of the STRIDE-2 convolution, mvi_conv3x3_s2_dgrad): the same source addressing, but the H x W image
+// the taps walk is the half-size source ZERO-STUFFED, z[2 r, 2 c] = src[r, c] and 0 elsewhere, not repeated: neighbour (y + dy, x + dx)
+// contributes only when both coordinates are even. The rule is folded into tap_ok once per row, so an excluded tap takes the masked
+// tap's path below — it loads the row's own centre address and `keep` zeroes the fragment; no address is formed for an excluded pixel.
 
 // kStats: the GroupNorm that FOLLOWS this convolution gets its statistics from here (ResBlock out_layers[0] behind in_layers[2],
 // openaimodel.py:292-305, :339-343; the temporal twin, video_model.py:41-54): every block leaves, per GroupNorm group inside its 320
@@ -133,7 +137,7 @@ struct LnEpi {
 // convolutions (split operands, fp32 out). Everything below is written in terms of kN / kNT / kChunkBytes / kPieces..., re-derived here
 // from NOUT (the epilogues that know about 320 — kStats, kGeglu, kLn — are only instantiated with it).
 template <typename T, bool kConv, bool kSplit = false, bool kStats = false, bool kGeglu = false, bool kLn = false, int NOUT = 320,
-          bool kUps = false, bool kPersist = false>
+          bool kUps = false, bool kPersist = false, bool kZs = false>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void linear_n320_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias, T* __restrict__ out,
                         int64_t rows, int K, int64_t x_rs, int64_t o_rs, int n_blocks, ConvGeom cg, float* __restrict__ part, GnStats gn,
@@ -141,6 +145,7 @@ void linear_n320_kernel(const T* __restrict__ x, const T* __restrict__ w, const 
     using M = Mma<T>;
     static_assert(NOUT == 320 || !(kStats || kGeglu || kLn), "the fused epilogues are written for 320 columns");
     static_assert(!kPersist || !(kConv || kSplit || kStats || kLn), "the persistent form is written for the plain and the GEGLU projection");
+    static_assert(!kZs || (kUps && kConv && !kSplit && !kStats), "the zero-stuffed source is a mode of the upsampling form");
     constexpr int kN = NOUT, kNT = kN / 16, kChunkBytes = kN * kKC * 2, kPieces = kChunkBytes / 1024, kPiecesPerLoader = kPieces / kLoaders;
     static_assert(kNT % 4 == 0 && kPieces % kLoaders == 0, "column tiles leave four at a time; every loader moves the same number of pieces");
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -249,6 +254,10 @@ void linear_n320_kernel(const T* __restrict__ x, const T* __restrict__ w, const 
                 if (py == cg.H - 1) tap_ok[t] &= ~0x1C0u;
                 if (px == 0) tap_ok[t] &= ~0x049u;
                 if (px == cg.W - 1) tap_ok[t] &= ~0x124u;
+                if (kZs) {                           // z is non-zero at (even, even) only: from an even y only dy = 0 lands on one, from an odd y only dy = +-1
+                    tap_ok[t] &= (py & 1) ? ~0x038u : ~0x1C7u;
+                    tap_ok[t] &= (px & 1) ? ~0x092u : ~0x16Du;
+                }
             } else {                                 // bit dy + 1
                 if (py == 0) tap_ok[t] &= ~0x1u;
                 if (py == cg.H - 1) tap_ok[t] &= ~0x4u;
@@ -800,7 +809,7 @@ static bool persist_ok(int64_t n_tiles, int K) {
 }
 
 template <typename T, bool kConv = false, bool kSplit = false, bool kStats = false, bool kGeglu = false, bool kLn = false, int NOUT = 320,
-          bool kUps = false, bool kPersist = false>
+          bool kUps = false, bool kPersist = false, bool kZs = false>
 static int linear_n320_launch(const void* x, const void* w, const float* bias, void* out, int64_t rows, int K, int64_t x_rs, int64_t o_rs,
                               hipStream_t st, ln3::ConvGeom cg = {0, 0, 0, 0, 1, 1, 1, 0, 0, 0, 0}, float* part = nullptr,
                               ln3::GnStats gn = {nullptr, nullptr, 0, 0},
@@ -811,7 +820,7 @@ static int linear_n320_launch(const void* x, const void* w, const float* bias, v
     static unsigned long long attr_set = 0;                      // per device and instantiation: the opt-in for > 64 KiB of dynamic LDS
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MVI_EHIP;
-    auto kern = &linear_n320_kernel<T, kConv, kSplit, kStats, kGeglu, kLn, NOUT, kUps, kPersist>;
+    auto kern = &linear_n320_kernel<T, kConv, kSplit, kStats, kGeglu, kLn, NOUT, kUps, kPersist, kZs>;
     constexpr int kLdsBytes = kRing * NOUT * kKC * 2 + kWaves * 4096 + (kPersist ? 2048 : 0);       // (+ the staged bias of the next tile)
     if (!(attr_set >> dev & 1ull)) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
@@ -1009,6 +1018,11 @@ static int conv_taps_n320(const char* what, const void* x, const void* weight, c
     if (ups) {                                       // (H, W: the upsampled image — both even by construction; its own instantiation, never K-split)
         if (taps != 9 || stride != 1 || gn.part || (H & 1) || (W & 1)) return fail("upsampling: 3x3, stride 1, no statistics");
         cg.ksplit = 1;
+        if (ups == 2)                                // the zero-stuffed source (kZs): mvi_conv3x3_s2_dgrad
+            rc = dtype == MVI_DT_BF16
+                     ? mvi::linear_n320_launch<__hip_bfloat16, true, false, false, false, false, 320, true, false, true>(x, weight, bias, out, rows, taps * C_in, C_in, out_row_stride, st, cg)
+                     : mvi::linear_n320_launch<__half, true, false, false, false, false, 320, true, false, true>(x, weight, bias, out, rows, taps * C_in, C_in, out_row_stride, st, cg);
+        else
         rc = dtype == MVI_DT_BF16
                  ? mvi::linear_n320_launch<__hip_bfloat16, true, false, false, false, false, 320, true>(x, weight, bias, out, rows, taps * C_in, C_in, out_row_stride, st, cg)
                  : mvi::linear_n320_launch<__half, true, false, false, false, false, 320, true>(x, weight, bias, out, rows, taps * C_in, C_in, out_row_stride, st, cg);
@@ -1056,6 +1070,23 @@ extern "C" int mvi_conv3x3_up2_n320(const void* x, const void* weight, const flo
     if (h <= 0 || w <= 0 || h > (1 << 29) || w > (1 << 29)) return mvi::unet_fail(MVI_EINVAL, "conv3x3_up2_n320: bad image size");
     return conv_taps_n320("conv3x3_up2_n320", x, weight, bias, out, N, 2 * h, 2 * w, 9, 1, C_in, C_out, out_rows_capacity, out_row_stride, dtype,
                           workspace, workspace_bytes, stream, {nullptr, nullptr, 0, 0}, 1);
+}
+
+// Input gradient of the 3x3 / stride 2 / padding 1 convolution y = conv(x, W) of token-major x [N, H W, C_in] (H, W even):
+//     dx = conv3x3(z, W', padding 1, stride 1),  z = dy zero-stuffed to H x W (z[2 r, 2 c] = dy[r, c]),  W'[ci][co][ky][kx] = W[co][ci][2 - ky][2 - kx]
+// on the kUps form's half-size source addressing plus the zero rule (kZs at the kernel): z never exists. dy [N, (H / 2)(W / 2), C_out],
+// weight_t = W' packed as mvi_conv3x3_n320's weight ([C_in][9 C_out] in the kernel's K order), dx [N H W rows, C_in] in rows of
+// out_row_stride elements, padded to whole 256-row blocks. C_in (the kernel's output columns) a multiple of 320, C_out (its
+// contraction channels) a multiple of 64. No bias, no K split.
+extern "C" int mvi_conv3x3_s2_dgrad_supported(int32_t C_in, int32_t C_out, int32_t dtype) {
+    return mvi_conv3x3_n320_supported(C_out, C_in, dtype);
+}
+
+extern "C" int mvi_conv3x3_s2_dgrad(const void* dy, const void* weight_t, void* dx, int64_t N, int32_t H, int32_t W, int32_t C_in,
+                                    int32_t C_out, int64_t out_rows_capacity, int64_t out_row_stride, int32_t dtype, void* stream) {
+    if (H <= 0 || W <= 0 || (H & 1) || (W & 1)) return mvi::unet_fail(MVI_EINVAL, "conv3x3_s2_dgrad: H and W must be even and positive");
+    return conv_taps_n320("conv3x3_s2_dgrad", dy, weight_t, nullptr, dx, N, H, W, 9, 1, C_out, C_in, out_rows_capacity, out_row_stride, dtype,
+                          nullptr, 0, stream, {nullptr, nullptr, 0, 0}, 2);
 }
 
 extern "C" int mvi_conv_n320_gnstats_supported(int64_t rows, int32_t taps, int32_t stride, int32_t C_in, int32_t C_out, int64_t spatial,

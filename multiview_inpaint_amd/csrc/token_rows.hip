@@ -479,3 +479,47 @@ extern "C" int mvi_tokens_blend_to_planes(const void* tok, const void* base, con
         return rc ? unet_fail(MVI_EHIP, "tokens_blend_to_planes: kernel launch failed") : MVI_OK;
     });
 }
+
+/* out[n, y, x, c] = g[n, 2 y, 2 x, c] + g[n, 2 y, 2 x + 1, c] + g[n, 2 y + 1, 2 x, c] + g[n, 2 y + 1, 2 x + 1, c]: the adjoint of the
+ * nearest-neighbour 2x upsampling on token-major tensors, g [N, (2 h)(2 w), C] -> out [N, h w, C] — the second half of the input gradient
+ * of Upsample.conv (dx = pool(conv3x3(dy, W'))). A thread owns one 16-byte vector of out: four 16-byte loads, the sum in fp32 as
+ * (a + b) + (c + d), ONE rounding, one 16-byte store. C a multiple of 8, bf16 / f16. */
+namespace mvi {
+template <typename T>
+__global__ __launch_bounds__(256) void rows_pool2x2_sum_kernel(const T* __restrict__ g, T* __restrict__ out, int64_t n_vec, int h, int w, int vpr) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_vec) return;
+    const int64_t pix = i / vpr;                                    // (n h + y) w + x
+    const int cv = (int)(i - pix * vpr);
+    const int64_t ny = pix / w;                                     // n h + y
+    const int x = (int)(pix - ny * w);
+    const int64_t row = (int64_t)vpr * 8;                           // C
+    const T* const p = g + ((2 * ny) * (2 * (int64_t)w) + 2 * x) * row + 8 * cv;       // (n 2 h + 2 y) 2 w + 2 x
+    const uint4 r0 = *reinterpret_cast<const uint4*>(p), r1 = *reinterpret_cast<const uint4*>(p + row);
+    const uint4 r2 = *reinterpret_cast<const uint4*>(p + 2 * (int64_t)w * row), r3 = *reinterpret_cast<const uint4*>(p + (2 * (int64_t)w + 1) * row);
+    float a[8], b[8], c[8], d[8];
+    Io<T>::load(reinterpret_cast<const T*>(&r0), a);
+    Io<T>::load(reinterpret_cast<const T*>(&r1), b);
+    Io<T>::load(reinterpret_cast<const T*>(&r2), c);
+    Io<T>::load(reinterpret_cast<const T*>(&r3), d);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = (a[k] + b[k]) + (c[k] + d[k]);
+    Io<T>::store(out + pix * row + 8 * cv, a);
+}
+}  // namespace mvi
+
+extern "C" int mvi_rows_pool2x2_sum(const void* g, void* out, int64_t N, int32_t h, int32_t w, int32_t C, int32_t dtype, void* stream) {
+    if (N < 0 || h <= 0 || w <= 0 || h > (1 << 29) || w > (1 << 29) || C <= 0 || C % 8 || (dtype != MVI_DT_BF16 && dtype != MVI_DT_F16))
+        return unet_fail(MVI_EINVAL, "rows_pool2x2_sum: needs C a positive multiple of 8, bf16 or f16");
+    if (N == 0) return MVI_OK;
+    if (!g || !out) return unet_fail(MVI_EINVAL, "rows_pool2x2_sum: NULL pointer");
+    if (((uintptr_t)g | (uintptr_t)out) % 16) return unet_fail(MVI_EINVAL, "rows_pool2x2_sum: pointers must be 16-byte aligned");
+    const int64_t n_vec = N * h * w * (C / 8), blocks = (n_vec + 255) / 256;
+    if (blocks > 0x7FFFFFFFll) return unet_fail(MVI_EINVAL, "rows_pool2x2_sum: too many rows for one launch");
+    return dispatch_dtype16(dtype, "rows_pool2x2_sum: unknown dtype", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((rows_pool2x2_sum_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)g, (T*)out, n_vec,
+                           (int)h, (int)w, C / 8);
+        return hipGetLastError() == hipSuccess ? MVI_OK : unet_fail(MVI_EHIP, "rows_pool2x2_sum: kernel launch failed");
+    });
+}

@@ -819,6 +819,78 @@ def conv3x3_wgrad(tok, dy_tok, H, W, split=True):
     return dw
 
 
+# ---- the stride-2 and the upsampling 3x3 convolution under autograd (ops._Conv3x3DownTokensFn / _Conv3x3UpTokensFn) ---------------------
+
+def conv3x3_s2_dgrad_supported(C_in, C_out, dtype):
+    return dtype in (torch.bfloat16, torch.float16) and bool(_lib.lib().mvi_conv3x3_s2_dgrad_supported(int(C_in), int(C_out), _DT[dtype]))
+
+
+def conv3x3_s2_dgrad(dy_tok, weight_t_taps, H, W):
+    """dx [N, H W, C_in] of the 3x3 / padding 1 / STRIDE 2 convolution of an H x W image (both even) from dy [N, (H / 2)(W / 2), C_out]:
+    the forward kernel on the packed transposed weight (conv3x3_n320_weight(conv3x3_transposed_weight(weight)), the packing of
+    conv3x3_dgrad) reading dy as the zero-stuffed H x W image it never builds (mvi_conv3x3_s2_dgrad). PROFILE kind conv3x3_s2_dgrad."""
+    L = _lib.lib()
+    if dy_tok.dim() != 3 or H % 2 or W % 2 or dy_tok.shape[1] != (H // 2) * (W // 2):
+        raise ValueError("conv3x3_s2_dgrad: dy_tok [N, (H / 2)(W / 2), C_out] with even H and W expected")
+    N, _, Co = dy_tok.shape
+    if weight_t_taps.dim() != 2 or weight_t_taps.shape[1] != 9 * Co or weight_t_taps.dtype != dy_tok.dtype:
+        raise ValueError("conv3x3_s2_dgrad: packed transposed weight [C_in, 9 C_out] of dy's dtype expected")
+    dc = dy_tok if dy_tok.is_contiguous() and dy_tok.data_ptr() % 16 == 0 else dy_tok.contiguous().clone()
+    wc = _contig(weight_t_taps)
+    Ci = wc.shape[0]
+    rows = N * H * W
+    cap = int(L.mvi_ff_geglu_out_rows(rows))
+    full = torch.empty(cap, Ci, dtype=dy_tok.dtype, device=dy_tok.device)
+    with torch.cuda.device(dy_tok.device), _Timed("conv3x3_s2_dgrad", 2.0 * rows * 9 * Ci * Co / 4, dy_tok.device):
+        _check(L.mvi_conv3x3_s2_dgrad(dc.data_ptr(), wc.data_ptr(), full.data_ptr(), N, H, W, Ci, Co, cap, full.stride(0),
+                                      _DT.get(dy_tok.dtype, -1), _stream(dy_tok.device)), "conv3x3_s2_dgrad")
+    return full[:rows].view(N, H * W, Ci)
+
+
+def conv3x3_s2_wgrad_supported(C_in, C_out, dtype):
+    return dtype in (torch.bfloat16, torch.float16) and bool(_lib.lib().mvi_conv3x3_s2_wgrad_supported(int(C_in), int(C_out), _DT[dtype]))
+
+
+def conv3x3_s2_wgrad_workspace_bytes(N, H, W, C_in, C_out):
+    """> 0: the stride-2 form of csrc/conv3x3_wgrad.hip splits the pixel axis of this shape over blocks (a pure host function of the shape)."""
+    return int(_lib.lib().mvi_conv3x3_s2_wgrad_workspace_bytes(int(N), int(H), int(W), int(C_in), int(C_out)))
+
+
+def conv3x3_s2_wgrad(tok, dy_tok, H, W, split=True):
+    """dweight, fp32 [C_out, C_in, 3, 3], of the 3x3 / padding 1 / STRIDE 2 convolution from its input tok [N, H W, C_in] and the output
+    gradient dy_tok [N, (H / 2)(W / 2), C_out] (one 16-bit dtype; H, W even): csrc/conv3x3_wgrad.hip's stride-2 form (x staged as four
+    parity planes), deterministic. split = False withholds the workspace (the unsplit launch). PROFILE kind conv3x3_s2_wgrad."""
+    L = _lib.lib()
+    if tok.dim() != 3 or dy_tok.dim() != 3 or tok.shape[0] != dy_tok.shape[0] or tok.shape[1] != H * W or tok.dtype != dy_tok.dtype \
+            or dy_tok.shape[1] != ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1):
+        raise ValueError("conv3x3_s2_wgrad: tok [N, H W, C_in] and dy_tok [N, (H / 2)(W / 2), C_out] of one dtype expected")
+    N, S, C = tok.shape
+    Co = dy_tok.shape[2]
+    xc = tok if tok.is_contiguous() and tok.data_ptr() % 16 == 0 else tok.contiguous().clone()
+    dc = dy_tok if dy_tok.is_contiguous() and dy_tok.data_ptr() % 16 == 0 else dy_tok.contiguous().clone()
+    dw = torch.empty(Co, C, 3, 3, dtype=torch.float32, device=tok.device)
+    ws_bytes = int(L.mvi_conv3x3_s2_wgrad_workspace_bytes(N, H, W, C, Co)) if split else 0
+    ws = _workspace(tok.device, ws_bytes) if ws_bytes else None
+    with torch.cuda.device(tok.device), _Timed("conv3x3_s2_wgrad", 2.0 * N * dy_tok.shape[1] * 9 * C * Co, tok.device):
+        _check(L.mvi_conv3x3_s2_wgrad(xc.data_ptr(), dc.data_ptr(), dw.data_ptr(), N, H, W, C, Co, _DT.get(tok.dtype, -1), _ptr(ws), ws_bytes,
+                                      _stream(tok.device)), "conv3x3_s2_wgrad")
+    return dw
+
+
+def pool2x2_sum(g_tok, h, w):
+    """g_tok [N, (2 h)(2 w), C] -> [N, h w, C]: the sum over every 2x2 cell in fp32, rounded once (mvi_rows_pool2x2_sum) — the adjoint of the
+    nearest-neighbour 2x upsampling. C a multiple of 8, bf16 / f16. PROFILE kind pool2x2_sum."""
+    L = _lib.lib()
+    if g_tok.dim() != 3 or g_tok.shape[1] != 4 * h * w:
+        raise ValueError("pool2x2_sum: g_tok [N, (2 h)(2 w), C] expected")
+    N, _, C = g_tok.shape
+    gc = g_tok if g_tok.is_contiguous() and g_tok.data_ptr() % 16 == 0 else g_tok.contiguous().clone()
+    out = torch.empty(N, h * w, C, dtype=g_tok.dtype, device=g_tok.device)
+    with torch.cuda.device(g_tok.device), _Timed("pool2x2_sum", 3.0 * N * h * w * C, g_tok.device):
+        _check(L.mvi_rows_pool2x2_sum(gc.data_ptr(), out.data_ptr(), N, h, w, C, _DT.get(g_tok.dtype, -1), _stream(g_tok.device)), "pool2x2_sum")
+    return out
+
+
 def conv3t_n320(tok, weight_taps, bias, T, split=True, gn=None, kind="conv3t_n320"):
     """(3, 1, 1) / padding (1, 0, 0) convolution over the frame axis of token-major activations tok [(b T), S, C_in] (frames of a video
     consecutive) -> [(b T), S, C_out]; weight_taps from conv3t_n320_weight. gn: as conv3x3_n320 (a sample = a frame).

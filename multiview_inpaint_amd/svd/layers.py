@@ -282,6 +282,12 @@ class Upsample(nn.Module):
                 y = conv3x3_planes_via_tokens(self.conv, x, upsample=2)      # upsampling folded into the layout change
                 if y is not None:
                     return y
+                if _resample_conv_bwd_ok(self.conv, x, up=True):
+                    # under autograd with a frozen convolution: the HIP forward and input gradient; the 4x tensor is never built
+                    # or kept. The layout changes are plain copies autograd differentiates.
+                    N, C, H, W = x.shape
+                    t = ops.conv3x3_up_tokens(x.permute(0, 2, 3, 1).reshape(N, H * W, C), self.conv.weight, self.conv.bias, H, W)
+                    return t.transpose(1, 2).reshape(N, self.conv.out_channels, 2 * H, 2 * W)
             x = F.interpolate(x, scale_factor=s, mode="nearest")
         return self.conv(x) if self.use_conv else x
 
@@ -313,6 +319,11 @@ class Downsample(nn.Module):
             y = conv3x3_planes_via_tokens(self.op, x)                        # the stride-2 convolution on tokens
             if y is not None:
                 return y
+            if _resample_conv_bwd_ok(self.op, x, up=False):
+                # under autograd: the HIP forward, input gradient and weight gradient; the layout changes are plain copies
+                N, C, H, W = x.shape
+                t = ops.conv3x3_down_tokens(x.permute(0, 2, 3, 1).reshape(N, H * W, C), self.op.weight, self.op.bias, H, W)
+                return t.transpose(1, 2).reshape(N, self.op.out_channels, H // 2, W // 2)
         return self.op(x)
 
 
@@ -684,6 +695,43 @@ RESBLOCK_CONV_BWD = os.environ.get("MVI_RESBLOCK_CONV_BWD", "0") == "1"
 # layers.TIME_STACK_CONV_BWD = True; VideoResBlock._time_stack_tokens_autograd). Off by default — a tested opt-in
 # (tests/test_conv3t_bwd_gpu.py); ops.conv3t_backward_pays routes nothing yet (no class won tools/bench_conv3t_bwd.py), so neither does this.
 TIME_STACK_CONV_BWD = os.environ.get("MVI_TIME_STACK_CONV_BWD", "0") == "1"
+
+
+# Downsample / Upsample on NCHW planes under autograd with their convolution on ops.conv3x3_down_tokens / ops.conv3x3_up_tokens
+# (MVI_RESAMPLE_CONV_BWD_ROUTE=1, or layers.RESAMPLE_CONV_BWD = True). Off by default — a tested opt-in like RESBLOCK_CONV_BWD
+# (tests/test_resample_conv_bwd_gpu.py); the existing suite has not been run with it on, which is the other condition for the default.
+RESAMPLE_CONV_BWD = os.environ.get("MVI_RESAMPLE_CONV_BWD_ROUTE", "0") == "1"
+# The module lines of tools/bench_resample_conv_bwd.py (profiles/resample_conv_bwd_bench.json; bf16, N = 14, the layout copies around the op
+# included) that won: (module, H, W, C, trainable) with H x W the Downsample's input / the Upsample's output. The trainable Downsamples of
+# 320 and 640 channels LOST there (1.239 against 0.803 ms, 0.927 against 0.645: the two copies cost more than the kernels gain), the frozen
+# Downsample was not measured as a module: neither is routed.
+RESAMPLE_CONV_BWD_ROUTED = {("down", 18, 32, 1280, True), ("up", 72, 128, 320, False), ("up", 36, 64, 640, False), ("up", 18, 32, 1280, False)}
+
+
+def resample_conv_module_pays(which, N, H, W, C, dtype, trains):
+    """The module route's own speed decision, on top of the op's (ops.conv3x3_*_backward_pays): only what its bench line showed ahead."""
+    return N == 14 and dtype == torch.bfloat16 and (which, H, W, C, bool(trains)) in RESAMPLE_CONV_BWD_ROUTED
+
+
+def _resample_conv_bwd_ok(conv, x, up):
+    """Under autograd: does this Downsample.op (up = False) / Upsample.conv (up = True) pass the conditions of its ops.conv3x3_*_tokens
+    (switches, the kernels' gates, the speed decision; the upsampling form only with a frozen convolution)?"""
+    if not (RESAMPLE_CONV_BWD and ops.RESAMPLE_CONV_BACKWARD and torch.is_grad_enabled() and x.is_cuda and x.dim() == 4
+            and x.dtype in (torch.bfloat16, torch.float16) and isinstance(conv, nn.Conv2d) and conv.weight.dtype == x.dtype
+            and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == ((1, 1) if up else (2, 2)) and tuple(conv.padding) == (1, 1)
+            and tuple(conv.dilation) == (1, 1) and conv.groups == 1):
+        return False
+    trains = any(p.requires_grad for p in conv.parameters())
+    if not (x.requires_grad or trains):
+        return False
+    N, C, H, W = x.shape
+    if up:
+        return (not trains and ops.conv3x3_up_tokens_gates(N, H, W, C, conv.out_channels, x.dtype)
+                and ops.conv3x3_up_backward_pays(N, H, W, C, conv.out_channels, x.dtype)
+                and resample_conv_module_pays("up", N, 2 * H, 2 * W, C, x.dtype, False))
+    return (ops.conv3x3_down_tokens_gates(N, H, W, C, conv.out_channels, x.dtype)
+            and ops.conv3x3_down_backward_pays(N, H, W, C, conv.out_channels, x.dtype, conv.weight.requires_grad)
+            and resample_conv_module_pays("down", N, H, W, C, x.dtype, trains))
 
 
 def _conv_bwd_path_ok(self, x, emb):

@@ -959,6 +959,189 @@ def conv3x3_tokens(tok, weight, H, W):
     return y.permute(0, 2, 3, 1).reshape(N, S, Co)
 
 
+# The two resampling forms of that convolution under autograd — stride 2 (Downsample.op) and the convolution of the nearest-neighbour 2x
+# upsampled image (Upsample.conv) — on token-major activations: forwards on csrc/linear_n320.hip as at inference; the stride-2 input
+# gradient on its zero-stuffed-source form (mvi_conv3x3_s2_dgrad), the stride-2 weight gradient on csrc/conv3x3_wgrad.hip's stride-2
+# form, the upsampling form's input gradient as the stride-1 dgrad at 2 h x 2 w + mvi_rows_pool2x2_sum. MVI_RESAMPLE_CONV_BWD=0 (or
+# ops.RESAMPLE_CONV_BACKWARD = False): both take PyTorch-ROCm's F.conv2d (F.interpolate + F.conv2d) under autograd again.
+RESAMPLE_CONV_BACKWARD = os.environ.get("MVI_RESAMPLE_CONV_BWD", "1") != "0"
+RESAMPLE_CONV_MIN_BLOCKS = 128           # the forward's fill-the-chip line (layers.CONV_N320_MIN_BLOCKS); the s2 dgrad has no K split
+# Classes tools/bench_resample_conv_bwd.py showed to win (profiles/resample_conv_bwd_bench.json): {(H, W, C, need_dweight): the batch
+# sizes N measured ahead, in bf16 AND f16 (the two types had the same verdicts)}; C -> C channels, H x W is the Downsample's input /
+# the Upsample's output. Unmeasured classes — any other size, channel count or batch — are not routed.
+_B16 = (torch.bfloat16, torch.float16)
+CONV3X3_DOWN_BACKWARD_ROUTED = {(72, 128, 320, False): (14, 28), (36, 64, 640, False): (14, 28), (18, 32, 1280, False): (14, 28),
+                                (72, 128, 320, True): (14, 28), (18, 32, 1280, True): (14,)}
+CONV3X3_UP_BACKWARD_ROUTED = {(72, 128, 320, False): (14, 28), (36, 64, 640, False): (14, 28), (18, 32, 1280, False): (14, 28)}
+
+
+def conv3x3_down_backward_pays(N, H, W, C_in, C_out, dtype, need_dweight):
+    """Whether forward + backward of the stride-2 convolution on the HIP kernels is faster than F.conv2d(stride 2) under autograd on NCHW
+    planes (what the training path runs today) for this shape class — the routing's second question after conv3x3_down_tokens_gates.
+    The project's standing rule: a class goes to HIP only where tools/bench_resample_conv_bwd.py measured its median ahead of the
+    PyTorch route's by more than that route's spread (forward + backward by device events, the two routes alternating in one process,
+    9 pairs, medians); unmeasured classes are not routed. ms HIP / PyTorch (spread), dx only | all gradients, bf16, C -> C:
+      N = 14  72x128  320   0.359 / 0.522 (0.017) | 0.694 / 0.810 (0.047)    wins | wins
+      N = 14  36x64   640   0.331 / 0.422 (0.022) | 0.650 / 0.629 (0.019)    wins | LOSES
+      N = 14  18x32  1280   0.484 / 0.786 (0.043) | 0.806 / 1.041 (0.021)    wins | wins
+      N = 28  72x128  320   0.523 / 0.960 (0.020) | 1.093 / 1.529 (0.037)    wins | wins
+      N = 28  36x64   640   0.526 / 0.666 (0.036) | 1.110 / 0.944 (0.019)    wins | LOSES
+      N = 28  18x32  1280   0.525 / 0.702 (0.042) | 1.135 / 1.022 (0.011)    wins | LOSES
+    f16 (the JSON): the same verdicts. dx only — the frozen UNet's Downsamples — won everywhere; with the weight gradient the 640-channel
+    level and, at N = 28, the 1280-channel level lose: the stride-2 weight-gradient kernel runs at 0.10 of the matrix peak (0.24 ms at
+    N = 14 whatever the level) where the library's is faster. One run on one machine."""
+    ns = CONV3X3_DOWN_BACKWARD_ROUTED.get((H, W, C_in, bool(need_dweight))) if C_in == C_out and dtype in _B16 else None
+    return ns is not None and N in ns
+
+
+def conv3x3_up_backward_pays(N, h, w, C_in, C_out, dtype):
+    """The same question for the upsampling form (frozen weight: dx only) against F.conv2d(F.interpolate(x)) under autograd; h x w is the
+    SOURCE size, the table is keyed by the output size 2 h x 2 w. ms HIP / PyTorch (spread), bf16, N = 14 | N = 28 (f16: the JSON, same
+    verdicts):
+      36x64 -> 72x128  320   0.485 / 1.545 (0.067) | 0.842 / 3.125 (0.052)    wins
+      18x32 -> 36x64   640   0.442 / 0.970 (0.041) | 0.811 / 1.774 (0.044)    wins
+       9x16 -> 18x32  1280   0.694 / 1.000 (0.036) | 0.750 / 1.689 (0.066)    wins
+    Every measured class won: the PyTorch route writes, convolves and keeps the 4x tensor. One run on one machine."""
+    ns = CONV3X3_UP_BACKWARD_ROUTED.get((2 * h, 2 * w, C_in, False)) if C_in == C_out and dtype in _B16 else None
+    return ns is not None and N in ns
+
+
+def conv3x3_down_tokens_gates(N, H, W, C_in, C_out, dtype):
+    """Do the three launches of _Conv3x3DownTokensFn take this shape? Even H and W; the forward's conditions at stride 2 (channel gate,
+    32-bit byte offsets, enough blocks or a K split); the input gradient's with the channel roles swapped (C_in a multiple of 320,
+    C_out of 64; it has no K split, so its N H W / 256 row blocks x C_in / 320 column groups alone must reach the line); and the
+    weight-gradient kernel's gate."""
+    from . import hip_ops
+    rows = N * H * W
+    return (dtype in (torch.bfloat16, torch.float16) and rows > 0 and H % 2 == 0 and W % 2 == 0
+            and hip_ops.conv3x3_n320_supported(C_in, C_out, dtype) and hip_ops.conv3x3_s2_dgrad_supported(C_in, C_out, dtype)
+            and rows * max(C_in, C_out) * 2 < 2 ** 32
+            and hip_ops.conv3x3_n320_fills_chip(N, H, W, C_in, C_out, RESAMPLE_CONV_MIN_BLOCKS, stride=2)
+            and -(-rows // 256) * (C_in // 320) >= RESAMPLE_CONV_MIN_BLOCKS
+            and hip_ops.conv3x3_s2_wgrad_supported(C_in, C_out, dtype) and W <= hip_ops.CONV3X3_WGRAD_MAX_W)
+
+
+def conv3x3_up_tokens_gates(N, h, w, C_in, C_out, dtype):
+    """Do the launches of _Conv3x3UpTokensFn take this shape (h x w: the source)? The upsampling forward's conditions at 2 h x 2 w, the
+    stride-1 input gradient's there with the channel roles swapped, and the pooling pass's (C_in a multiple of 8: implied)."""
+    from . import hip_ops
+    rows = N * 4 * h * w
+    return (dtype in (torch.bfloat16, torch.float16) and rows > 0
+            and hip_ops.conv3x3_n320_supported(C_in, C_out, dtype) and hip_ops.conv3x3_n320_supported(C_out, C_in, dtype)
+            and rows * max(C_in, C_out) * 2 < 2 ** 32
+            and -(-rows // 256) * (C_out // 320) >= RESAMPLE_CONV_MIN_BLOCKS
+            and hip_ops.conv3x3_n320_fills_chip(N, 2 * h, 2 * w, C_out, C_in, RESAMPLE_CONV_MIN_BLOCKS))
+
+
+class _Conv3x3DownTokensFn(torch.autograd.Function):
+    """conv3x3_down_tokens on the implicit-GEMM kernel (stride 2, the bias in its accumulators: the inference launch, so y has the same
+    bits) with a deterministic HIP backward: dx = conv3x3(zero-stuffed dy, W') (hip_ops.conv3x3_s2_dgrad), dweight =
+    hip_ops.conv3x3_s2_wgrad, dbias = the fp32 sum of dy over rows. Holds tok and weight only; nothing is cached outside ctx, so
+    torch.utils.checkpoint may re-run the forward."""
+
+    @staticmethod
+    def forward(ctx, tok, weight, bias, H, W):
+        from . import hip_ops
+        ctx.save_for_backward(tok, weight)
+        ctx.hw = (H, W)
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), bias, H, W, stride=2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        tok, weight = ctx.saved_tensors
+        H, W = ctx.hw
+        n = ctx.needs_input_grad
+        dy = dy if dy.is_contiguous() else dy.contiguous()
+        dx = hip_ops.conv3x3_s2_dgrad(dy, _conv3x3_packed_transposed(weight), H, W) if n[0] else None
+        dw = hip_ops.conv3x3_s2_wgrad(tok, dy, H, W).to(weight.dtype) if n[1] else None
+        db = dy.sum(dim=(0, 1), dtype=torch.float32).to(ctx.bias_dtype) if n[2] else None
+        return dx, dw, db, None, None
+
+
+class _Conv3x3UpTokensFn(torch.autograd.Function):
+    """conv3x3_up_tokens on the upsampling form of the implicit-GEMM kernel (the inference launch) with a frozen weight: dx is the
+    stride-1 input gradient at 2 h x 2 w summed over every 2x2 cell (hip_ops.conv3x3_dgrad + hip_ops.pool2x2_sum). Holds the weight only:
+    neither the input nor the 4x upsampled activation is kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, tok, weight, bias, h, w):
+        from . import hip_ops
+        ctx.save_for_backward(weight)
+        ctx.hw = (h, w)
+        return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), bias, h, w, up2=True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        weight, = ctx.saved_tensors
+        h, w = ctx.hw
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        return conv3x3_up_dgrad(dy, weight, h, w), None, None, None, None
+
+
+def conv3x3_up_dgrad(dy, weight, h, w):
+    """dx [N, h w, C_in] of conv3x3_up_tokens from dy [N, (2 h)(2 w), C_out] — _Conv3x3UpTokensFn's backward: the stride-1 input gradient
+    at 2 h x 2 w on the forward kernel, then the sum over every 2x2 cell (one more rounding than a bare dgrad)."""
+    from . import hip_ops
+    dy = dy if dy.is_contiguous() else dy.contiguous()
+    g = hip_ops.conv3x3_dgrad(dy, _conv3x3_packed_transposed(weight), 2 * h, 2 * w)
+    return hip_ops.pool2x2_sum(g, h, w)
+
+
+def conv3x3_down_tokens(tok, weight, bias, H, W):
+    """3x3 / padding 1 / STRIDE 2 convolution (Downsample.op) of token-major activations tok [N, H W, C_in] with weight [C_out, C_in, 3, 3]
+    and bias [C_out] or None -> [N, Ho Wo, C_out], Ho = (H - 1) // 2 + 1. Without autograd: the implicit-GEMM kernel. Under autograd:
+    _Conv3x3DownTokensFn where the switch is on, the launches take the shape (conv3x3_down_tokens_gates) and conv3x3_down_backward_pays
+    says so; anything else is F.conv2d on the channels-last view (a recorded fallback; strict mode raises) — also the CPU path."""
+    N, S, C = tok.shape
+    Co = weight.shape[0]
+    if S != H * W or tuple(weight.shape[1:]) != (C, 3, 3):
+        raise ValueError("conv3x3_down_tokens: tok [N, H W, C_in] and weight [C_out, C_in, 3, 3] expected")
+    if tok.is_cuda and tok.dtype == weight.dtype:
+        from . import hip_ops
+        if not _needs_autograd(tok, weight, bias):
+            if (tok.dtype in (torch.bfloat16, torch.float16) and N * S > 0 and hip_ops.conv3x3_n320_supported(C, Co, tok.dtype)
+                    and N * S * C * 2 < 2 ** 32 and hip_ops.conv3x3_n320_fills_chip(N, H, W, C, Co, RESAMPLE_CONV_MIN_BLOCKS, stride=2)):
+                return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), bias, H, W, stride=2)
+        elif RESAMPLE_CONV_BACKWARD and conv3x3_down_tokens_gates(N, H, W, C, Co, tok.dtype) \
+                and conv3x3_down_backward_pays(N, H, W, C, Co, tok.dtype, weight.requires_grad):
+            return _Conv3x3DownTokensFn.apply(tok, weight, bias, H, W)
+    _fallback(tok, "conv3x3_down_tokens", _why(tok, weight, bias))
+    x = tok.view(N, H, W, C).permute(0, 3, 1, 2)                  # [N, C, H, W] with channels-last strides: no copy
+    y = F.conv2d(x, weight, bias, 2, 1)
+    return y.permute(0, 2, 3, 1).reshape(N, y.shape[2] * y.shape[3], Co)
+
+
+def conv3x3_up_tokens(tok, weight, bias, h, w):
+    """conv3x3(nearest 2x upsampling of x) (Upsample.conv) of token-major activations tok [N, h w, C_in] -> [N, (2 h)(2 w), C_out]. Without
+    autograd: the upsampling form of the implicit-GEMM kernel. Under autograd with a FROZEN weight and bias: _Conv3x3UpTokensFn where the
+    switch is on, the launches take the shape (conv3x3_up_tokens_gates) and conv3x3_up_backward_pays says so. Anything else — a
+    trainable weight or bias among it: this form's weight gradient is not built, no trained network has an Upsample — is
+    F.conv2d(F.interpolate(x)) on the channels-last view (a recorded fallback; strict mode raises) — also the CPU path."""
+    N, S, C = tok.shape
+    Co = weight.shape[0]
+    if S != h * w or tuple(weight.shape[1:]) != (C, 3, 3):
+        raise ValueError("conv3x3_up_tokens: tok [N, h w, C_in] and weight [C_out, C_in, 3, 3] expected")
+    if tok.is_cuda and tok.dtype == weight.dtype:
+        from . import hip_ops
+        if not _needs_autograd(tok, weight, bias):
+            if (tok.dtype in (torch.bfloat16, torch.float16) and N * S > 0 and hip_ops.conv3x3_n320_supported(C, Co, tok.dtype)
+                    and 4 * N * S * C * 2 < 2 ** 32 and -(-4 * N * S // 256) * (Co // 320) >= RESAMPLE_CONV_MIN_BLOCKS):
+                return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), bias, h, w, up2=True)
+        elif RESAMPLE_CONV_BACKWARD and not _needs_autograd(weight, bias) and conv3x3_up_tokens_gates(N, h, w, C, Co, tok.dtype) \
+                and conv3x3_up_backward_pays(N, h, w, C, Co, tok.dtype):
+            return _Conv3x3UpTokensFn.apply(tok, weight, bias, h, w)
+    _fallback(tok, "conv3x3_up_tokens", _why(tok, weight, bias))
+    x = tok.view(N, h, w, C).permute(0, 3, 1, 2)
+    y = F.conv2d(F.interpolate(x, scale_factor=2, mode="nearest"), weight, bias, 1, 1)
+    return y.permute(0, 2, 3, 1).reshape(N, 4 * S, Co)
+
+
 # The (3, 1, 1) / padding (1, 0, 0) frame convolution of token-major activations under autograd (VideoResBlock.time_stack): forward and
 # input gradient on csrc/linear_n320.hip's three-tap implicit GEMM, weight gradient on csrc/conv3t_wgrad.hip. MVI_CONV3T_BWD=0 (or
 # ops.CONV3T_BACKWARD = False): a frame convolution that requires grad takes PyTorch-ROCm's F.conv3d again.
