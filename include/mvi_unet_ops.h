@@ -262,6 +262,20 @@ size_t mvi_conv3x3_wgrad_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_
 int mvi_conv3x3_wgrad(const void* x, const void* dy, float* dweight, int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out,
                       int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Weight and bias gradient of a projection y = x W^T + b, W [out_features, K] (training: csrc/linear_wgrad.hip):
+ *     dweight[n][k] = sum over r of dy[r, n] * x[r, k]          dbias[n] = sum over r of dy[r, n]   (dbias may be NULL)
+ * x [rows, K] and dy [rows, out_features] in one 16-bit dtype with row strides in ELEMENTS (a column range of a wider matrix is taken
+ * as it lies: each stride covers its row, is a multiple of 8 and below 2^24), 16-byte aligned; dweight and dbias fp32, every element
+ * written once (rows = 0: zeros). K and out_features multiples of 64, bf16 / f16 (fp32 is declined with the invalid-argument
+ * status). No atomics: where the 128 x 128 output tiles alone would not fill the chip the row axis is split over blocks that write
+ * fp32 partials to `workspace` (16-byte aligned, at least ..._workspace_bytes(), a pure function of the shape; 0 = no split) and a
+ * second launch adds them in slice order, so two calls return identical bits. workspace NULL with workspace_bytes 0 asks for the
+ * unsplit launch; a workspace that is given but shorter than ..._workspace_bytes() is declined, nothing is launched. */
+int mvi_linear_wgrad_supported(int32_t K, int32_t out_features, int32_t dtype);
+size_t mvi_linear_wgrad_workspace_bytes(int64_t rows, int32_t K, int32_t out_features);
+int mvi_linear_wgrad(const void* x, const void* dy, float* dweight, float* dbias, int64_t rows, int32_t K, int32_t out_features,
+                     int64_t x_row_stride, int64_t dy_row_stride, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The 3x3 / STRIDE 2 / padding 1 convolution y = conv(x, W) under autograd (training: Downsample.op), H and W even. With z = dy
  * zero-stuffed to H x W (z[2 r, 2 c] = dy[r, c], 0 elsewhere; never in memory) and W'[ci][co][ky][kx] = W[co][ci][2 - ky][2 - kx]:
  *   mvi_conv3x3_s2_dgrad: dx = conv3x3(z, W', padding 1, stride 1) on csrc/linear_n320.hip (the upsampling form's half-size source

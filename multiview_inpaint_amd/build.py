@@ -26,7 +26,8 @@ _ATTN = ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"] + os.environ.get
 # than the scalar adds they replace (MI355X_MICROARCH.md, cycle constants)
 EXTRA = {"attn_flash.hip": _ATTN, "attn_flash8m16.hip": _ATTN + ["-fno-slp-vectorize"], "ff_geglu.hip": _ATTN + ["-fno-slp-vectorize"],
          "linear_n320.hip": _ATTN + ["-fno-slp-vectorize"], "attn_bwd.hip": _ATTN, "ff_geglu_bwd.hip": _ATTN,
-         "conv3x3_wgrad.hip": _ATTN, "conv3t_wgrad.hip": _ATTN, "stem_conv_bwd.hip": _ATTN}
+         "conv3x3_wgrad.hip": _ATTN, "conv3t_wgrad.hip": _ATTN, "stem_conv_bwd.hip": _ATTN,
+         "linear_wgrad.hip": _ATTN}
 
 
 def sources():

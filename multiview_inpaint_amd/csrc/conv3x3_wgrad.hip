@@ -154,21 +154,13 @@ void conv3x3_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, flo
             const uint32_t so = (uint32_t)(32 * st * kRow);
             frag a[4];
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(ldy + so + tr + 32 * mt));
-                s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(ldy + so + tr + 32 * mt + 16 * kRow));
-                const u32x2 l = *reinterpret_cast<u32x2*>(&lo4), h = *reinterpret_cast<u32x2*>(&hi4);
-                a[mt] = as_frag<frag>(u32x4{l[0], l[1], h[0], h[1]});
-            }
+            for (int mt = 0; mt < 4; ++mt) a[mt] = read_frag_tr<frag>(ldy + so + tr + 32 * mt, 16 * kRow);
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 // kS2: tap (ky, kx) = plane (ky != 1, kx != 1) at offset (ky == 2) P + (kx == 2)
                 const uint32_t to = so + tr_b + (kS2 ? (uint32_t)((pl_base[2 * (t / 3 != 1) + (t % 3 != 1)] + (t / 3 == 2 ? P : 0) + (t % 3 == 2)) * kRow)
                                                      : (uint32_t)(((t / 3) * P + t % 3) * kRow));
-                s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(lx + to));
-                s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(lx + to + 16 * kRow));
-                const u32x2 l = *reinterpret_cast<u32x2*>(&lo4), h = *reinterpret_cast<u32x2*>(&hi4);
-                const frag b = as_frag<frag>(u32x4{l[0], l[1], h[0], h[1]});
+                const frag b = read_frag_tr<frag>(lx + to, 16 * kRow);
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt) acc[t][mt] = M::mfma(a[mt], b, acc[t][mt]);
             }

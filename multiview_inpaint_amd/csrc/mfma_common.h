@@ -75,6 +75,17 @@ template <> struct MmaTied16<__half> : MmaType<__half> {
 
 template <typename F> __device__ __forceinline__ F as_frag(u32x4 v) { return *reinterpret_cast<F*>(&v); }
 
+// An MFMA operand fragment read TRANSPOSED from a row-major [contraction row][channel] LDS image (the weight-gradient kernels: both
+// operands are contracted along their slow index): two ds_read_b64_tr_b16, each a 16-row x 16-channel block of which lane 4 q + p
+// of 16-lane group g addresses row 4 g + q, channels 4 p .. 4 p + 3 (p is the lane's own address); hi_bytes = 16 rows further on.
+// Element j of lane (c, g) is row (j < 4 ? 4 g + j : 16 + 4 g + j - 4) of the 32-row step at channel c.
+template <typename F> __device__ __forceinline__ F read_frag_tr(MVI_AS3 char* p, uint32_t hi_bytes) {
+    s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)p);
+    s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(p + hi_bytes));
+    const u32x2 l = *reinterpret_cast<u32x2*>(&lo4), h = *reinterpret_cast<u32x2*>(&hi4);
+    return as_frag<F>(u32x4{l[0], l[1], h[0], h[1]});
+}
+
 // One LDS-DMA piece: every lane moves 16 bytes from sbase + voff to LDS address (m0 + 16 * lane); sbase is wave-uniform (scalar
 // registers). Invisible to the compiler's wait-count bookkeeping on purpose: the kernels count their own vmcnt (a builtin DMA makes
 // hipcc put s_waitcnt vmcnt(0) in front of every later LDS read, which serialises a ring of tiles).

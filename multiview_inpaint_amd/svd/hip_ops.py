@@ -16,7 +16,8 @@ _ws = {}
 # "groupnorm_stats_fwd" and "groupnorm_bwd" ("groupnorm_bwd_params" when the call also launched the dweight / dbias kernel), the
 # token-major norm as "groupnorm_tok2tok_stats_fwd" and "groupnorm_tok2tok_bwd" / "groupnorm_tok2tok_bwd_params",
 # GEGLU under autograd as "ff_geglu" + "ff_geglu_bwd" (the kernel alone) + "ff_geglu_dparams" (for trainable parameters: the library's
-# dweight GEMM and the dbias sum on the kernel's dh), or "geglu" + "geglu_bwd".
+# dweight GEMM and the dbias sum on the kernel's dh), or "geglu" + "geglu_bwd"; a projection under autograd (ops._LinearFn) as its forward kind +
+# "linear_dgrad_n320" / "linear_dgrad_k320" (the forward kernels on the transposed weight) + "linear_wgrad" (dweight and dbias, one kind).
 PROFILE = None
 # When a list: every attention call appends (kernel variant, Sq, Sk) — 0 rowtile, 4 / 16 = the 4- / 8-wave MFMA kernel
 # (mvi_attention_kernel_variant, the function the C dispatch itself uses). The parity tests assert from it WHICH kernel ran
@@ -585,13 +586,14 @@ def linear_k320_supported(K, out_features, dtype):
     return dtype in (torch.bfloat16, torch.float16) and bool(_lib.lib().mvi_linear_k320_supported(int(K), int(out_features), _DT[dtype]))
 
 
-def linear_k320(x, weight, bias):
-    """F.linear(x, weight, bias) for K = 320 on the MFMA kernel of ff_geglu (plain epilogue): x [..., 320], weight [N, 320]."""
+def linear_k320(x, weight, bias, kind="linear_k320"):
+    """F.linear(x, weight, bias) for K = 320 on the MFMA kernel of ff_geglu (plain epilogue): x [..., 320], weight [N, 320]. `kind`
+    names the launch in PROFILE (linear_dgrad: the same kernel as an input gradient)."""
     L = _lib.lib()
     K, N = x.shape[-1], weight.shape[0]
     xc, wc, b, rows, cap = _rows_operands(x, weight, bias, True)
     full = torch.empty(cap, N, dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device), _Timed("linear_k320", float(rows) * (K + N) * x.element_size(), x.device):
+    with torch.cuda.device(x.device), _Timed(kind, float(rows) * (K + N) * x.element_size(), x.device):
         _check(L.mvi_linear_k320(xc.data_ptr(), wc.data_ptr(), _ptr(b), full.data_ptr(), rows, cap, K, N, xc.stride(0), full.stride(0), _DT[x.dtype],
                                  _stream(x.device)), "linear_k320")
     return full[:rows].reshape(*x.shape[:-1], N)
@@ -601,16 +603,87 @@ def linear_n320_supported(K, out_features, dtype):
     return dtype in (torch.bfloat16, torch.float16) and bool(_lib.lib().mvi_linear_n320_supported(int(K), int(out_features), _DT[dtype]))
 
 
-def linear_n320(x, weight, bias):
-    """F.linear(x, weight, bias) for 320 outputs and K a multiple of 64 (csrc/linear_n320.hip): x [..., K], weight [320, K]."""
+def linear_n320(x, weight, bias, kind="linear_n320"):
+    """F.linear(x, weight, bias) for 320 outputs and K a multiple of 64 (csrc/linear_n320.hip): x [..., K], weight [320, K]. `kind`
+    names the launch in PROFILE (linear_dgrad: the same kernel as an input gradient)."""
     L = _lib.lib()
     K, N = x.shape[-1], weight.shape[0]
     xc, wc, b, rows, cap = _rows_operands(x, weight, bias, False)
     full = torch.empty(cap, N, dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device), _Timed("linear_n320", 2.0 * rows * K * N, x.device):
+    with torch.cuda.device(x.device), _Timed(kind, 2.0 * rows * K * N, x.device):
         _check(L.mvi_linear_n320(xc.data_ptr(), wc.data_ptr(), _ptr(b), full.data_ptr(), rows, cap, K, N, xc.stride(0), full.stride(0), _DT[x.dtype],
                                  _stream(x.device)), "linear_n320")
     return full[:rows].reshape(*x.shape[:-1], N)
+
+
+# ---- the projections under autograd (ops._LinearFn): dgrad on the forward kernels, wgrad + dbias in csrc/linear_wgrad.hip --------------
+
+N320_GROUP_WIDTHS = (640, 1280)                 # ops.linear prefers linear_n320 into these widths (its measured classes)
+
+
+def linear_dgrad_kernel(K, out_features, dtype):
+    """Which forward kernel computes dx = dy . W for a forward with W [out_features, K] — a projection with weight W^T [K, out_features],
+    contraction out_features, K outputs — in ops.linear's order of preference: 'n320' into 640 / 1280 channels and for 320 -> 320,
+    then 'k320', then 'n320'; None where neither takes the shape."""
+    n320 = linear_n320_supported(out_features, K, dtype)
+    if n320 and (K in N320_GROUP_WIDTHS or (K == 320 and out_features == 320)):
+        return "n320"
+    if linear_k320_supported(out_features, K, dtype):
+        return "k320"
+    return "n320" if n320 else None
+
+
+def linear_dgrad(dy, weight_t, bias=None):
+    """dx [..., K] of y = F.linear(x, W) for the upstream gradient dy [..., N]: the forward kernel on weight_t = W^T [K, N] (contiguous).
+    PROFILE kind linear_dgrad_n320 / linear_dgrad_k320 (linear_dgrad_kernel's choice); raises where neither kernel takes the shape."""
+    if weight_t.dim() != 2 or weight_t.shape[1] != dy.shape[-1] or weight_t.dtype != dy.dtype:
+        raise ValueError("linear_dgrad: dy [..., N] and weight_t [K, N] of one dtype expected")
+    which = linear_dgrad_kernel(weight_t.shape[0], weight_t.shape[1], dy.dtype)
+    if which is None:
+        raise ValueError(f"linear_dgrad: no kernel for a contraction of {weight_t.shape[1]} into {weight_t.shape[0]} outputs in {dy.dtype}")
+    if which == "n320":
+        return linear_n320(dy, weight_t, bias, kind="linear_dgrad_n320")
+    return linear_k320(dy, weight_t, bias, kind="linear_dgrad_k320")
+
+
+def linear_wgrad_supported(K, out_features, dtype):
+    return dtype in (torch.bfloat16, torch.float16) and bool(_lib.lib().mvi_linear_wgrad_supported(int(K), int(out_features), _DT[dtype]))
+
+
+def linear_wgrad_workspace_bytes(rows, K, out_features):
+    """> 0: csrc/linear_wgrad.hip splits the row axis of this shape over blocks (a pure host function of the shape)."""
+    return int(_lib.lib().mvi_linear_wgrad_workspace_bytes(int(rows), int(K), int(out_features)))
+
+
+def _rows16(t):
+    """t [..., C] as [rows, C] with unit column stride, rows 16-byte aligned at a stride linear_wgrad.hip takes; a copy only otherwise."""
+    t2 = t.reshape(-1, t.shape[-1])
+    if t2.stride(1) != 1 or t2.stride(0) % 8 or t2.stride(0) < t2.shape[1] or t2.stride(0) >= 1 << 24 or t2.data_ptr() % 16:
+        t2 = t2.contiguous()
+        if t2.data_ptr() % 16:
+            t2 = t2.clone()
+    return t2
+
+
+def linear_wgrad(x, dy, need_dbias, split=True):
+    """(dweight fp32 [N, K], dbias fp32 [N] or None) of y = F.linear(x, W, b) from x [..., K] and the output gradient dy [..., N] (one
+    16-bit dtype; row-strided views such as a third of the packed q | k | v output are read in place): csrc/linear_wgrad.hip, one
+    launch for both (plus the fixed-order sum of the row slices), deterministic. split = False withholds the workspace (the unsplit
+    launch). PROFILE kind linear_wgrad."""
+    L = _lib.lib()
+    if x.dtype != dy.dtype or x.shape[:-1] != dy.shape[:-1]:
+        raise ValueError("linear_wgrad: x [..., K] and dy [..., N] of one dtype and the same leading shape expected")
+    xc, dc = _rows16(x), _rows16(dy)
+    rows, K = xc.shape
+    N = dc.shape[1]
+    dw = torch.empty(N, K, dtype=torch.float32, device=x.device)
+    db = torch.empty(N, dtype=torch.float32, device=x.device) if need_dbias else None
+    ws_bytes = int(L.mvi_linear_wgrad_workspace_bytes(rows, K, N)) if split else 0
+    ws = _workspace(x.device, ws_bytes) if ws_bytes else None
+    with torch.cuda.device(x.device), _Timed("linear_wgrad", 2.0 * rows * K * N, x.device):
+        _check(L.mvi_linear_wgrad(xc.data_ptr(), dc.data_ptr(), dw.data_ptr(), _ptr(db), rows, K, N, xc.stride(0), dc.stride(0),
+                                  _DT.get(x.dtype, -1), _ptr(ws), ws_bytes, _stream(x.device)), "linear_wgrad")
+    return dw, db
 
 
 def linear_n320_add_layer_norm(x, weight, bias, ln_weight, ln_bias, eps, resid=None, row=None, ret_pre=False):

@@ -20,9 +20,12 @@ gradient), where `conv3t_backward_pays` says so; VideoResBlock reaches it throug
 The 16- / 32-channel conv + SiLU layers of the ControlNet hint stem have one as well (`stem_conv3x3_silu`: dz on csrc/stem_conv.hip's second
 epilogue, weight / bias gradient on csrc/stem_conv_bwd.hip), where `stem_conv_backward_pays` says so; ControlNet._hint_stem reaches it
 through the opt-in unet.HINT_STEM_BWD.
+The projections have one behind a switch that is off by default (`linear` with MVI_LINEAR_BWD=1: the forward on the kernel inference
+launches, the input gradient on the forward kernels with the transposed weight, weight and bias gradient on csrc/linear_wgrad.hip),
+where `linear_gates` and `linear_backward_pays` say so; `linear_module` and `linear_add_layer_norm` under grad reach it through `linear`.
 Every other kernel is forward-only: a GPU tensor that requires grad goes through PyTorch-ROCm's differentiable ops there
-(the projections, the strided and upsampling convolutions — `linear_add_layer_norm` under grad is `linear_module` +
-`add_layer_norm` —, `add_lerp`).
+(the projections without that switch or outside its classes, the cross-attention projections of the context —
+`linear_add_layer_norm` under grad is `linear_module` + `add_layer_norm` —, `add_lerp`).
 
 Reference ops: GroupNorm32 + SiLU (sgm/modules/diffusionmodules/util.py:259-276,
 openaimodel.py:257-261,292-305), Normalize (sgm/modules/attention.py:125-128),
@@ -587,12 +590,127 @@ N320_GROUP_WIDTHS = (640, 1280)
 N320_GROUP_MIN_BLOCKS = 200
 
 
+def _linear_route(rows, K, N, dtype):
+    """The kernel linear() launches WITHOUT autograd for x [rows, K] and weight [N, K] of one 16-bit dtype on the GPU: 'n320', 'k320'
+    or None (the library GEMM) — linear()'s own conditions in its own order."""
+    if not K320_KERNELS:
+        return None
+    from . import hip_ops
+    if N320_KERNEL and N320_GROUPS and N in N320_GROUP_WIDTHS and (rows + 255) // 256 * (N // 320) >= N320_GROUP_MIN_BLOCKS \
+            and hip_ops.linear_n320_supported(K, N, dtype):
+        return "n320"
+    if rows >= FF_GEGLU_MIN_ROWS:
+        n320 = N320_KERNEL and N == 320 and hip_ops.linear_n320_supported(K, N, dtype)
+        if n320 and K == 320:
+            return "n320"
+        if hip_ops.linear_k320_supported(K, N, dtype):
+            return "k320"
+        if n320:
+            return "n320"
+    return None
+
+
+# The projections under autograd: forward on the kernel linear() launches at inference, the input gradient on the forward kernels with
+# the transposed weight (dx = dy W is a projection with weight W^T [K, N]), weight and bias gradient on csrc/linear_wgrad.hip —
+# deterministic, where the library's split-K GEMMs are not run-to-run reproducible. DEFAULT OFF (MVI_LINEAR_BWD=1 or
+# ops.LINEAR_BACKWARD = True turns it on): linear() is called by every transformer block, and off it is exactly the function it was.
+LINEAR_BACKWARD = os.environ.get("MVI_LINEAR_BWD", "0") == "1"
+# Classes tools/bench_linear_bwd.py showed to win (profiles/linear_bwd_bench.json): {(N, K, need_dweight): the smallest measured row
+# count from which every measured size of the class won in both dtypes}. A class that is not listed is not routed.
+LINEAR_BACKWARD_ROUTED = {(320, 320, True): 14 * 9216, (320, 320, False): 28 * 9216, (960, 320, True): 14 * 9216, (960, 320, False): 14 * 9216,
+                          (320, 1280, True): 14 * 9216, (320, 1280, False): 28 * 9216, (640, 640, True): 14 * 2304, (640, 640, False): 28 * 2304,
+                          (1280, 1280, True): 28 * 576}
+
+
+def linear_backward_pays(rows, K, N, dtype, need_dweight):
+    """Whether forward + backward on the HIP kernels is faster than F.linear under autograd for this shape class — the routing's second
+    question after linear_gates. Measured by tools/bench_linear_bwd.py (profiles/linear_bwd_bench.json; DESIGN.md 'Projections under
+    autograd'): forward + backward by device events, the two routes alternating in one process, 9 pairs, medians; a class goes to HIP
+    only where its median beats the F.linear route's by more than that route's spread. ms HIP / PyTorch (spread), dx only | all
+    gradients, bf16 (f16: the JSON):
+      129024 x  320 ->  320   0.239 / 0.193 (0.006) | 0.300 / 0.618 (0.020)    dx only LOSES, all gradients wins
+      258048 x  320 ->  320   0.198 / 0.338 (0.004) | 0.327 / 0.987 (0.011)    wins
+      129024 x  320 ->  960   0.271 / 0.338 (0.050) | 0.438 / 0.817 (0.013)    wins
+      258048 x  320 ->  960   0.390 / 0.613 (0.041) | 0.679 / 1.528 (0.030)    wins
+      129024 x 1280 ->  320   0.334 / 0.365 (0.020) | 0.473 / 0.897 (0.016)    dx only UNSTEADY (lost one of three runs), all gradients wins
+      258048 x 1280 ->  320   0.550 / 0.670 (0.014) | 0.920 / 1.793 (0.067)    wins
+       32256 x  640 ->  640   0.108 / 0.118 (0.007) | 0.165 / 0.306 (0.008)    dx only UNSTEADY (lost two of three runs), all gradients wins
+       64512 x  640 ->  640   0.145 / 0.232 (0.005) | 0.292 / 0.596 (0.045)    wins
+       16128 x 1280 -> 1280   0.173 / 0.188 (0.032) | 0.273 / 0.360 (0.052)    dx only LOSES, all gradients wins
+    The tool ran three times; a class is routed only if it won every time (the small dx-only classes are bound by the host side of two
+    launches and change sides between runs). The other shapes of the list — 640 -> 1920, 2560 -> 640, 1280 -> 3840, 5120 -> 1280 at
+    every size and 1280 -> 1280 at 8064 rows — are outside linear_gates (their forward, or the projection that is their input gradient,
+    is the library's) and were measured for the wgrad kernel alone. Unmeasured classes are not routed. One machine."""
+    lo = LINEAR_BACKWARD_ROUTED.get((N, K, bool(need_dweight)))
+    return lo is not None and rows >= lo
+
+
+def linear_gates(rows, K, N, dtype):
+    """Do the launches of _LinearFn take x [rows, K] and weight [N, K]? The forward's conditions (_linear_route: linear()'s own), the same
+    with K and N swapped for the input gradient, csrc/linear_wgrad.hip's gate (K and N multiples of 64), and byte offsets of the
+    activations inside 32 bits (what the forward kernels address with)."""
+    from . import hip_ops
+    if dtype not in (torch.bfloat16, torch.float16) or rows <= 0 or K <= 0 or N <= 0 or K % 64 or N % 64:
+        return False
+    return (rows * max(K, N) * 2 < 2 ** 32 and _linear_route(rows, K, N, dtype) is not None
+            and _linear_route(rows, N, K, dtype) is not None and hip_ops.linear_dgrad_kernel(K, N, dtype) is not None
+            and hip_ops.linear_wgrad_supported(K, N, dtype))
+
+
+def _linear_transposed(weight):
+    """W^T [K, N], contiguous: the weight of the input gradient. Kept in svd/derived.py's table while the weight is frozen, built from
+    the live tensor while it trains (it changes every step)."""
+    def build(w):
+        return w.detach().t().contiguous()
+    if weight.requires_grad:
+        return build(weight)
+    from .derived import derived1
+    return derived1("linear_transposed", weight, build)
+
+
+class _LinearFn(torch.autograd.Function):
+    """linear() on the kernel it launches without autograd (y is bit-identical to inference) with a deterministic HIP backward: dx is a
+    forward kernel on the transposed weight, dweight and dbias are one launch of csrc/linear_wgrad.hip, each only where asked for.
+    Holds x and weight only; nothing is cached outside ctx, so torch.utils.checkpoint may re-run the forward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        from . import hip_ops
+        ctx.save_for_backward(x, weight)
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        route = _linear_route(x.numel() // max(x.shape[-1], 1), x.shape[-1], weight.shape[0], x.dtype)
+        if route is None:
+            raise HipPathError("linear: _LinearFn reached without a forward kernel for this shape")
+        return (hip_ops.linear_n320 if route == "n320" else hip_ops.linear_k320)(x, weight, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        x, weight = ctx.saved_tensors
+        n = ctx.needs_input_grad
+        dx = hip_ops.linear_dgrad(dy, _linear_transposed(weight)) if n[0] else None
+        dw = db = None
+        if n[1] or n[2]:
+            dw, db = hip_ops.linear_wgrad(x, dy, n[2])
+            dw = dw.to(weight.dtype) if n[1] else None
+            db = db.to(ctx.bias_dtype) if n[2] else None
+        return dx, dw, db
+
+
 def linear(x, weight, bias=None):
     """F.linear(x, weight, bias). On the GPU, the K = 320 projections of the level-0 transformer blocks (packed q/k/v, to_out,
     proj_in / proj_out: output-bound GEMMs around a 20-step loop) take csrc/ff_geglu.hip's plain-epilogue kernel
     (mvi_linear_k320), the level-0 projections INTO 320 channels with a long contraction (FeedForward.net[2], K = 1280) take
     csrc/linear_n320.hip (mvi_linear_n320), and so do the projections into 640 / 1280 channels of levels 1 and 2 (N320_GROUPS above);
-    everything else is the library GEMM."""
+    everything else is the library GEMM. Under autograd with LINEAR_BACKWARD on: _LinearFn where the launches take the shape
+    (linear_gates) and linear_backward_pays says so; F.linear otherwise, as without the switch."""
+    if LINEAR_BACKWARD and x.is_cuda and _needs_autograd(x, weight, bias) and x.dtype == weight.dtype and weight.dim() == 2 \
+            and weight.is_cuda and weight.shape[1] == x.shape[-1] and (bias is None or (bias.is_cuda and bias.shape == weight.shape[:1])):
+        rows = x.numel() // max(x.shape[-1], 1)
+        if linear_gates(rows, x.shape[-1], weight.shape[0], x.dtype) \
+                and linear_backward_pays(rows, x.shape[-1], weight.shape[0], x.dtype, weight.requires_grad or (bias is not None and bias.requires_grad)):
+            return _LinearFn.apply(x, weight, bias)
     if K320_KERNELS and N320_KERNEL and N320_GROUPS and x.is_cuda and weight.shape[0] in N320_GROUP_WIDTHS and x.dtype == weight.dtype \
             and not _needs_autograd(x, weight, bias):
         rows = x.numel() // max(x.shape[-1], 1)
