@@ -450,6 +450,51 @@ int mvi_planes_add_to_tokens(const void* x, const void* tok, const float* bias, 
 int mvi_tokens_blend_to_planes(const void* tok, const void* base, const float* bias, const float* alpha, void* out, int64_t N, int32_t C,
                                int64_t spatial, int32_t dtype, void* stream);
 
+/* Backward of those block tails (training: csrc/block_tails_bwd.hip). bf16 / f16 only (fp32 is declined with the invalid-argument
+ * status), no atomics: every sum is added in a fixed order, two calls return identical bits. dy is the incoming gradient.
+ *   mvi_planes_tail_backward: the adjoint of mvi_tokens_to_planes_add(_bias) (mode A, alpha NULL) and of mvi_tokens_blend_to_planes
+ *     (mode B, alpha fp32 [N]). dy [N, C, S] planes, read through the forward's 64 x 64 LDS tile.
+ *       d_tok[n, p, c]  = (1 - alpha[n]) dy[n, c, p]   one fp32 multiply, one rounding; mode A: the transposition itself
+ *       d_base[n, p, c] = dy[n, c, p]                   mode B only
+ *       dbias[c]        = sum_n (1 - alpha[n]) sum_p dy[n, c, p]                       fp32 [C]; mode A: the weights are 1
+ *       dalpha[n]       = - sum_{c, p} dy[n, c, p] (tok[n, p, c] + bias[c])            fp32 [N]; needs alpha and tok [N, S, C]; bias fp32 [C] or NULL
+ *     The pass (mvi_planes_tail_backward) writes d_tok and d_base, each only where its pointer is not NULL (the gradient of x_in is dy
+ *     itself and needs no launch), and for the sums named in `sums` (MVI_TAILS_DBIAS | MVI_TAILS_DALPHA) fp32 per-block partials into
+ *     `workspace` (at least mvi_planes_tail_backward_workspace_bytes(N, C, S, sums), a pure function of the shape, 0 where nothing is
+ *     reduced); a block walks mvi_planes_tail_backward_walk(S) pixel tiles. mvi_planes_tail_reduce then adds the partials in an
+ *     order fixed by the shape into dbias and / or dalpha (the non-NULL ones must be the sums the pass was asked for; bias is read for dalpha only).
+ *     C and S multiples of 8.
+ *   mvi_rows_tail_backward: the adjoint of mvi_add_lerp. dy, x, h, base [R, C] rows, alpha fp32 [R / row_div], g = r / row_div:
+ *       d_t[r, c]    = (1 - alpha[g]) dy[r, c]           the gradient of x AND of h (one tensor)
+ *       d_base[r, c] = alpha[g] dy[r, c]
+ *       dalpha[g]    = sum_{r in g, c} dy[r, c] (base[r, c] - t[r, c]),  t = x + h rounded to the storage type as the forward rounds it (x when h is NULL)
+ *     dalpha (fp32 [R / row_div], sums = MVI_TAILS_DALPHA) needs x and base; a block covers rows of one group
+ *     (mvi_rows_tail_backward_blocks_per_group(row_div, C) blocks each) and writes one fp32 partial to `workspace`
+ *     (mvi_rows_tail_backward_workspace_bytes, 0 without dalpha), which mvi_rows_tail_reduce adds in an order fixed by the shape. C a multiple of 8;
+ *     row_div positive and dividing R.
+ * Declined with the invalid-argument status before any launch, outputs untouched: C or S not a multiple of 8, fp32, a NULL required
+ * pointer, a tensor or workspace pointer that is not 16-byte aligned (fp32 vectors: 4-byte), a workspace shorter than the function
+ * says, row_div <= 0 or not dividing R, more than 2^31 - 1 blocks. N = 0, S = 0, R = 0: MVI_OK, nothing launched, zeros where a sum
+ * is asked for. mvi_planes_tail_backward_set_walk(w > 0) replaces the walk rule (measurement only; 0 restores it). */
+#define MVI_TAILS_DTOK 1
+#define MVI_TAILS_DBASE 2
+#define MVI_TAILS_DBIAS 4
+#define MVI_TAILS_DALPHA 8
+int mvi_block_tails_backward_supported(int32_t C, int64_t S, int32_t dtype);
+size_t mvi_planes_tail_backward_workspace_bytes(int64_t N, int32_t C, int64_t S, int32_t flags);
+int32_t mvi_planes_tail_backward_walk(int64_t S);
+void mvi_planes_tail_backward_set_walk(int32_t walk);
+int mvi_planes_tail_backward(const void* dy, const float* alpha, const void* tok, void* d_tok, void* d_base, int32_t sums, void* workspace,
+                             size_t workspace_bytes, int64_t N, int32_t C, int64_t S, int32_t dtype, void* stream);
+int mvi_planes_tail_reduce(const void* workspace, size_t workspace_bytes, const float* alpha, const float* bias, float* dbias, float* dalpha,
+                           int64_t N, int32_t C, int64_t S, void* stream);
+int64_t mvi_rows_tail_backward_blocks_per_group(int64_t row_div, int32_t C);
+size_t mvi_rows_tail_backward_workspace_bytes(int64_t R, int32_t C, int64_t row_div, int32_t flags);
+int mvi_rows_tail_backward(const void* dy, const float* alpha, const void* x, const void* h, const void* base, void* d_t, void* d_base,
+                           int32_t sums, void* workspace, size_t workspace_bytes, int64_t R, int32_t C, int64_t row_div, int32_t dtype,
+                           void* stream);
+int mvi_rows_tail_reduce(const void* workspace, size_t workspace_bytes, float* dalpha, int64_t R, int32_t C, int64_t row_div, void* stream);
+
 /* out = silu(h + bias[c]) for h [N, C, spatial]: convolution bias + SiLU of the ControlNet hint stem
  * (svd_inpaint1/models/csvd.py:234-250: eight convolutions with SiLU between, at up to 576x1024) in one pass instead of
  * the library's broadcast bias add followed by a separate activation. out may alias h. */

@@ -17,7 +17,9 @@ _ws = {}
 # token-major norm as "groupnorm_tok2tok_stats_fwd" and "groupnorm_tok2tok_bwd" / "groupnorm_tok2tok_bwd_params",
 # GEGLU under autograd as "ff_geglu" + "ff_geglu_bwd" (the kernel alone) + "ff_geglu_dparams" (for trainable parameters: the library's
 # dweight GEMM and the dbias sum on the kernel's dh), or "geglu" + "geglu_bwd"; a projection under autograd (ops._LinearFn) as its forward kind +
-# "linear_dgrad_n320" / "linear_dgrad_k320" (the forward kernels on the transposed weight) + "linear_wgrad" (dweight and dbias, one kind).
+# "linear_dgrad_n320" / "linear_dgrad_k320" (the forward kernels on the transposed weight) + "linear_wgrad" (dweight and dbias, one kind);
+# the block tails under autograd (ops.BLOCK_TAILS_BACKWARD) as their forward kind + "planes_tail_bwd" / "rows_tail_bwd", and "tails_reduce"
+# (the finishing kernel) when a sum (dbias, dalpha) was asked for.
 PROFILE = None
 # When a list: every attention call appends (kernel variant, Sq, Sk) — 0 rowtile, 4 / 16 = the 4- / 8-wave MFMA kernel
 # (mvi_attention_kernel_variant, the function the C dispatch itself uses). The parity tests assert from it WHICH kernel ran
@@ -1429,6 +1431,118 @@ def planes_to_tokens(x, upsample=1):
         _check(L.mvi_planes_to_tokens(xc.data_ptr(), out.data_ptr(), N, Cc, H, W, int(upsample), _DT[x.dtype], _stream(x.device)),
                "planes_to_tokens")
     return out
+
+
+# ---- the block tails under autograd (ops._TokensToPlanesAddFn, _TokensBlendToPlanesFn, _AddLerpFn): csrc/block_tails_bwd.hip --------------
+TAILS_DTOK, TAILS_DBASE, TAILS_DBIAS, TAILS_DALPHA = 1, 2, 4, 8
+
+
+def block_tails_backward_supported(C, S, dtype):
+    """Whether planes_tail_backward takes dy [N, C, S] (rows_tail_backward: dy [R, C], any S that is a multiple of 8, e.g. 8): the
+    forward tails' own conditions in bf16 / f16 (host-only)."""
+    return dtype in (torch.bfloat16, torch.float16) and bool(_lib.lib().mvi_block_tails_backward_supported(int(C), int(S), _DT[dtype]))
+
+
+def planes_tail_backward_workspace_bytes(N, C, S, flags):
+    return int(_lib.lib().mvi_planes_tail_backward_workspace_bytes(int(N), int(C), int(S), int(flags)))
+
+
+def planes_tail_backward(dy, alpha=None, tok=None, bias=None, need_dtok=True, need_dbase=False, need_dbias=False):
+    """(d_tok, d_base, dbias, dalpha) of out = tokens_to_planes_add(tok, x_in, bias) (alpha None) or of
+    out = tokens_blend_to_planes(tok, base, bias, alpha, spatial) for the upstream gradient dy [N, C, *spatial] (a 16-bit dtype):
+    d_tok [N, S, C] = (1 - alpha[n]) dy^T, d_base [N, S, C] = dy^T (with alpha only), dbias fp32 [C] = sum_n (1 - alpha[n]) sum_p dy,
+    dalpha fp32 [N] = -sum dy (tok + bias) — computed when tok [N, S, C] is given (bias, optional, is read only there). Outputs not
+    asked for are None and cost nothing; the gradient of x_in is dy itself. Deterministic. PROFILE kinds planes_tail_bwd, and
+    tails_reduce when a sum was asked for."""
+    L = _lib.lib()
+    if dy.dtype not in (torch.bfloat16, torch.float16) or dy.dim() < 3:
+        raise TypeError("planes_tail_backward: dy [N, C, *spatial] in bf16 or f16 expected")
+    N, Cc = int(dy.shape[0]), int(dy.shape[1])
+    S = math.prod(int(v) for v in dy.shape[2:])
+    if need_dbase and alpha is None:
+        raise ValueError("planes_tail_backward: d_base belongs to the blend (alpha)")
+    if tok is not None and (alpha is None or tok.dtype != dy.dtype or tuple(tok.shape) != (N, S, Cc)):
+        raise ValueError("planes_tail_backward: dalpha needs alpha and tok [N, S, C] in dy's dtype")
+    if alpha is not None and alpha.numel() != N:
+        raise ValueError("planes_tail_backward: alpha must hold one value per sample")
+    dc = _contig(dy)
+    tc = None if tok is None else _contig(tok)
+    al = None if alpha is None else alpha.detach().reshape(N).float().contiguous()
+    bf = None if (bias is None or tok is None) else _f32(bias)
+    f32 = dict(dtype=torch.float32, device=dy.device)
+    d_tok = torch.empty(N, S, Cc, dtype=dy.dtype, device=dy.device) if need_dtok else None
+    d_base = torch.empty(N, S, Cc, dtype=dy.dtype, device=dy.device) if need_dbase else None
+    dbias = torch.empty(Cc, **f32) if need_dbias else None
+    dalpha = torch.empty(N, **f32) if tok is not None else None
+    flags = (TAILS_DTOK if need_dtok else 0) | (TAILS_DBASE if need_dbase else 0) | (TAILS_DBIAS if need_dbias else 0) \
+        | (TAILS_DALPHA if tok is not None else 0)
+    if N == 0 or S == 0 or not flags:
+        for t in (dbias, dalpha):
+            if t is not None:
+                t.zero_()
+        return d_tok, d_base, dbias, dalpha
+    nbytes = int(L.mvi_planes_tail_backward_workspace_bytes(N, Cc, S, flags))
+    ws = _workspace(dy.device, nbytes) if nbytes else None
+    n_io = 1 + bool(need_dtok) + bool(need_dbase) + (tok is not None)
+    sums = flags & (TAILS_DBIAS | TAILS_DALPHA)
+    with torch.cuda.device(dy.device):
+        with _Timed("planes_tail_bwd", float(n_io) * dc.numel() * dc.element_size() + nbytes, dy.device):
+            _check(L.mvi_planes_tail_backward(dc.data_ptr(), _ptr(al), _ptr(tc), _ptr(d_tok), _ptr(d_base), sums, _ptr(ws), nbytes, N, Cc, S,
+                                              _DT[dy.dtype], _stream(dy.device)), "planes_tail_backward")
+        if sums:
+            with _Timed("tails_reduce", float(nbytes) + 4.0 * (Cc * (1 + (bf is not None)) + 2 * N), dy.device):
+                _check(L.mvi_planes_tail_reduce(ws.data_ptr(), nbytes, _ptr(al), _ptr(bf), _ptr(dbias), _ptr(dalpha), N, Cc, S, _stream(dy.device)),
+                       "planes_tail_reduce")
+    return d_tok, d_base, dbias, dalpha
+
+
+def rows_tail_backward_workspace_bytes(R, C, row_div, need_dalpha=True):
+    return int(_lib.lib().mvi_rows_tail_backward_workspace_bytes(int(R), int(C), int(row_div), TAILS_DALPHA if need_dalpha else 0))
+
+
+def rows_tail_backward(dy, alpha, x=None, h=None, base=None, need_dt=True, need_dbase=True):
+    """(d_t, d_base, dalpha) of out = add_lerp(x, h, base, alpha) for the upstream gradient dy [..., C] (a 16-bit dtype), alpha [G]
+    over equal runs of rows: d_t = (1 - alpha[g]) dy (the gradient of x AND of h, one tensor), d_base = alpha[g] dy, dalpha fp32 [G] =
+    sum dy (base - round(x + h)) — computed when x and base are given (h optional). Outputs not asked for are None. Deterministic.
+    PROFILE kinds rows_tail_bwd, and tails_reduce with dalpha."""
+    L = _lib.lib()
+    if dy.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError("rows_tail_backward: dy in bf16 or f16 expected")
+    Cc = int(dy.shape[-1])
+    dc = _contig(dy)
+    R = dc.numel() // Cc if Cc else 0
+    al = alpha.detach().reshape(-1).float().contiguous()
+    G = al.numel()
+    if G == 0 or R % G:
+        raise ValueError(f"rows_tail_backward: {R} rows do not split into {G} equal runs")
+    want_da = x is not None and base is not None
+    ins = []
+    for name, t in (("x", x), ("h", h), ("base", base)):
+        if t is not None and want_da:
+            if t.shape != dy.shape or t.dtype != dy.dtype:
+                raise ValueError(f"rows_tail_backward: {name} must match dy in shape and dtype")
+            t = _contig(t)
+        ins.append(t if want_da else None)
+    d_t = torch.empty_like(dc) if need_dt else None
+    d_base = torch.empty_like(dc) if need_dbase else None
+    dalpha = torch.empty(G, dtype=torch.float32, device=dy.device) if want_da else None
+    if R == 0 or not (need_dt or need_dbase or want_da):
+        if dalpha is not None:
+            dalpha.zero_()
+        return d_t, d_base, dalpha
+    row_div = R // G
+    nbytes = int(L.mvi_rows_tail_backward_workspace_bytes(R, Cc, row_div, TAILS_DALPHA if want_da else 0))
+    ws = _workspace(dy.device, nbytes) if nbytes else None
+    n_io = 1 + bool(need_dt) + bool(need_dbase) + sum(t is not None for t in ins)
+    sums = TAILS_DALPHA if want_da else 0
+    with torch.cuda.device(dy.device):
+        with _Timed("rows_tail_bwd", float(n_io) * dc.numel() * dc.element_size() + nbytes, dy.device):
+            _check(L.mvi_rows_tail_backward(dc.data_ptr(), al.data_ptr(), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(d_t), _ptr(d_base),
+                                            sums, _ptr(ws), nbytes, R, Cc, row_div, _DT[dy.dtype], _stream(dy.device)), "rows_tail_backward")
+        if sums:
+            with _Timed("tails_reduce", float(nbytes) + 4.0 * G, dy.device):
+                _check(L.mvi_rows_tail_reduce(ws.data_ptr(), nbytes, dalpha.data_ptr(), R, Cc, row_div, _stream(dy.device)), "rows_tail_reduce")
+    return d_t, d_base, dalpha
 
 
 def group_norm_tok2tok_supported(N, C_, S, groups, dtype):

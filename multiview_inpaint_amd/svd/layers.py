@@ -890,18 +890,25 @@ class VideoResBlock(ResBlock):
         """_time_stack_frames under autograd on tokens (TIME_STACK_CONV_BWD): a plain permute copy to [(b T), S, c], the temporal norms
         token-major on both sides (ops.group_norm_tok2tok chooses between its HIP Function and its differentiable fallback), the two
         frame convolutions on ops.conv3t_tokens (HIP forward, dgrad and wgrad), a plain copy back, the same differentiable tail. No
-        channel-stacked 3 c tensor, forward or backward."""
+        channel-stacked 3 c tensor, forward or backward. With the opt-in ops.BLOCK_TAILS_BACKWARD, where each is routed: the entry on
+        ops.planes_to_tokens and the tail on ops.tokens_blend_to_planes / ops.tokens_to_planes_add (HIP forward and backward), so the
+        copy back and the PyTorch blend disappear."""
         ts = self.time_stack
         g0, g1 = ts.in_layers[0], ts.out_layers[0]
         c1, c2 = ts.in_layers[2], ts.out_layers[3]
         bt, c, hh, ww = x.shape
-        xt = x.flatten(2).transpose(1, 2).contiguous()
+        # (opt-in ops.BLOCK_TAILS_BACKWARD: the entry and the tail on their HIP kernels with a HIP backward, where each is routed)
+        xt = ops.planes_to_tokens(x) if ops.planes_to_tokens_routed(x) else x.flatten(2).transpose(1, 2).contiguous()
         h = ops.group_norm_tok2tok(xt, g0.num_groups, g0.weight, g0.bias, g0.eps, silu=True, frames=T)
         h = ops.conv3t_tokens(h, c1.weight, T)
         e = _emb_chan_bias(ts.emb_layers, emb, c1)                 # [(b T), c] fp32 incl. the first convolution's bias
         e = e if e.is_contiguous() else e.contiguous()
         h = ops.group_norm_tok2tok(h, g1.num_groups, g1.weight, g1.bias, g1.eps, silu=True, chan_bias=e, frames=T)
         h = ops.conv3t_tokens(ts.out_layers[2](h), c2.weight, T)
+        if blend is not None and ops.tokens_blend_to_planes_routed(h, xt, c2.bias, blend):
+            return ops.tokens_blend_to_planes(h, xt, c2.bias, blend, (hh, ww))       # xt, the token copy made above, is the base
+        if blend is None and ops.tokens_to_planes_add_routed(h, x, c2.bias):
+            return ops.tokens_to_planes_add(h, x, c2.bias)
         h = h.transpose(1, 2).reshape(bt, c2.out_channels, hh, ww).contiguous()
         if blend is not None:
             return ops.bias_residual_blend(h, c2.bias, x, blend)

@@ -23,9 +23,12 @@ through the opt-in unet.HINT_STEM_BWD.
 The projections have one behind a switch that is off by default (`linear` with MVI_LINEAR_BWD=1: the forward on the kernel inference
 launches, the input gradient on the forward kernels with the transposed weight, weight and bias gradient on csrc/linear_wgrad.hip),
 where `linear_gates` and `linear_backward_pays` say so; `linear_module` and `linear_add_layer_norm` under grad reach it through `linear`.
+The block tails have one behind another switch that is off by default (`tokens_to_planes_add`, `tokens_blend_to_planes`, `add_lerp`,
+`planes_to_tokens` with MVI_BLOCK_TAILS_BWD=1: the forward on the inference kernel, the backward on csrc/block_tails_bwd.hip,
+deterministic dbias / dalpha), where `block_tails_backward_pays` says so.
 Every other kernel is forward-only: a GPU tensor that requires grad goes through PyTorch-ROCm's differentiable ops there
 (the projections without that switch or outside its classes, the cross-attention projections of the context —
-`linear_add_layer_norm` under grad is `linear_module` + `add_layer_norm` —, `add_lerp`).
+`linear_add_layer_norm` under grad is `linear_module` + `add_layer_norm` —, the tails without their switch).
 
 Reference ops: GroupNorm32 + SiLU (sgm/modules/diffusionmodules/util.py:259-276,
 openaimodel.py:257-261,292-305), Normalize (sgm/modules/attention.py:125-128),
@@ -937,12 +940,252 @@ def finish_add_layer_norm(h, fuse):
     return add_layer_norm(resid, fuse["norm"], h=h, row=row, ret_pre=ret_pre)
 
 
+# The block tails under autograd (csrc/block_tails_bwd.hip): tokens_to_planes_add, tokens_blend_to_planes, add_lerp and planes_to_tokens
+# keep their one-pass HIP forward when a graph is recorded, with a fused deterministic backward — the transposition of dy, the scaled
+# copies and the sums dbias / dalpha (the gradient of time_mixer.mix_factor) without atomics. DEFAULT OFF (MVI_BLOCK_TAILS_BWD=1 or
+# ops.BLOCK_TAILS_BACKWARD = True turns it on): off, every function below is exactly the function it was.
+BLOCK_TAILS_BACKWARD = os.environ.get("MVI_BLOCK_TAILS_BWD", "0") == "1"
+# Classes tools/bench_block_tails_bwd.py showed to win (profiles/block_tails_bwd_bench.json): {(kind, C, S, need_dparams): the smallest
+# measured N (add_lerp: row count R, S = rows per alpha) from which every measured size of the class won in both dtypes, in every run of
+# the tool}. A class that is not listed is not routed. Kinds: "planes_add" (tokens_to_planes_add), "planes_blend"
+# (tokens_blend_to_planes), "add_lerp", "to_tokens" (planes_to_tokens).
+BLOCK_TAILS_BACKWARD_ROUTED = {
+    ("planes_add", 320, 9216, True): 14, ("planes_add", 320, 9216, False): 14, ("planes_add", 640, 2304, True): 28,
+    ("planes_add", 640, 2304, False): 14, ("planes_add", 1280, 576, True): 28, ("planes_add", 1280, 576, False): 28,
+    ("planes_blend", 320, 9216, True): 14, ("planes_blend", 320, 9216, False): 14, ("planes_blend", 640, 2304, True): 14,
+    ("planes_blend", 640, 2304, False): 14, ("planes_blend", 1280, 576, True): 14, ("planes_blend", 1280, 576, False): 28,
+    ("planes_blend", 1280, 144, True): 28, ("planes_blend", 1280, 144, False): 28,
+    ("add_lerp", 320, 9216, True): 14 * 9216, ("add_lerp", 320, 9216, False): 28 * 9216, ("add_lerp", 640, 2304, True): 14 * 2304,
+    ("add_lerp", 640, 2304, False): 28 * 2304, ("add_lerp", 1280, 576, True): 28 * 576,
+    ("to_tokens", 320, 9216, False): 14, ("to_tokens", 640, 2304, False): 14, ("to_tokens", 1280, 576, False): 28}
+
+
+def block_tails_backward_pays(kind, N_or_R, C, S, dtype, need_dparams):
+    """Whether the tail's forward + the HIP backward is faster than the PyTorch-ROCm composition under autograd for this shape class —
+    the routing's second question after hip_ops.block_tails_backward_supported. The rule ops.linear_backward_pays documents: a class
+    is routed only if it won every time it was measured (tools/bench_block_tails_bwd.py, profiles/block_tails_bwd_bench.json; DESIGN.md
+    'Block tails under autograd'), and anything unmeasured is not routed. Forward + backward by device events, the two routes
+    alternating in one process, 9 pairs, medians; a win is a HIP median below the PyTorch median by more than that route's spread, in
+    bf16 AND f16, in each of three runs of the tool. ms HIP / PyTorch (spread), all gradients | bias and alpha frozen, bf16 of the
+    last run (f16: the JSON):
+      planes_add    14 x  320 x 9216   0.248 / 0.513 (0.012) | 0.221 / 0.452 (0.006)    wins
+                    28 x  320 x 9216   0.300 / 1.129 (0.019) | 0.263 / 1.033 (0.008)    wins
+                    14 x  640 x 2304   0.251 / 0.262 (0.013) | 0.205 / 0.232 (0.007)    all gradients UNSTEADY (lost one of three runs), frozen wins
+                    28 x  640 x 2304   0.149 / 0.473 (0.012) | 0.126 / 0.436 (0.003)    wins
+                    14 x 1280 x  576   0.242 / 0.170 (0.040) | 0.197 / 0.139 (0.007)    LOSES in bf16 (f16 wins)
+                    28 x 1280 x  576   0.111 / 0.240 (0.004) | 0.084 / 0.221 (0.004)    wins
+                    .. x 1280 x  144   loses at both sizes (0.109 / 0.094 at 28)
+      planes_blend  14 x  320 x 9216   0.298 / 0.977 (0.029) | 0.226 / 0.598 (0.010)    wins
+                    28 x  320 x 9216   0.347 / 1.838 (0.018) | 0.244 / 1.180 (0.014)    wins
+                    14 x  640 x 2304   0.301 / 0.514 (0.007) | 0.234 / 0.324 (0.007)    wins
+                    28 x  640 x 2304   0.165 / 0.832 (0.005) | 0.115 / 0.587 (0.012)    wins
+                    14 x 1280 x  576   0.290 / 0.301 (0.007) | 0.231 / 0.198 (0.006)    all gradients wins, frozen LOSES in bf16
+                    28 x 1280 x  576   0.136 / 0.439 (0.006) | 0.098 / 0.310 (0.004)    wins
+                    14 x 1280 x  144   0.288 / 0.263 (0.024) | 0.227 / 0.192 (0.059)    UNSTEADY
+                    28 x 1280 x  144   0.174 / 0.220 (0.042) | 0.130 / 0.162 (0.031)    wins
+      add_lerp      14 x 9216 x  320   0.308 / 0.524 (0.007) | 0.238 / 0.217 (0.003)    all gradients wins, frozen UNSTEADY
+                    28 x 9216 x  320   0.431 / 0.935 (0.011) | 0.333 / 0.390 (0.012)    wins
+                    14 x 2304 x  640   0.283 / 0.308 (0.014) | 0.246 / 0.172 (0.008)    all gradients wins, frozen LOSES
+                    28 x 2304 x  640   0.214 / 0.402 (0.007) | 0.162 / 0.205 (0.004)    wins
+                    14 x  576 x 1280   0.284 / 0.210 (0.067) | 0.246 / 0.170 (0.009)    LOSES
+                    28 x  576 x 1280   0.145 / 0.210 (0.006) | 0.110 / 0.108 (0.062)    all gradients wins, frozen TIES
+                    .. x  144 x 1280   loses everywhere
+      to_tokens     wins at 320 x 9216 and 640 x 2304 at both sizes and at 28 x 1280 x 576; loses in bf16 at 14 x 1280 x 576 and
+                    everywhere at 1280 x 144
+    The kernels themselves take 8 - 180 us; below about 20 M elements a forward + backward is bound by the host side of the Function
+    (0.07 - 0.25 ms, the first type measured in a process — bf16 — slower than the second), which is why the small classes lose or
+    change sides and why N = 14 can lose where N = 28 wins. One machine."""
+    lo = BLOCK_TAILS_BACKWARD_ROUTED.get((kind, int(C), int(S), bool(need_dparams)))
+    return lo is not None and N_or_R >= lo
+
+
+def _rg(t):
+    return t is not None and t.requires_grad
+
+
+def _tails_planes_route(kind, tok, bias, N, C_, S, need_dparams):
+    """Under autograd with the switch on: do the tail's launches take tok [N, S, C] (+ bias [C]), and does the route pay?"""
+    from . import hip_ops
+    return (tok.dim() == 3 and tok.dtype in (torch.bfloat16, torch.float16) and tok.numel() > 0
+            and (bias is None or (bias.is_cuda and tuple(bias.shape) == (C_,)))
+            and hip_ops.block_tails_backward_supported(C_, S, tok.dtype)
+            and block_tails_backward_pays(kind, N, C_, S, tok.dtype, need_dparams))
+
+
+class _TokensToPlanesAddFn(torch.autograd.Function):
+    """tokens_to_planes_add on its inference kernel; backward: d_x_in is dy itself, d_tok its transposition (the planes_to_tokens kernel
+    when the bias is frozen or absent, csrc/block_tails_bwd.hip with dbias otherwise). Saves nothing."""
+
+    @staticmethod
+    def forward(ctx, tok, x_in, bias):
+        from . import hip_ops
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        ctx.set_materialize_grads(False)
+        return hip_ops.tokens_to_planes_add(tok, x_in, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        n = ctx.needs_input_grad
+        if dy is None:
+            return None, None, None
+        d_tok = db = None
+        if n[2]:
+            d_tok, _, db, _ = hip_ops.planes_tail_backward(dy, need_dtok=n[0], need_dbias=True)
+            db = db.to(ctx.bias_dtype)
+        elif n[0]:
+            d_tok = hip_ops.planes_to_tokens(dy.reshape(dy.shape[0], dy.shape[1], 1, -1))
+        return d_tok, (dy if n[1] else None), db
+
+
+class _TokensBlendToPlanesFn(torch.autograd.Function):
+    """tokens_blend_to_planes on its inference kernel with the fused backward of csrc/block_tails_bwd.hip (mode B). Saves alpha; tok and
+    bias only when alpha requires grad (its gradient is the one that reads an activation)."""
+
+    @staticmethod
+    def forward(ctx, tok, base, bias, alpha, spatial):
+        from . import hip_ops
+        need_da = ctx.needs_input_grad[3]
+        ctx.save_for_backward(alpha, *((tok,) if need_da else ()), *((bias,) if need_da and bias is not None else ()))
+        ctx.cfg = (None if bias is None else bias.dtype, need_da, bias is not None)
+        ctx.set_materialize_grads(False)
+        return hip_ops.tokens_blend_to_planes(tok, base, bias, alpha, spatial)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        n = ctx.needs_input_grad
+        if dy is None or not any(n[:4]):
+            return (None,) * 5
+        bias_dtype, saved_tok, has_bias = ctx.cfg
+        saved = ctx.saved_tensors                                      # (read once: checkpoint unpacks a tensor a single time)
+        alpha = saved[0]
+        tok = saved[1] if saved_tok and n[3] else None
+        bias = saved[2] if saved_tok and has_bias and n[3] else None
+        d_tok, d_base, db, da = hip_ops.planes_tail_backward(dy, alpha=alpha, tok=tok, bias=bias, need_dtok=n[0], need_dbase=n[1],
+                                                             need_dbias=n[2] and has_bias)
+        return (d_tok, d_base, db.to(bias_dtype) if db is not None else None,
+                da.to(alpha.dtype).reshape(alpha.shape) if da is not None else None, None)
+
+
+class _AddLerpFn(torch.autograd.Function):
+    """add_lerp on its inference kernel with the row pass of csrc/block_tails_bwd.hip as backward: one tensor for d_x and d_h, d_base,
+    and dalpha in alpha's own shape and dtype. Saves alpha; x, h, base only when alpha requires grad."""
+
+    @staticmethod
+    def forward(ctx, x, h, base, alpha):
+        from . import hip_ops
+        need_da = ctx.needs_input_grad[3]
+        ctx.save_for_backward(alpha, *((x, base) if need_da else ()), *((h,) if need_da and h is not None else ()))
+        ctx.cfg = (need_da, h is not None)
+        ctx.set_materialize_grads(False)
+        return hip_ops.add_lerp(x, h, base, alpha)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import hip_ops
+        n = ctx.needs_input_grad
+        if dy is None or not any(n):
+            return (None,) * 4
+        saved_x, has_h = ctx.cfg
+        saved = ctx.saved_tensors                                      # (read once: checkpoint unpacks a tensor a single time)
+        alpha = saved[0]
+        x = base = h = None
+        if saved_x and n[3]:
+            x, base = saved[1], saved[2]
+            h = saved[3] if has_h else None
+        need_dt = n[0] or (has_h and n[1])
+        d_t, d_base, da = hip_ops.rows_tail_backward(dy, alpha, x=x, h=h, base=base, need_dt=need_dt, need_dbase=n[2])
+        return (d_t if n[0] else None, d_t if has_h and n[1] else None, d_base,
+                da.to(alpha.dtype).reshape(alpha.shape) if da is not None else None)
+
+
+class _PlanesToTokensFn(torch.autograd.Function):
+    """x [N, C, H, W] -> tokens [N, H W, C] on the planes_to_tokens kernel; backward: the tokens_to_planes_add kernel without an addend."""
+
+    @staticmethod
+    def forward(ctx, x):
+        from . import hip_ops
+        ctx.spatial = tuple(x.shape[2:])
+        return hip_ops.planes_to_tokens(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from . import hip_ops
+        return hip_ops.tokens_to_planes_add(g, None, spatial=ctx.spatial)
+
+
+def planes_to_tokens_routed(x):
+    """Under autograd: does planes_to_tokens(x) run _PlanesToTokensFn? (switch on, the kernels take the shape, the route pays)"""
+    return (BLOCK_TAILS_BACKWARD and x.is_cuda and _needs_autograd(x) and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float16)
+            and x.numel() > 0 and x.shape[1] % 8 == 0 and (x.shape[2] * x.shape[3]) % 8 == 0
+            and block_tails_backward_pays("to_tokens", x.shape[0], x.shape[1], x.shape[2] * x.shape[3], x.dtype, False))
+
+
+def planes_to_tokens(x):
+    """x [N, C, H, W] -> [N, (H W), C] ("b c h w -> b (h w) c"), one pass through an LDS tile; under autograd with BLOCK_TAILS_BACKWARD
+    on, where the kernels take the shape and the route pays, the same kernel with the opposite one as backward."""
+    ok = x.dim() == 4 and x.shape[1] % 8 == 0 and (x.shape[2] * x.shape[3]) % 8 == 0
+    if x.is_cuda and not _needs_autograd(x):
+        if ok:
+            from . import hip_ops
+            return hip_ops.planes_to_tokens(x)
+    elif planes_to_tokens_routed(x):
+        return _PlanesToTokensFn.apply(x)
+    _fallback(x, "planes_to_tokens", _why(x))
+    return x.flatten(2).transpose(1, 2).contiguous()
+
+
+def tokens_blend_to_planes_routed(tok, base, bias, alpha):
+    """Under autograd: does tokens_blend_to_planes run _TokensBlendToPlanesFn for these tensors?"""
+    return (BLOCK_TAILS_BACKWARD and tok.is_cuda and _needs_autograd(tok, base, bias, alpha) and tok.dim() == 3 and base.is_cuda
+            and alpha.is_cuda and base.shape == tok.shape and base.dtype == tok.dtype and alpha.numel() == tok.shape[0]
+            and _tails_planes_route("planes_blend", tok, bias, tok.shape[0], tok.shape[2], tok.shape[1], _rg(bias) or _rg(alpha)))
+
+
+def tokens_blend_to_planes(tok, base, bias, alpha, spatial):
+    """base + (1 - alpha[n]) * (tok + bias[c]) for token-major tok, base [N, S, C] -> [N, C, *spatial]; alpha [N] per sample: the
+    temporal ResBlock's skip add followed by AlphaBlender (alpha x + (1 - alpha)(x + h + b), video_model.py:67-81, util.py:358-372)
+    evaluated on tokens, in the pass that restores b c h w. Under autograd with BLOCK_TAILS_BACKWARD on: _TokensBlendToPlanesFn where
+    the kernels take the shape and the route pays; on the CPU, or otherwise, the differentiable composition."""
+    N, S, C_ = tok.shape
+    if tok.is_cuda and not _needs_autograd(tok, base, bias, alpha):
+        if C_ % 8 == 0 and S % 8 == 0:
+            from . import hip_ops
+            return hip_ops.tokens_blend_to_planes(tok, base, bias, alpha, spatial)
+    elif tokens_blend_to_planes_routed(tok, base, bias, alpha):
+        return _TokensBlendToPlanesFn.apply(tok, base, bias, alpha, tuple(int(v) for v in spatial))
+    _fallback(tok, "tokens_blend_to_planes", _why(tok, base, bias, alpha))
+    t = tok if bias is None else tok + bias.to(tok.dtype)
+    out = torch.lerp(base + t, base, alpha.reshape(N, 1, 1).to(tok.dtype))
+    return out.transpose(1, 2).reshape(N, C_, *spatial)
+
+
+def _add_lerp_route(x, h, base, alpha):
+    """Under autograd with the switch on: does add_lerp run _AddLerpFn? (the forward's conditions, 16-bit, and it pays)"""
+    from . import hip_ops
+    C_ = x.shape[-1]
+    G = alpha.numel()
+    R = x.numel() // max(C_, 1)
+    return (x.is_cuda and base.is_cuda and alpha.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and x.numel() > 0
+            and base.shape == x.shape and base.dtype == x.dtype and (h is None or (h.is_cuda and h.shape == x.shape and h.dtype == x.dtype))
+            and G > 0 and R % G == 0 and hip_ops.block_tails_backward_supported(C_, 8, x.dtype)
+            and block_tails_backward_pays("add_lerp", R, C_, R // G, x.dtype, alpha.requires_grad))
+
+
 def add_lerp(x, h, base, alpha):
     """lerp(x + h, base, alpha): alpha * base + (1 - alpha) * (x + h) with alpha [G] broadcast over equal runs of
-    the rows of x [B, S, C] (AlphaBlender after the temporal block's last residual add)."""
+    the rows of x [B, S, C] (AlphaBlender after the temporal block's last residual add). Under autograd with BLOCK_TAILS_BACKWARD on:
+    the same kernel inside _AddLerpFn where it takes the shape and block_tails_backward_pays says so."""
     if x.is_cuda and not _needs_autograd(x, h, base, alpha) and x.shape[-1] % 8 == 0:
         from . import hip_ops
         return hip_ops.add_lerp(x, h, base, alpha)
+    if BLOCK_TAILS_BACKWARD and _needs_autograd(x, h, base, alpha) and _add_lerp_route(x, h, base, alpha):
+        return _AddLerpFn.apply(x, h, base, alpha)
     _fallback(x, "add_lerp", _why(x, h, base, alpha))
     t = x if h is None else x + h
     C_ = x.shape[-1]
@@ -951,13 +1194,24 @@ def add_lerp(x, h, base, alpha):
     return torch.lerp(t.reshape(G, -1, C_), base.reshape(G, -1, C_), a).reshape(x.shape)
 
 
+def tokens_to_planes_add_routed(tok, x_in, bias=None):
+    """Under autograd: does tokens_to_planes_add run _TokensToPlanesAddFn for these tensors?"""
+    return (BLOCK_TAILS_BACKWARD and tok.is_cuda and _needs_autograd(tok, x_in, bias) and x_in is not None and x_in.is_cuda
+            and x_in.dtype == tok.dtype and tok.dim() == 3 and x_in.dim() >= 3 and x_in.shape[0] == tok.shape[0]
+            and x_in.shape[1] == tok.shape[2] and x_in.numel() == tok.numel()
+            and _tails_planes_route("planes_add", tok, bias, tok.shape[0], tok.shape[2], tok.shape[1], _rg(bias)))
+
+
 def tokens_to_planes_add(tok, x_in, bias=None):
     """tok [B, (h w), C] (+ bias[c]) -> [B, C, h, w] plus x_in, one pass (SpatialTransformer's exit; ResBlock's exit when its
-    convolutions ran channels-last)."""
+    convolutions ran channels-last). Under autograd with BLOCK_TAILS_BACKWARD on: the same kernel inside _TokensToPlanesAddFn where
+    the backward's kernels take the shape and block_tails_backward_pays says so."""
     if tok.is_cuda and not _needs_autograd(tok, x_in, bias):
         from . import hip_ops
         if tok.shape[-1] % 8 == 0 and tok.shape[1] % 8 == 0:
             return hip_ops.tokens_to_planes_add(tok, x_in, bias)
+    elif tokens_to_planes_add_routed(tok, x_in, bias):
+        return _TokensToPlanesAddFn.apply(tok, x_in, bias)
     _fallback(tok, "tokens_to_planes_add", _why(tok, x_in))
     t = tok if bias is None else tok + bias.to(tok.dtype)
     return t.transpose(1, 2).reshape(x_in.shape) + x_in
