@@ -253,6 +253,13 @@ const char* mvi_raster_stage_name(int stage);
  * (-1, -1, -1, depth) and clamped 0 for the Gaussians no tile staged. Pass 0 or 1 to select, anything else to query;
  * returns the previous selection. Must not change between the two forward calls of one view. Not thread-safe. */
 int mvi_raster_color_mode(int deferred);
+/* Strip walk of the forward render kernel: the kept entries of a 64-entry chunk are composited in groups of `group` (one
+ * address and one loop test per group; a wave whose pixels are all saturated leaves in front of a group). Built: 4 (default)
+ * and 1, the one-entry loop that tests for saturation per chunk only (MVI_RASTER_FORWARD_GROUP selects at start-up). Every
+ * output is identical bit for bit; the switch exists for the A/B exactness test and A/B timing. Pass a built size to select,
+ * 0 for the default, -1 to query; returns the previous selection, or MVI_EINVAL (nothing changed) for a size that is not
+ * built. Not thread-safe. */
+int mvi_raster_forward_group(int group);
 /* Evaluates every colour still pending after a deferred forward (no-op after an eager one), so that mvi_raster_views.rgbd /
  * clamped are complete: for the parity tests and for callers that inspect colours of Gaussians that were never composited.
  * Needs the means3D / shs arrays of the forward still valid. */

@@ -136,6 +136,10 @@ int mvi_raster_backward_mode(int dense) {
     return old;
 }
 int mvi_raster_binning_version(int version) { return mvi::set_binning_version(version); }
+int mvi_raster_forward_group(int group) {
+    const int old = mvi::set_forward_group(group);
+    return old < 0 ? fail(MVI_EINVAL, "forward group: no such instantiation of render_forward%s") : old;
+}
 int mvi_raster_color_mode(int deferred) {
     const int old = g_defer_colors;
     if (deferred == 0 || deferred == 1) g_defer_colors = deferred;

@@ -67,6 +67,7 @@ constexpr int kEx2SmallCap = 7168;                  // image entries of that ins
 bool binning_v2_enabled();                          // false when MVI_BINNING_LEGACY=1 or after set_binning_version(1)
 void set_dev_stamps(int pass, void* buf);            // diagnostics: shader-clock stamps of the partition kernel's phases
 int set_binning_version(int v);                     // 1 | 2 (anything else: query only); returns the previous version
+int set_forward_group(int g);                       // render_forward's strip-walk group: a built size | 0 = default | -1 = query
 inline bool binning_v2_ok(int gx, int gy) { return gx <= 256 && gy <= 256 && binning_v2_enabled(); }
 
 // Deferred SH colours. With SH input the forward preprocess does NOT evaluate SH -> RGB for every visible Gaussian (192 bytes

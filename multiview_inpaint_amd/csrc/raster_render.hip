@@ -85,7 +85,15 @@ __device__ __forceinline__ float gauss_power1(float4 co, float dx, float dy) {  
 // strip (lane-parallel copies at popcount positions) and walked by a plain counted loop, and a
 // pixel that has saturated is represented by T = 0 (its committed transmittance lives in T_out), so
 // the body needs no per-lane "done" mask and no divergent branch.
-__global__ __launch_bounds__(kBlock) void render_forward_kernel(
+//
+// The strip is walked in groups of G kept entries (G = 1: one entry per iteration, the next entry's address clamped and
+// rebuilt every time, the wave's pixels tested at the top of a chunk only). One address register per group and
+// compile-time offsets for its 3 G reads, one loop test per group, and in front of every group the wave asks whether any
+// of its pixels is still live (T > 0): if none is, nothing behind this point changes any output (test_T = 0: no
+// contribution, T stays 0), and the wave leaves the round's chunk loop. The cnt % G entries behind the last full group
+// are walked one by one: no padding entry is ever evaluated.
+template <int G>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G == 1 ? 1 : 6, G == 1 ? 8 : 6))) void render_forward_kernel(
     Frame f, const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ point_list,
     const float2* __restrict__ xy, float4* rgbd, const float4* __restrict__ conic_opacity,
     float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color,
@@ -157,13 +165,14 @@ __global__ __launch_bounds__(kBlock) void render_forward_kernel(
                 w_s[wave][1][pos] = s_co[e];
                 w_s[wave][2][pos] = s_cd[e];
             }
-            const int cnt = __popcll(mask);
-            float4 a = w_s[wave][0][0], co = w_s[wave][1][0], cd = w_s[wave][2][0];
-            for (int k = 0; k < cnt; ++k) {
-                const int kn = k + 1 < 64 ? k + 1 : 63;
-                const float4* nx = &w_s[wave][0][kn];
-                const float4 an = nx[0], con = nx[64], cdn = nx[128];   // next entry's reads overlap the math
+            // one kept entry (strip position, conic + opacity, colour + depth) composited onto the lane's pixel
+            auto entry = [&](const float4 a, const float4 co, const float4 cd, const float chain) __attribute__((always_inline)) {
                 float dx = a.x - pfx, dy = a.y - pfy;
+                // No instruction: dx and dy are made to come after the previous entry's exponent (`chain`). The entries of a
+                // group are independent up to alpha, and the compiler otherwise pairs their dx / dy / power arithmetic on
+                // packed fp32, with register copies to build the pairs (86 VGPRs: five waves); a packed instruction issues
+                // at the price of 1.8 plain ones on a busy SIMD.
+                if constexpr (G > 1) asm("" : "+v"(dx), "+v"(dy) : "v"(chain));
                 float power = gauss_power1(co, dx, dy);
                 float alpha = fminf(kAlphaMax, co.w * __expf(power));
                 alpha = power <= 0.0f ? alpha : 0.0f;
@@ -184,7 +193,46 @@ __global__ __launch_bounds__(kBlock) void render_forward_kernel(
                 T_out = contrib ? test_T : T_out;
                 last = contrib ? __float_as_uint(a.z) : last;           // 1-based position in the tile's list
                 T = contrib ? test_T : (valid ? 0.0f : T);              // valid but below 1e-4: saturated from here on
-                a = an; co = con; cd = cdn;
+                return power;
+            };
+            const int cnt = __popcll(mask);
+            if constexpr (G == 1) {
+                float4 a = w_s[wave][0][0], co = w_s[wave][1][0], cd = w_s[wave][2][0];
+                for (int k = 0; k < cnt; ++k) {
+                    const int kn = k + 1 < 64 ? k + 1 : 63;
+                    const float4* nx = &w_s[wave][0][kn];
+                    const float4 an = nx[0], con = nx[64], cdn = nx[128];   // next entry's reads overlap the math
+                    entry(a, co, cd, 0.0f);
+                    a = an; co = con; cd = cdn;
+                }
+            } else {
+                // Rotated by hand: every exit of the group loop is at its bottom, behind the group, so the eight carried
+                // registers of a pixel leave in the registers they live in. (With the test at the top and a jump out of the
+                // chunk loop the compiler kept two copies of them and paid seven v_mov per group.) The chunk-top test above
+                // is the first group's test, asked before the cull; the test in front of the remainder also catches a wave
+                // that left the group loop saturated with full groups still to go.
+                const float4* g = &w_s[wave][0][0];
+                int k = 0;
+                float chain = 0.0f;
+                if (cnt >= G) {
+                    do {
+                        // The reads of entry j + 1 are issued in front of the arithmetic of entry j, and the scheduling barrier
+                        // keeps them there: left alone the compiler issues an entry's conic and colour reads right in front
+                        // of their first use and waits for each (207 against 216 us for the kernel).
+                        float4 a = g[0], co = g[64], cd = g[128];
+#pragma unroll
+                        for (int j = 0; j < G; ++j) {
+                            const int jn = j + 1 < G ? j + 1 : j;
+                            const float4 an = g[jn], con = g[64 + jn], cdn = g[128 + jn];
+                            __builtin_amdgcn_sched_barrier(0);
+                            chain = entry(a, co, cd, chain);
+                            a = an; co = con; cd = cdn;
+                        }
+                        k += G; g += G;
+                    } while ((k + G <= cnt) & (ballot64(T > 0.0f) != 0ull));   // both asked every time: one block, no inner branch
+                }
+                if (k < cnt && ballot64(T > 0.0f) != 0ull)
+                    for (; k < cnt; ++k, ++g) chain = entry(g[0], g[64], g[128], chain);
             }
         }
     }
@@ -253,6 +301,21 @@ __global__ __launch_bounds__(kBlock) void resolve_marked_kernel(Frame f, GeomVie
     }
 }
 
+// Strip-walk group size of the forward kernel (the instantiations launch_render_forward dispatches on). Same images bit for
+// bit; 1 is the one-entry loop, kept as the partner of the exactness test and of A/B timing. (8 was built and measured: it
+// passed the same A/B and came out 3.8 us behind 4, profiles/render_forward_groups_ab.txt.)
+constexpr int kForwardGroupDefault = 4;
+static bool forward_group_built(int g) { return g == 1 || g == 4; }
+static int g_forward_group = [] { const char* e = getenv("MVI_RASTER_FORWARD_GROUP"); const int v = e ? atoi(e) : 0;
+                                  return forward_group_built(v) ? v : kForwardGroupDefault; }();
+int set_forward_group(int g) {
+    const int old = g_forward_group;
+    if (g == -1) return old;
+    if (g != 0 && !forward_group_built(g)) return MVI_EINVAL;
+    g_forward_group = g == 0 ? kForwardGroupDefault : g;
+    return old;
+}
+
 int launch_zero_fill(void* p, size_t bytes, hipStream_t st);
 int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D,
                           float* out_color, float* out_depth, hipStream_t st, float* zero_rows) {
@@ -278,8 +341,15 @@ int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView i
                                f, g);
         }
     }
-    hipLaunchKernelGGL(render_forward_kernel, dim3(blocks), dim3(kBlock), 0, st, f, im.ranges, plist, g.xy,
-                       g.rgbd, g.conic_opacity, im.final_T, im.n_contrib, out_color, out_depth, z, g.color_src, g.clamped);
+#define MVI_RENDER_FORWARD(G)                                                                                          \
+    hipLaunchKernelGGL(render_forward_kernel<G>, dim3(blocks), dim3(kBlock), 0, st, f, im.ranges, plist, g.xy, g.rgbd, \
+                       g.conic_opacity, im.final_T, im.n_contrib, out_color, out_depth, z, g.color_src, g.clamped)
+    switch (g_forward_group) {
+        case 1: MVI_RENDER_FORWARD(1); break;
+        case 4: MVI_RENDER_FORWARD(4); break;
+        default: return MVI_EINVAL;                              // a kernel that is not built is an error, never another kernel
+    }
+#undef MVI_RENDER_FORWARD
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 
