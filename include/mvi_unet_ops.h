@@ -564,10 +564,15 @@ int mvi_attention_forward_strided_qlog2(const void* q, const void* k, const void
 int mvi_attention_temporal_strided_qlog2(const void* q, const void* k, const void* v, void* out, int32_t Bo, int32_t T,
                                          int32_t S, int32_t H, int32_t D, int32_t dtype, int64_t qkv_token_stride,
                                          int64_t out_token_stride, void* stream);
-/* Which kernel serves a temporal-attention call of this shape: 1 = the MFMA kernel of csrc/attn_temporal.hip (bf16 / f16, D = 64,
- * T <= 16, 16-byte aligned rows), 0 = the fp32-math kernel of csrc/attn_rowtile.hip. Strides in elements, 0 = H*D. */
+/* Which kernel serves a temporal-attention call of this shape: 1 = the 16-frame MFMA kernel of csrc/attn_temporal.hip (bf16 / f16,
+ * D = 64, T <= 16, 16-byte aligned rows), 0 = any other. Strides in elements, 0 = H*D. */
 int mvi_attention_temporal_kernel_variant(int32_t T, int32_t H, int32_t D, int32_t dtype, int64_t qkv_token_stride,
                                           int64_t out_token_stride);
+/* The frame capacity of the MFMA kernel that serves the call: 16 (csrc/attn_temporal.hip, T <= 16), 32 (csrc/attn_temporal32.hip,
+ * 16 < T <= 32; both bf16 / f16, D = 64, 16-byte aligned rows), or 0 = the fp32-math kernel of csrc/attn_rowtile.hip (everything
+ * else, and every call while MVI_ATTN_TEMPORAL_MFMA=0 is set). The temporal entry points dispatch on exactly this function. */
+int mvi_attention_temporal_kernel_kind(int32_t T, int32_t H, int32_t D, int32_t dtype, int64_t qkv_token_stride,
+                                       int64_t out_token_stride);
 
 /* x[r, :] = softmax(scale * x[r, :]) in place, x [rows, cols] contiguous, scale > 0, fp32 statistics. The scaled
  * softmax between the two library GEMMs of the first-stage autoencoder's single-head attention with D = C = 512
@@ -603,7 +608,7 @@ int mvi_attention_backward(const void* q, const void* k, const void* v, const vo
                            void* dk, void* dv, int32_t B, int32_t H, int32_t Sq, int32_t Sk, int32_t D, float scale, int32_t dtype,
                            void* workspace, size_t workspace_bytes, void* stream);
 /* Backward of mvi_attention_temporal, same layout [(Bo*T), S, H, D] for all seven tensors, nothing regrouped: dq, dk, dv from q, k, v,
- * dout. The softmax is recomputed in fp32 (T <= 16); fp32 / bf16 / f16 I/O, D in {16, 32, 64}. Deterministic. */
+ * dout. The softmax is recomputed in fp32 (T <= 32); fp32 / bf16 / f16 I/O, D in {16, 32, 64}. Deterministic. */
 int mvi_attention_temporal_backward(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
                                     int32_t Bo, int32_t T, int32_t S, int32_t H, int32_t D, float scale, int32_t dtype, void* stream);
 

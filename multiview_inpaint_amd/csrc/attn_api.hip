@@ -1,5 +1,5 @@
 // The C entry points of forward attention (include/mvi_unet_ops.h) and the one place that picks a kernel for a call: spatial
-// (attn_flash.hip, attn_flash8m16.hip, attn_rowtile.hip) and temporal (attn_temporal.hip, attn_rowtile.hip). The backward's entry
+// (attn_flash.hip, attn_flash8m16.hip, attn_rowtile.hip) and temporal (attn_temporal.hip, attn_temporal32.hip, attn_rowtile.hip). The backward's entry
 // points are in attn_bwd.hip and ask the same functions.
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
@@ -99,11 +99,22 @@ extern "C" int mvi_attention_forward_strided_qlog2(const void* q, const void* k,
     return attention_forward_impl(q, k, v, out, B, H, Sq, Sk, D, kLn2, dtype, q_token_stride, kv_token_stride, out_token_stride, stream, true);
 }
 
-// 1 when the MFMA kernel of csrc/attn_temporal.hip serves this call, 0 for the fp32-math kernel of csrc/attn_rowtile.hip
+// The frame capacity of the MFMA kernel that serves this call: 16 (csrc/attn_temporal.hip), 32 (csrc/attn_temporal32.hip), or 0 for the
+// fp32-math kernel of csrc/attn_rowtile.hip. The ONE place that picks the temporal kernel.
+extern "C" int mvi_attention_temporal_kernel_kind(int32_t T, int32_t H, int32_t D, int32_t dtype, int64_t qkv_token_stride,
+                                                  int64_t out_token_stride) {
+    static const bool off = getenv("MVI_ATTN_TEMPORAL_MFMA") && getenv("MVI_ATTN_TEMPORAL_MFMA")[0] == '0';     // same-box A/B runs: both off
+    if (off) return 0;
+    const int64_t hd = (int64_t)H * D;
+    if (mvi::attn_temporal16_ok(T, D, dtype, hd, qkv_token_stride, out_token_stride, nullptr, nullptr, nullptr, nullptr)) return 16;
+    if (mvi::attn_temporal32_ok(T, D, dtype, hd, qkv_token_stride, out_token_stride, nullptr, nullptr, nullptr, nullptr)) return 32;
+    return 0;
+}
+
+// 1 when the 16-frame MFMA kernel of csrc/attn_temporal.hip serves this call, 0 otherwise
 extern "C" int mvi_attention_temporal_kernel_variant(int32_t T, int32_t H, int32_t D, int32_t dtype, int64_t qkv_token_stride,
                                                      int64_t out_token_stride) {
-    static const bool off = getenv("MVI_ATTN_TEMPORAL_MFMA") && getenv("MVI_ATTN_TEMPORAL_MFMA")[0] == '0';     // same-box A/B runs
-    return !off && mvi::attn_temporal16_ok(T, D, dtype, (int64_t)H * D, qkv_token_stride, out_token_stride, nullptr, nullptr, nullptr, nullptr);
+    return mvi_attention_temporal_kernel_kind(T, H, D, dtype, qkv_token_stride, out_token_stride) == 16;
 }
 
 static int attention_temporal_impl(const void* q, const void* k, const void* v, void* out, int32_t Bo, int32_t T, int32_t S,
@@ -119,9 +130,14 @@ static int attention_temporal_impl(const void* q, const void* k, const void* v, 
     hipStream_t st = (hipStream_t)stream;
     const int B = Bo * S;
     const auto launched = [](int rc) { return rc ? mvi::unet_fail(rc, "temporal attention: kernel launch failed") : MVI_OK; };
-    if (mvi_attention_temporal_kernel_variant(T, H, D, dtype, qkv_ts, o_ts) && mvi::attn_temporal16_ok(T, D, dtype, hd, qkv_ts, o_ts, q, k, v, out))
+    const int kind = mvi_attention_temporal_kernel_kind(T, H, D, dtype, qkv_ts, o_ts);
+    if (kind == 16 && mvi::attn_temporal16_ok(T, D, dtype, hd, qkv_ts, o_ts, q, k, v, out))
         return mvi::dispatch_dtype16(dtype, "temporal attention: unknown dtype", [&](auto t) {
             return launched(mvi::attn_temporal16_launch<typename decltype(t)::type>(q, k, v, out, Bo, T, S, H, scale, st, qkv_ts, o_ts));
+        });
+    if (kind == 32 && mvi::attn_temporal32_ok(T, D, dtype, hd, qkv_ts, o_ts, q, k, v, out))
+        return mvi::dispatch_dtype16(dtype, "temporal attention: unknown dtype", [&](auto t) {
+            return launched(mvi::attn_temporal32_launch<typename decltype(t)::type>(q, k, v, out, Bo, T, S, H, scale, st, qkv_ts, o_ts));
         });
     return mvi::dispatch_dtype(dtype, "temporal attention: unknown dtype", [&](auto t) {
         return launched(mvi::attn_rowtile_launch<typename decltype(t)::type>(q, k, v, out, B, H, T, T, D, scale, st, S, qkv_ts, qkv_ts, o_ts));

@@ -27,8 +27,8 @@
 // Rows past the end of a ragged last tile: resident rows are loaded as zeros and not stored; streamed rows are loaded as zeros and
 // their P and dS are set to zero. No lane is ever masked around a transposed LDS read (it needs EXEC all ones).
 //
-// Temporal backward (softmax over the T <= 16 frames of each (video, token, head), [(Bo T), S, H, D], nothing regrouped): HBM-bound
-// (seven tensors against T x T scores), so one 64-thread block per problem recomputes the softmax in fp32 from an LDS copy.
+// Temporal backward (softmax over the T <= 32 frames of each (video, token, head), [(Bo T), S, H, D], nothing regrouped): seven tensors
+// against T x T scores, so one block per problem (64 threads for T <= 16, 256 above) recomputes the softmax in fp32 from an LDS copy.
 #include <cstdlib>
 #include <type_traits>
 
@@ -304,23 +304,36 @@ void attn_bwd_kernel(const T* __restrict__ res1, const T* __restrict__ res2, con
     }
 }
 
-// ---- temporal: one 64-thread block per (video, token, head); fp32 math on an LDS copy of q, k, v, dout [T][D]
+// ---- temporal: one block per (video, token, head); fp32 math on an LDS copy of q, k, v, dout [T][D]
 template <typename T> __device__ __forceinline__ float ld_f(const T* p) { return (float)*p; }
 template <> __device__ __forceinline__ float ld_f<__hip_bfloat16>(const __hip_bfloat16* p) { return __bfloat162float(*p); }
 template <> __device__ __forceinline__ float ld_f<__half>(const __half* p) { return __half2float(*p); }
 template <typename T> __device__ __forceinline__ void st_f(T* p, float x) { *p = (T)x; }
 template <> __device__ __forceinline__ void st_f<__hip_bfloat16>(__hip_bfloat16* p, float x) { *p = __float2bfloat16(x); }
 template <> __device__ __forceinline__ void st_f<__half>(__half* p, float x) { *p = __float2half(x); }
+// global -> the LDS copy: to fp32, or as it is where the copy keeps the I/O type
+template <typename L, typename T> __device__ __forceinline__ L to_lds(const T* p) {
+    if constexpr (std::is_same<L, T>::value) return *p;
+    else return ld_f(p);
+}
 
-constexpr int kTMax = 16;
+constexpr int kTMax = 32;
 
-template <typename T, int D>
-__global__ __launch_bounds__(64) void attn_temporal_bwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
-                                                               const T* __restrict__ dout, T* __restrict__ dq, T* __restrict__ dk,
-                                                               T* __restrict__ dv, int Tn, int S, int H, float scale) {
-    constexpr int kRow = D + 1;                                  // rows one bank apart
-    __shared__ float s_q[kTMax * kRow], s_k[kTMax * kRow], s_v[kTMax * kRow], s_do[kTMax * kRow];
-    __shared__ float s_p[kTMax * (kTMax + 1)], s_ds[kTMax * (kTMax + 1)];
+// kCap = 16 (T <= 16): 64 threads and an fp32 copy, 18.4 KB at D = 64. kCap = 32 (16 < T <= 32): the fp32 copy would be 41 KB per block
+// — three blocks per CU — so a block has 256 threads and a 16-bit input stays 16-bit in LDS (25 KB: six blocks, 24 waves per CU). A
+// 16-bit number is an fp32 number: the same formulas on the same values in the same fixed summation order, whatever the thread count.
+// Measured at (Bo, T, S, H) = (2, 25, 9216, 5) bf16: 1.92 ms; an fp32 copy with 256 threads 2.41, the 16-bit copy with 128 / 64
+// threads 2.04 / 2.82 ('Attention under autograd').
+template <typename T, int D, int kCap>
+__global__ __launch_bounds__(kCap == 16 ? 64 : 256) void attn_temporal_bwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                                 const T* __restrict__ v, const T* __restrict__ dout,
+                                                                                 T* __restrict__ dq, T* __restrict__ dk, T* __restrict__ dv,
+                                                                                 int Tn, int S, int H, float scale) {
+    constexpr int kThreads = kCap == 16 ? 64 : 256;
+    using L = typename std::conditional<kCap == 16, float, T>::type;     // element type of the LDS copy
+    constexpr int kRow = D + (sizeof(L) == 4 ? 1 : 2);           // rows one bank apart
+    __shared__ L s_q[kCap * kRow], s_k[kCap * kRow], s_v[kCap * kRow], s_do[kCap * kRow];
+    __shared__ float s_p[kCap * (kCap + 1)], s_ds[kCap * (kCap + 1)];
     const int tid = threadIdx.x;
     const int64_t prob = blockIdx.x;                             // (bo S + s) H + h
     const int h = (int)(prob % H);
@@ -329,31 +342,31 @@ __global__ __launch_bounds__(64) void attn_temporal_bwd_kernel(const T* __restri
     const int64_t hd = (int64_t)H * D;
     const int64_t base = ((bo * Tn) * S + s) * hd + (int64_t)h * D;      // frame t: + t S hd
     const int64_t fstride = (int64_t)S * hd;
-    for (int e = tid; e < Tn * D; e += 64) {
+    for (int e = tid; e < Tn * D; e += kThreads) {
         const int t = e / D, d = e % D;
         const int64_t o = base + t * fstride + d;
-        s_q[t * kRow + d] = ld_f(q + o);
-        s_k[t * kRow + d] = ld_f(k + o);
-        s_v[t * kRow + d] = ld_f(v + o);
-        s_do[t * kRow + d] = ld_f(dout + o);
+        s_q[t * kRow + d] = to_lds<L>(q + o);
+        s_k[t * kRow + d] = to_lds<L>(k + o);
+        s_v[t * kRow + d] = to_lds<L>(v + o);
+        s_do[t * kRow + d] = to_lds<L>(dout + o);
     }
     __syncthreads();
     // scores and dP: entry (i, j) per thread, scaled scores into s_p, dP into s_ds
-    for (int e = tid; e < Tn * Tn; e += 64) {
+    for (int e = tid; e < Tn * Tn; e += kThreads) {
         const int i = e / Tn, j = e % Tn;
         float a = 0.f, c = 0.f;
 #pragma unroll 8
         for (int d = 0; d < D; ++d) {
-            a = __builtin_fmaf(s_q[i * kRow + d], s_k[j * kRow + d], a);
-            c = __builtin_fmaf(s_do[i * kRow + d], s_v[j * kRow + d], c);
+            a = __builtin_fmaf(ld_f(s_q + i * kRow + d), ld_f(s_k + j * kRow + d), a);
+            c = __builtin_fmaf(ld_f(s_do + i * kRow + d), ld_f(s_v + j * kRow + d), c);
         }
-        s_p[i * (kTMax + 1) + j] = a * scale;
-        s_ds[i * (kTMax + 1) + j] = c;
+        s_p[i * (kCap + 1) + j] = a * scale;
+        s_ds[i * (kCap + 1) + j] = c;
     }
     __syncthreads();
     if (tid < Tn) {                                              // one softmax row per thread
-        float* const pr = s_p + tid * (kTMax + 1);
-        float* const dr = s_ds + tid * (kTMax + 1);
+        float* const pr = s_p + tid * (kCap + 1);
+        float* const dr = s_ds + tid * (kCap + 1);
         float m = pr[0];
         for (int j = 1; j < Tn; ++j) m = fmaxf(m, pr[j]);
         float l = 0.f;
@@ -364,13 +377,13 @@ __global__ __launch_bounds__(64) void attn_temporal_bwd_kernel(const T* __restri
         for (int j = 0; j < Tn; ++j) dr[j] = pr[j] * (dr[j] - dl);
     }
     __syncthreads();
-    for (int e = tid; e < Tn * D; e += 64) {
+    for (int e = tid; e < Tn * D; e += kThreads) {
         const int t = e / D, d = e % D;
         float aq = 0.f, ak = 0.f, av = 0.f;
         for (int j = 0; j < Tn; ++j) {
-            aq = __builtin_fmaf(s_ds[t * (kTMax + 1) + j], s_k[j * kRow + d], aq);       // dQ_t = scale sum_j dS_tj k_j
-            ak = __builtin_fmaf(s_ds[j * (kTMax + 1) + t], s_q[j * kRow + d], ak);       // dK_t = scale sum_i dS_it q_i
-            av = __builtin_fmaf(s_p[j * (kTMax + 1) + t], s_do[j * kRow + d], av);       // dV_t = sum_i P_it dout_i
+            aq = __builtin_fmaf(s_ds[t * (kCap + 1) + j], ld_f(s_k + j * kRow + d), aq);      // dQ_t = scale sum_j dS_tj k_j
+            ak = __builtin_fmaf(s_ds[j * (kCap + 1) + t], ld_f(s_q + j * kRow + d), ak);      // dK_t = scale sum_i dS_it q_i
+            av = __builtin_fmaf(s_p[j * (kCap + 1) + t], ld_f(s_do + j * kRow + d), av);      // dV_t = sum_i P_it dout_i
         }
         const int64_t o = base + t * fstride + d;
         st_f(dq + o, aq * scale);
@@ -383,12 +396,18 @@ template <typename T>
 static int temporal_bwd_launch(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv, int Bo, int Tn,
                                int S, int H, int D, float scale, hipStream_t st) {
     const unsigned grid = (unsigned)((int64_t)Bo * S * H);
-#define MVI_TB(DD)                                                                                                                        \
-    hipLaunchKernelGGL((attn_temporal_bwd_kernel<T, DD>), dim3(grid), dim3(64), 0, st, (const T*)q, (const T*)k, (const T*)v,            \
-                       (const T*)dout, (T*)dq, (T*)dk, (T*)dv, Tn, S, H, scale)
-    if (D == 16) MVI_TB(16);
-    else if (D == 32) MVI_TB(32);
-    else MVI_TB(64);
+#define MVI_TB(DD, CAP)                                                                                                                   \
+    hipLaunchKernelGGL((attn_temporal_bwd_kernel<T, DD, CAP>), dim3(grid), dim3(CAP == 16 ? 64 : 256), 0, st, (const T*)q, (const T*)k,  \
+                       (const T*)v, (const T*)dout, (T*)dq, (T*)dk, (T*)dv, Tn, S, H, scale)
+    if (Tn <= 16) {
+        if (D == 16) MVI_TB(16, 16);
+        else if (D == 32) MVI_TB(32, 16);
+        else MVI_TB(64, 16);
+    } else {
+        if (D == 16) MVI_TB(16, 32);
+        else if (D == 32) MVI_TB(32, 32);
+        else MVI_TB(64, 32);
+    }
 #undef MVI_TB
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
@@ -458,7 +477,7 @@ extern "C" int mvi_attention_temporal_backward(const void* q, const void* k, con
                                                int32_t Bo, int32_t T, int32_t S, int32_t H, int32_t D, float scale, int32_t dtype, void* stream) {
     if (Bo < 0 || T <= 0 || S <= 0 || H <= 0 || D <= 0) return mvi::unet_fail(MVI_EINVAL, "temporal attention backward: bad shape");
     if (Bo == 0) return MVI_OK;
-    if (T > mvi::bwd::kTMax) return mvi::unet_fail(MVI_EINVAL, "temporal attention backward: at most 16 frames");
+    if (T > mvi::bwd::kTMax) return mvi::unet_fail(MVI_EINVAL, "temporal attention backward: at most 32 frames");
     if (D != 16 && D != 32 && D != 64) return mvi::unet_fail(MVI_EINVAL, "temporal attention backward: head dim must be 16, 32 or 64");
     if (!q || !k || !v || !dout || !dq || !dk || !dv) return mvi::unet_fail(MVI_EINVAL, "temporal attention backward: NULL pointer");
     if ((int64_t)Bo * S * H > 0x7FFFFFFFll) return mvi::unet_fail(MVI_EINVAL, "temporal attention backward: too many problems");

@@ -31,6 +31,13 @@ template <typename T>
 int attn_temporal16_launch(const void* q, const void* k, const void* v, void* out, int Bo, int Tn, int S, int H, float scale, hipStream_t st,
                            int64_t qkv_ts, int64_t o_ts);
 
+// attn_temporal32.hip: the same for 16 < T <= 32 (a second key tile and a second query tile)
+bool attn_temporal32_ok(int T, int D, int dtype, int64_t hd, int64_t qkv_ts, int64_t o_ts, const void* q, const void* k, const void* v,
+                        const void* out);
+template <typename T>
+int attn_temporal32_launch(const void* q, const void* k, const void* v, void* out, int Bo, int Tn, int S, int H, float scale, hipStream_t st,
+                           int64_t qkv_ts, int64_t o_ts);
+
 // attn_api.hip. Does the forward of this kernel variant (mvi_attention_kernel_variant) and dtype round scale * log2(e) into Q instead
 // of multiplying the fp32 scores by it? The forward launches by it and the backward recomputes P by it: L came from those scores.
 bool attention_folds_scale(int variant, int dtype);

@@ -5,8 +5,8 @@ BASELINE.json configs[0] ("sgm VideoUNet single denoise step ... fp32 on CPU PyT
 reference's own CPU-runnable case, not a fallback for the GPU.
 
 Under autograd (ControlNet training — SURVEY.md §2 row 21) attention stays on the HIP path, forward and backward
-(csrc/attn_bwd.hip: `attention` for bf16 / f16 with D = 64 and more than 32 keys, `attention_temporal` for every shape its
-forward takes), and so do GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip: `group_norm`, `group_norm_frames`, `group_norm_tokens`, and the
+(csrc/attn_bwd.hip: `attention` for bf16 / f16 with D = 64 and more than 32 keys, `attention_temporal` up to 32 frames in every
+type and head dim its forward takes), and so do GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip: `group_norm`, `group_norm_frames`, `group_norm_tokens`, and the
 token-major `group_norm_tok2tok` where `group_norm_tok2tok_backward_pays` says so) and GEGLU
 (csrc/ff_geglu_bwd.hip: `linear_geglu` at K = 320 in bf16 / f16, the projection recomputed, never stored; csrc/geglu.hip: `geglu`;
 from the sizes at which they were measured faster, `linear_geglu_backward_pays` / `geglu_backward_pays`), and the residual add(s) +
@@ -324,7 +324,8 @@ class _AttentionFn(torch.autograd.Function):
 
 
 class _AttentionTemporalFn(torch.autograd.Function):
-    """attention_temporal with its HIP backward (the softmax over T <= 16 frames is recomputed: only q, k, v are held)."""
+    """attention_temporal with its HIP backward (the softmax over T <= 32 frames is recomputed: only q, k, v are held). The forward is
+    the inference entry: the MFMA kernels up to 16 and up to 32 frames where they apply (bf16 / f16, D = 64), else the fp32-math kernel."""
 
     @staticmethod
     def forward(ctx, q, k, v, heads, T):
@@ -346,7 +347,7 @@ class _AttentionTemporalFn(torch.autograd.Function):
 def _temporal_backward_supported(q, k, v, heads, T):
     D = q.shape[-1] // max(heads, 1)
     return (q.dtype in (torch.float32, torch.bfloat16, torch.float16) and k.dtype == q.dtype and v.dtype == q.dtype
-            and q.shape == k.shape == v.shape and D in (16, 32, 64) and D * heads == q.shape[-1] and 0 < T <= 16 and q.shape[0] % T == 0)
+            and q.shape == k.shape == v.shape and D in (16, 32, 64) and D * heads == q.shape[-1] and 0 < T <= 32 and q.shape[0] % T == 0)
 
 
 def attention(q, k, v, heads):
