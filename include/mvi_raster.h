@@ -99,6 +99,18 @@ int mvi_raster_forward_render_prepare(const mvi_raster_settings* s, int32_t P, i
                                       size_t binning_bytes, void* image, size_t image_bytes, float* out_color,
                                       float* out_depth, float* grad_rows_scratch, void* stream);
 
+/* mvi_raster_forward_render_prepare with two more per-pixel outputs, computed by the same render kernel from the same geometry,
+ * sort and binning state (no second preprocess or sort): out_expected_depth [1,H,W] = sum_i z_i alpha_i T_i, the UNNORMALISED
+ * accumulated view-space depth over exactly the entries the colour composites (divide by alpha for the normalised depth), and
+ * out_alpha [1,H,W] = 1 - T_final (bit for bit 1 - mvi_raster_views.final_T). Both are differentiable:
+ * mvi_raster_backward_render_aux. out_color / out_depth (the median depth) are what mvi_raster_forward_render writes, bit for
+ * bit. grad_rows_scratch may be NULL (nothing is zeroed then). */
+int mvi_raster_forward_render_aux(const mvi_raster_settings* s, int32_t P, int64_t num_rendered,
+                                  const int32_t* radii, void* geom, size_t geom_bytes, void* binning,
+                                  size_t binning_bytes, void* image, size_t image_bytes, float* out_color,
+                                  float* out_depth, float* grad_rows_scratch, float* out_expected_depth, float* out_alpha,
+                                  void* stream);
+
 /* Backward. dL_dout_color [3,H,W]. Gradient outputs are overwritten (not accumulated):
  * dL_dmeans3D [P,3], dL_dmeans2D [P,3] (x,y = NDC-scaled screen gradient, z = 0; consumer
  * gs-simp/scene/gaussian_model.py:482-484), dL_dopacity [P], and
@@ -178,6 +190,21 @@ int mvi_raster_backward_geom(const mvi_raster_settings* s, int32_t P, int32_t M,
                              const float* grad_rows_scratch, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dopacity,
                              float* dL_dshs, float* dL_dcolors, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
                              void* stream);
+
+/* Backward of the aux outputs of mvi_raster_forward_render_aux. dL_dexpected_depth / dL_dalpha [1,H,W]; either may be NULL
+ * (= zero), with both NULL nothing is launched. mvi_raster_backward_render_aux ADDS its share into the accumulation rows
+ * grad_rows_scratch [P][16] — mean2D, conic and opacity into slots 0..5 (the slots the colour backward adds into: the two
+ * shares sum), dL/dz (view depth) into slot 9 — and marks the Gaussians it added to in the gradient support. It never zeroes
+ * the rows: run it on rows that are zeroed (mvi_raster_forward_render_aux / _prepare, or mvi_raster_backward_render) and before
+ * the per-Gaussian chain rule reads them — between mvi_raster_backward_render and mvi_raster_backward_geom, or in front of a
+ * one-call mvi_raster_backward / _raw with grad_rows_prezeroed = 1 (float adds commute up to rounding).
+ * mvi_raster_backward_depth_to_means then ADDS rows[i][9] * viewmatrix[0:3][2] into dL_dmeans3D [P,3] (after the raw forward:
+ * dL_dxyz) for the rows with a depth gradient; it runs after the chain rule has written dL_dmeans3D. */
+int mvi_raster_backward_render_aux(const mvi_raster_settings* s, int32_t P, int64_t num_rendered, const int32_t* radii,
+                                   const void* geom, const void* binning, const void* image, const float* dL_dexpected_depth,
+                                   const float* dL_dalpha, float* grad_rows_scratch, void* stream);
+int mvi_raster_backward_depth_to_means(const mvi_raster_settings* s, int32_t P, const float* grad_rows_scratch,
+                                       float* dL_dmeans3D, void* stream);
 
 /* mvi_raster_backward_geom for the Gaussians [first, first + count) only (any first row): every pointer is the
  * base of the FULL [P, ...] array, as in mvi_raster_backward_geom; only rows of the range are read and written. Lets a

@@ -101,6 +101,12 @@ def lib():
     L.mvi_raster_forward_render.argtypes = [C.POINTER(RasterSettings), i32, i64, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp]
     L.mvi_raster_forward_render_prepare.restype = C.c_int
     L.mvi_raster_forward_render_prepare.argtypes = [C.POINTER(RasterSettings), i32, i64, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp]
+    L.mvi_raster_forward_render_aux.restype = C.c_int
+    L.mvi_raster_forward_render_aux.argtypes = [C.POINTER(RasterSettings), i32, i64, vp, vp, sz, vp, sz, vp, sz] + [vp] * 6
+    L.mvi_raster_backward_render_aux.restype = C.c_int
+    L.mvi_raster_backward_render_aux.argtypes = [C.POINTER(RasterSettings), i32, i64] + [vp] * 8
+    L.mvi_raster_backward_depth_to_means.restype = C.c_int
+    L.mvi_raster_backward_depth_to_means.argtypes = [C.POINTER(RasterSettings), i32, vp, vp, vp]
     L.mvi_raster_backward.restype = C.c_int
     L.mvi_raster_backward.argtypes = [C.POINTER(RasterSettings), i32, i32, i64] + [vp] * 20 + [i32, vp]
     L.mvi_raster_backward_render.restype = C.c_int

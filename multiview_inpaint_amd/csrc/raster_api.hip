@@ -262,7 +262,8 @@ static int forward_geom_impl(const mvi_raster_settings* s, mvi::Frame& f, int32_
 
 static int forward_render_impl(const mvi_raster_settings* s, int32_t P, int64_t D, const int32_t* radii,
                                void* geom, size_t geom_bytes, void* binning, size_t binning_bytes, void* image,
-                               size_t image_bytes, float* out_color, float* out_depth, float* grad_rows_to_zero, void* stream) {
+                               size_t image_bytes, float* out_color, float* out_depth, float* grad_rows_to_zero, void* stream,
+                               float* out_expected_depth = nullptr, float* out_alpha = nullptr) {
     mvi::Frame f;
     if (int rc = make_frame(s, P, 0, f)) return rc;
     if (!image || !out_color || !out_depth) return fail(MVI_EINVAL, "NULL image/out_color/out_depth%s");
@@ -280,7 +281,7 @@ static int forward_render_impl(const mvi_raster_settings* s, int32_t P, int64_t 
         return hip_fail("binning", hipGetLastError());
     {
         mvi::StageTimer tm(mvi::kStRenderFwd, st);
-        if (mvi::launch_render_forward(f, g, b, im, D, out_color, out_depth, st, grad_rows_to_zero))
+        if (mvi::launch_render_forward(f, g, b, im, D, out_color, out_depth, st, grad_rows_to_zero, out_expected_depth, out_alpha))
             return hip_fail("render_forward", hipGetLastError());
     }
     return MVI_OK;
@@ -299,6 +300,15 @@ int mvi_raster_forward_render_prepare(const mvi_raster_settings* s, int32_t P, i
                                       void* stream) {
     return forward_render_impl(s, P, D, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, out_color, out_depth,
                                grad_rows_scratch, stream);
+}
+
+int mvi_raster_forward_render_aux(const mvi_raster_settings* s, int32_t P, int64_t D, const int32_t* radii,
+                                  void* geom, size_t geom_bytes, void* binning, size_t binning_bytes, void* image,
+                                  size_t image_bytes, float* out_color, float* out_depth, float* grad_rows_scratch,
+                                  float* out_expected_depth, float* out_alpha, void* stream) {
+    if (!out_expected_depth || !out_alpha) return fail(MVI_EINVAL, "NULL out_expected_depth/out_alpha%s");
+    return forward_render_impl(s, P, D, radii, geom, geom_bytes, binning, binning_bytes, image, image_bytes, out_color, out_depth,
+                               grad_rows_scratch, stream, out_expected_depth, out_alpha);
 }
 
 static int backward_render_impl(mvi::Frame& f, int32_t P, int64_t D, const int32_t* radii, const void* geom, const void* binning,
@@ -463,6 +473,36 @@ int mvi_raster_backward_render(const mvi_raster_settings* s, int32_t P, int64_t 
     if (int rc = make_frame(s, P, 0, f)) return rc;
     return backward_render_impl(f, P, D, radii, geom, binning, image, dL_dout_color, grad_rows_scratch, dL_dcolor_factor,
                                 sh_input, grad_rows_prezeroed, stream);
+}
+
+int mvi_raster_backward_render_aux(const mvi_raster_settings* s, int32_t P, int64_t D, const int32_t* radii, const void* geom,
+                                   const void* binning, const void* image, const float* dL_dexpected_depth,
+                                   const float* dL_dalpha, float* grad_rows_scratch, void* stream) {
+    mvi::Frame f;
+    if (int rc = make_frame(s, P, 0, f)) return rc;
+    if (P == 0 || (!dL_dexpected_depth && !dL_dalpha)) return MVI_OK;         // both NULL: zero gradients, nothing to add
+    if (D < 0 || D > 0xFFFFFFFFll) return fail(MVI_EINVAL, "num_rendered out of range%s: %lld", "", D);
+    if (!radii || !geom || !image || !grad_rows_scratch) return fail(MVI_EINVAL, "NULL required pointer in backward (aux)%s");
+    if (D > 0 && !binning) return fail(MVI_EINVAL, "NULL binning with num_rendered > 0%s");
+    mvi::GeomView g = mvi::carve_geom(const_cast<void*>(geom), P);
+    mvi::ImageView im = mvi::carve_image(const_cast<void*>(image), f.W, f.H);
+    mvi::BinningView b = mvi::carve_binning(const_cast<void*>(binning), D, f.W, f.H);
+    hipStream_t st = (hipStream_t)stream;
+    mvi::StageTimer tm(mvi::kStRenderBwd, st);
+    if (mvi::launch_render_backward_aux(f, g, b, im, D, dL_dexpected_depth, dL_dalpha, grad_rows_scratch, st))
+        return hip_fail("render_backward (aux)", hipGetLastError());
+    return MVI_OK;
+}
+
+int mvi_raster_backward_depth_to_means(const mvi_raster_settings* s, int32_t P, const float* grad_rows_scratch,
+                                       float* dL_dmeans3D, void* stream) {
+    mvi::Frame f;
+    if (int rc = make_frame(s, P, 0, f)) return rc;
+    if (P == 0) return MVI_OK;
+    if (!grad_rows_scratch || !dL_dmeans3D) return fail(MVI_EINVAL, "NULL pointer in backward_depth_to_means%s");
+    if (mvi::launch_depth_to_means(f, grad_rows_scratch, dL_dmeans3D, (hipStream_t)stream))
+        return hip_fail("depth_to_means", hipGetLastError());
+    return MVI_OK;
 }
 
 static int backward_geom_range_impl(const mvi_raster_settings* s, int32_t P, int32_t M, int32_t first, int32_t count,

@@ -569,7 +569,13 @@ int launch_binning2_level1(const Frame& f, GeomView g, hipStream_t st);
 // segments: the exact number of column segments if known (> 0), else the bound D is used to size the pass-2 grids
 int launch_binning2(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, int64_t segments, hipStream_t st);
 int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D,
-                          float* out_color, float* out_depth, hipStream_t st, float* zero_rows = nullptr);
+                          float* out_color, float* out_depth, hipStream_t st, float* zero_rows = nullptr,
+                          float* out_expected_depth = nullptr, float* out_alpha = nullptr);   // both or neither: the aux outputs
+// raster_render_aux.hip: backward of the expected-depth / alpha outputs. Adds into grad_rows (slots 0..5 and 9) and sets the
+// touched flags; either image gradient may be NULL (zero). depth_to_means: dL_dmeans3D[i] += grad_rows[i][9] * view[0:3][2].
+int launch_render_backward_aux(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, const float* dL_dexpected_depth,
+                               const float* dL_dalpha, float* grad_rows, hipStream_t st);
+int launch_depth_to_means(const Frame& f, const float* grad_rows, float* dL_dmeans3D, hipStream_t st);
 int launch_resolve_colors(const Frame& f, GeomView g, hipStream_t st);      // evaluates every colour still pending
 // fills g.depths, g.cov_a / g.cov_b and g.tiles_touched, which the forward leaves unwritten, from the forward's inputs
 int launch_materialize_geom_views(const Frame& f, const float* means3D, const float* scales, const float* rotations,

@@ -12,73 +12,12 @@
 #include <cstdlib>
 
 #include "raster_common.h"
+#include "raster_render_shared.h"
 
 namespace mvi {
 
-// ballot of a predicate that already lives in a lane mask: no 0/1 materialisation (__ballot(int) costs two VALU issues)
-__device__ __forceinline__ unsigned long long ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-
-
-// Per staged entry: t2 = 2 ln(255 o) (+ margin), the largest Mahalanobis distance^2 d^T conic d at which
-// alpha = o exp(-d^T conic d / 2) still reaches 1/255; negative = can never be active.
-__device__ __forceinline__ float active_t2(float4 co) {
-    float t2 = 2.0f * __logf(255.0f * co.w);
-    return t2 > 0.0f ? t2 * 1.001f + 0.01f : -1.0f;
-}
-
-// Exact conservative test "can any point of the pixel quadrant [qx0,qx0+7] x [qy0,qy0+7] be active?":
-// the minimum of the convex form f(d) = A dx^2 + 2 B dx dy + C dy^2 over the box is 0 if the centre
-// is inside; otherwise it lies on one of the (at most two) box edges facing the centre, where the
-// 1-D minimiser is a clamped closed form. Continuous minimum <= minimum over pixel centres, and t2
-// carries a margin that dwarfs the rcp / rounding error, so no active pair is ever dropped.
-__device__ __forceinline__ bool quad_overlap(float2 c, float4 co, float t2, float qx0, float qy0, float bw = 7.0f,
-                                             float bh = 7.0f) {
-    const float dxl = qx0 - c.x, dxr = dxl + bw, dyl = qy0 - c.y, dyr = dyl + bh;
-    const float px = fminf(fmaxf(0.0f, dxl), dxr), py = fminf(fmaxf(0.0f, dyl), dyr);   // box point nearest the centre, per axis
-    // edge x = px: dy* = clamp(-B px / C); edge y = py: dx* = clamp(-B py / A)
-    const float dy1 = fminf(fmaxf(-co.y * px * __builtin_amdgcn_rcpf(co.z), dyl), dyr);
-    const float dx2 = fminf(fmaxf(-co.y * py * __builtin_amdgcn_rcpf(co.x), dxl), dxr);
-    const float f1 = co.x * px * px + 2.0f * co.y * px * dy1 + co.z * dy1 * dy1;
-    const float f2 = co.x * dx2 * dx2 + 2.0f * co.y * dx2 * py + co.z * py * py;
-    // px == 0: only the y-facing edge matters (f2); py == 0: only f1; both 0: centre inside, f = 0
-    const float f = px == 0.0f ? (py == 0.0f ? 0.0f : f2) : (py == 0.0f ? f1 : fminf(f1, f2));
-    return f <= t2;
-}
-
-// Workgroups are handed to the 8 XCDs round-robin by linear id, and every XCD has its own L2. Tile t of a launch of
-// `tiles` workgroups is chosen so that XCD x works through ONE contiguous band of tiles (rows of the image): the ~11
-// tiles a Gaussian touches then gather its 40 bytes through the same L2 (and their gradient atomics meet there)
-// instead of through up to 8 of them.
-__device__ __forceinline__ int xcd_band_tile(int bid, int tiles) {
-    const int q = tiles >> 3, r = tiles & 7, x = bid & 7, i = bid >> 3;
-    return x * q + (x < r ? x : r) + i;
-}
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f2 splat(float v) { return f2{v, v}; }
-constexpr int kB2 = 128;                // threads per tile in the backward kernel: 2 wave64, two pixels per lane
-
-// power = -0.5 (A dx^2 + C dy^2) - B dx dy for the lane's two pixels (same x, adjacent y), ONE rounding recipe shared by
-// the forward and the backward kernel so the backward replays the forward's alpha / threshold decisions exactly:
-// products rounded, fma(dx, A dx, (C dy) dy), then fma(., -0.5, -(B dx) dy).
-__device__ __forceinline__ f2 gauss_power(float4 co, float dx, f2 dy) {
-#pragma clang fp contract(off)
-    const float ax = co.x * dx, bx = co.y * dx;
-    const f2 cyy = (co.z * dy) * dy;
-    const f2 sq = pk_fma(splat(dx), splat(ax), cyy);
-    const f2 bxy = bx * dy;
-    return pk_fma(sq, splat(-0.5f), -bxy);
-}
-
-__device__ __forceinline__ float gauss_power1(float4 co, float dx, float dy) {     // the same recipe, one pixel
-#pragma clang fp contract(off)
-    const float ax = co.x * dx, bx = co.y * dx;
-    const float cyy = (co.z * dy) * dy;
-    const float sq = __builtin_fmaf(dx, ax, cyy);
-    const float bxy = bx * dy;
-    return __builtin_fmaf(sq, -0.5f, -bxy);
-}
+// (ballot64, active_t2, quad_overlap, xcd_band_tile, gauss_power / gauss_power1 and wave_sum9 live in raster_render_shared.h:
+// raster_render_aux.hip replays the same decisions with them)
 
 // The CU's scalar unit issues one instruction per cycle for all four SIMDs, so the inner loop must
 // stay light on scalar work: the kept entries of a 64-entry chunk are compacted into a per-wave LDS
@@ -92,12 +31,16 @@ __device__ __forceinline__ float gauss_power1(float4 co, float dx, float dy) {  
 // of its pixels is still live (T > 0): if none is, nothing behind this point changes any output (test_T = 0: no
 // contribution, T stays 0), and the wave leaves the round's chunk loop. The cnt % G entries behind the last full group
 // are walked one by one: no padding entry is ever evaluated.
-template <int G>
+// AUX: the kernel also accumulates the expected depth sum z alpha T over exactly the entries it composites (one fma per entry
+// beside the colour's) and writes it and alpha = 1 - T_final; with AUX clear the two pointers are never read and the
+// instantiation is the colour-only kernel.
+template <int G, bool AUX>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G == 1 ? 1 : 6, G == 1 ? 8 : 6))) void render_forward_kernel(
     Frame f, const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ point_list,
     const float2* __restrict__ xy, float4* rgbd, const float4* __restrict__ conic_opacity,
     float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color,
-    float* __restrict__ out_depth, ZeroRegions zero, const ColorSource* __restrict__ color_src, uint8_t* clamped) {
+    float* __restrict__ out_depth, ZeroRegions zero, const ColorSource* __restrict__ color_src, uint8_t* clamped,
+    float* __restrict__ out_expected_depth, float* __restrict__ out_alpha) {
     __shared__ float2 s_xy[kBlock];
     __shared__ float s_t2[kBlock];
     __shared__ float4 s_co[kBlock];
@@ -122,6 +65,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G == 1 ?
 
     float T = inside ? 1.0f : 0.0f;                 // 0 = this pixel takes no further contributions
     float T_out = 1.0f, C2 = 0.f, Dp = kDepthSentinel, Tc = 1.0f;
+    [[maybe_unused]] float Dexp = 0.f;              // AUX: sum of depth * alpha * T
     f2 C01 = {0.f, 0.f};                            // red, green: one packed fma on the (aligned) first two registers of the colour
     uint32_t last = 0;
 
@@ -182,6 +126,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G == 1 ?
                 const float w = contrib ? alpha * T : 0.0f;
                 C01 = pk_fma(f2{cd.x, cd.y}, splat(w), C01);
                 C2 = __builtin_fmaf(cd.z, w, C2);
+                if constexpr (AUX) Dexp = __builtin_fmaf(cd.w, w, Dexp);
                 // median depth of the w-depth fork = depth of the entry that takes T from above 0.5 to below it (T > 0.5 and
                 // T (1 - alpha) < 0.5, both strict: oracle/raster_oracle.c orc_render_forward). Every contributing entry met
                 // while T > 0.5 overwrites the candidate and the T it leaves behind (two selects on one condition): the last
@@ -244,6 +189,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G == 1 ?
         out_color[hw + pix] = C01.y + T_out * f.bg[1];
         out_color[2 * hw + pix] = C2 + T_out * f.bg[2];
         out_depth[pix] = Tc < 0.5f ? Dp : kDepthSentinel;             // never crossed 0.5: the sentinel (gs-simp/gen_seq.py:50)
+        if constexpr (AUX) {
+            out_expected_depth[pix] = Dexp;
+            out_alpha[pix] = 1.0f - T_out;
+        }
     }
 }
 
@@ -318,7 +267,9 @@ int set_forward_group(int g) {
 
 int launch_zero_fill(void* p, size_t bytes, hipStream_t st);
 int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D,
-                          float* out_color, float* out_depth, hipStream_t st, float* zero_rows) {
+                          float* out_color, float* out_depth, hipStream_t st, float* zero_rows, float* out_expected_depth,
+                          float* out_alpha) {
+    if ((out_expected_depth == nullptr) != (out_alpha == nullptr)) return MVI_EINVAL;
     ZeroRegions z;
     if (zero_rows) {
         z.add(zero_rows, (size_t)f.P * kGradRow);
@@ -341,12 +292,15 @@ int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView i
                                f, g);
         }
     }
-#define MVI_RENDER_FORWARD(G)                                                                                          \
-    hipLaunchKernelGGL(render_forward_kernel<G>, dim3(blocks), dim3(kBlock), 0, st, f, im.ranges, plist, g.xy, g.rgbd, \
-                       g.conic_opacity, im.final_T, im.n_contrib, out_color, out_depth, z, g.color_src, g.clamped)
-    switch (g_forward_group) {
-        case 1: MVI_RENDER_FORWARD(1); break;
-        case 4: MVI_RENDER_FORWARD(4); break;
+#define MVI_RENDER_FORWARD(G, AUX)                                                                                          \
+    hipLaunchKernelGGL((render_forward_kernel<G, AUX>), dim3(blocks), dim3(kBlock), 0, st, f, im.ranges, plist, g.xy, g.rgbd, \
+                       g.conic_opacity, im.final_T, im.n_contrib, out_color, out_depth, z, g.color_src, g.clamped,            \
+                       out_expected_depth, out_alpha)
+    switch (g_forward_group * 2 + (out_alpha ? 1 : 0)) {
+        case 2: MVI_RENDER_FORWARD(1, false); break;
+        case 3: MVI_RENDER_FORWARD(1, true); break;
+        case 8: MVI_RENDER_FORWARD(4, false); break;
+        case 9: MVI_RENDER_FORWARD(4, true); break;
         default: return MVI_EINVAL;                              // a kernel that is not built is an error, never another kernel
     }
 #undef MVI_RENDER_FORWARD
@@ -370,58 +324,7 @@ int launch_zero_regions(const ZeroRegions& z, hipStream_t st) {
 // to wait for). Once per staged batch the block turns the raw sums into gradients and flushes
 // them with float atomics shaped as whole 64-byte rows (16 lanes per Gaussian): MI355X float atomics
 // run at the 64-B-request rate. Row layout of grad_rows [P][16]:
-//   0 mean2D.x  1 mean2D.y  2 conic A  3 conic B  4 conic C  5 opacity  6 r  7 g  8 b  9..15 unused
-constexpr int kRow = 16;
-
-// Wave totals of nine values by a halving butterfly: one level per bit of the lane index, and at every level TWO live
-// registers are folded into ONE that carries the first value's partial sums in the lanes whose bit is 0 and the second
-// value's in the lanes whose bit is 1 (9 -> 5 -> 3 -> 2 -> 1 registers); the odd register of a level takes a plain
-// full-width step and carries its partial sums in both halves. Levels, in order:
-//   bit 3, bit 2   two v_add_f32_dpp per pair, each writing half of the banks of a row (row_ror:n reads lane (l - n) mod 16
-//                  of the own row of 16: ror 8 is the partner l ^ 8 for every lane; ror 12 / ror 4 is l ^ 4 for the lanes with
-//                  bit 2 clear / set); one full-width add for the odd register (its partial sums no longer depend on bit 3
-//                  when bit 2 is folded, so ror 4 reads a value equal to the partner's in every lane)
-//   bit 4, bit 5   v_permlane16_swap / v_permlane32_swap exchange the odd rows (upper half) of the first register with
-//                  the even rows (lower half) of the second, then one plain add
-//   bit 0, bit 1   two quad_perm adds on the one register that is left
-// Lane <-> moment map of the result (a compile-time function of the lane, wave_sum9_moment): lane l < 32 holds the wave
-// total of argument (l >> 2), lanes 32..63 hold that of argument 8, every lane of a quad the same number. Lanes 0, 4, ..,
-// 32 are the nine owners (wave_sum9_owner). The sum is a balanced tree over the 64 lanes.
-// The DPP adds are asm because the compiler lowers update_dpp + add to v_mov_b32_dpp + v_add (two issues each; the
-// kernel is VALU-issue-bound). The s_nop in front covers the VALU-write -> DPP-read hazard for whatever precedes a block
-// (the assembler does not pad inline asm, and the compiler does not look into it; it does pad the swaps that read a
-// block's outputs); inside the first block every register is re-read at least four instructions after it was written.
-__device__ __forceinline__ constexpr int wave_sum9_moment(int lane) { return lane < 32 ? lane >> 2 : 8; }
-__device__ __forceinline__ constexpr bool wave_sum9_owner(int lane) { return (lane & 3) == 0 && lane <= 32; }
-#define MVI_FOLD(a, b, lo, hi, mlo, mhi)                                                                  \
-    "v_add_f32_dpp " a ", " a ", " a " row_ror:" lo " row_mask:0xf bank_mask:" mlo "\n\t"                  \
-    "v_add_f32_dpp " a ", " b ", " b " row_ror:" hi " row_mask:0xf bank_mask:" mhi "\n\t"
-#define MVI_FULL(a, n) "v_add_f32_dpp " a ", " a ", " a " row_ror:" n " row_mask:0xf bank_mask:0xf\n\t"
-__device__ __forceinline__ float wave_sum9(float m0, float m1, float m2, float m3, float m4, float m5, float m6, float m7,
-                                           float m8) {
-    asm("s_nop 1\n\t"
-        // bit 3: (m0, m2) -> m0, (m1, m3) -> m1, (m4, m6) -> m4, (m5, m7) -> m5: lanes 0..7 of a row | lanes 8..15
-        MVI_FOLD("%0", "%2", "8", "8", "0x3", "0xc") MVI_FOLD("%1", "%3", "8", "8", "0x3", "0xc")
-        MVI_FOLD("%4", "%6", "8", "8", "0x3", "0xc") MVI_FOLD("%5", "%7", "8", "8", "0x3", "0xc") MVI_FULL("%8", "8")
-        // bit 2: (m0, m1) -> m0, (m4, m5) -> m4: banks 0 and 2 | banks 1 and 3. Lane bits (3, 2) of m0 now name 2 a + b
-        MVI_FOLD("%0", "%1", "12", "4", "0x5", "0xa") MVI_FOLD("%4", "%5", "12", "4", "0x5", "0xa") MVI_FULL("%8", "4")
-        : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3), "+v"(m4), "+v"(m5), "+v"(m6), "+v"(m7), "+v"(m8));
-    // bit 4: rows 0, 2 <- m0..m3, rows 1, 3 <- m4..m7; the odd register is folded with itself
-    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(m0), __float_as_uint(m4), false, false);
-    const auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(m8), __float_as_uint(m8), false, false);
-    const float lo = __uint_as_float(a[0]) + __uint_as_float(a[1]), hi = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-    // bit 5: lanes 0..31 <- m0..m7, lanes 32..63 <- m8
-    const auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
-    float s = __uint_as_float(c[0]) + __uint_as_float(c[1]);
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
-        : "+v"(s));
-    return s;
-}
-#undef MVI_FOLD
-#undef MVI_FULL
+//   0 mean2D.x  1 mean2D.y  2 conic A  3 conic B  4 conic C  5 opacity  6 r  7 g  8 b  9 dL/dz (raster_render_aux.hip)  10..15 unused
 
 // Diagnostics (mvi_raster_dev_wave_sum9): one wave per block runs in[w][m][lane] through wave_sum9, the owners write out[w][m]
 __global__ __launch_bounds__(64) void wave_sum9_probe_kernel(const float* __restrict__ in, float* __restrict__ out) {

@@ -111,6 +111,13 @@ def _make_render(reference_render, base_model):
             scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
             projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
             campos=viewpoint_camera.camera_center, prefiltered=False)
+        if os.environ.get("MVI_RENDER_AUX") == "1":
+            # opt-in: the differentiable accumulated depth (sum z alpha T, unnormalised) and alpha (1 - T_final) from the same
+            # render, for depth-prior and mask / opacity losses; every other key is what the default path returns
+            o = GaussianRasterizer(raster_settings=settings).forward_raw_aux(
+                pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation)
+            return {"render": o.color, "depth": o.depth, "viewspace_points": screenspace_points, "visibility_filter": o.radii > 0,
+                    "radii": o.radii, "expected_depth": o.expected_depth, "alpha": o.alpha}
         image, radii, depth = GaussianRasterizer(raster_settings=settings).forward_raw(
             pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation)
         return {"render": image, "depth": depth, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,

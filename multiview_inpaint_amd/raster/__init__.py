@@ -65,7 +65,7 @@ class _Frame:
 class RasterState:
     """Scratch buffers one forward leaves behind for its backward (and for the parity tests)."""
     __slots__ = ("P", "M", "D", "W", "H", "geom", "binning", "image", "radii", "grad_rows", "rows_clean", "frame", "sources",
-                 "cov_sources")
+                 "cov_sources", "expected_depth", "alpha")     # the last two: only after a forward with aux=True
     # views no kernel reads: the forward leaves them unwritten and tensor() has them filled on demand
     ON_DEMAND_GEOM_VIEWS = ("depths", "cov3D_a", "cov3D_b", "tiles_touched")
 
@@ -101,6 +101,17 @@ class RasterState:
             self.rows_clean = False
             return self.grad_rows, 1
         return torch.empty(self.P, 16, dtype=torch.float32, device=dev), 0
+
+    def take_zeroed_rows(self, dev):
+        """Accumulation rows that ARE zero, with the gradient-support flags cleared, for a backward whose aux kernel adds into
+        them in front of the colour backward (which is then told the rows are prezeroed): the rows the forward zeroed if they
+        are still clean, else a fresh zeroed buffer and the flags (a view of the geom scratch) zeroed here."""
+        rows, clean = self.take_rows(dev)
+        if not clean and self.P > 0:
+            rows.zero_()
+            off = self.views().grad_support - self.geom.data_ptr()
+            self.geom[off:off + (self.P + 15) // 16 * 16].zero_()     # the 16-byte units the support compaction reads
+        return rows
 
     def views(self):
         L = _lib.lib()
@@ -140,8 +151,21 @@ class RasterState:
         return out
 
 
-def _forward_render(L, fr, st, color, depth, stream, prepare_backward, dev):
+def _forward_render(L, fr, st, color, depth, stream, prepare_backward, dev, aux=False):
     st.grad_rows, st.rows_clean = None, False
+    st.expected_depth = st.alpha = None
+    if aux:
+        # the same render kernel also writes sum z alpha T and 1 - T_final (its AUX instantiation): no second render
+        st.expected_depth = torch.empty(1, st.H, st.W, dtype=torch.float32, device=dev)
+        st.alpha = torch.empty(1, st.H, st.W, dtype=torch.float32, device=dev)
+        if prepare_backward and st.P > 0:
+            st.grad_rows = torch.empty(st.P, 16, dtype=torch.float32, device=dev)
+        _lib.check(L.mvi_raster_forward_render_aux(C.byref(fr.c), st.P, st.D, _ptr(st.radii), _ptr(st.geom), st.geom.numel(),
+                                                   _ptr(st.binning), st.binning.numel(), _ptr(st.image), st.image.numel(),
+                                                   _ptr(color), _ptr(depth), _ptr(st.grad_rows), _ptr(st.expected_depth),
+                                                   _ptr(st.alpha), stream), "rasterize forward (render, aux)")
+        st.rows_clean = st.grad_rows is not None
+        return
     if prepare_backward and st.P > 0:
         st.grad_rows = torch.empty(st.P, 16, dtype=torch.float32, device=dev)
         _lib.check(L.mvi_raster_forward_render_prepare(C.byref(fr.c), st.P, st.D, _ptr(st.radii), _ptr(st.geom), st.geom.numel(),
@@ -156,9 +180,12 @@ def _forward_render(L, fr, st, color, depth, stream, prepare_backward, dev):
 
 
 def rasterize_forward(rs: GaussianRasterizationSettings, means3D, opacities, shs=None, colors_precomp=None,
-                      scales=None, rotations=None, cov3D_precomp=None, prepare_backward=False):
+                      scales=None, rotations=None, cov3D_precomp=None, prepare_backward=False, aux=False):
     """Runs the HIP forward. Returns (color [3,H,W], radii [P] int32, depth [1,H,W], RasterState). prepare_backward: a
-    backward will follow — its accumulation rows (64 B per Gaussian) are allocated now and zeroed inside the render kernel."""
+    backward will follow — its accumulation rows (64 B per Gaussian) are allocated now and zeroed inside the render kernel.
+    aux: the state also carries `expected_depth` [1,H,W] = sum z alpha T (unnormalised; divide by alpha for the normalised
+    depth) and `alpha` [1,H,W] = 1 - T_final, written by the same render kernel; their upstream gradients go to
+    rasterize_backward(grad_expected_depth=, grad_alpha=)."""
     L = _lib.lib()
     fr = _Frame(rs)
     dev = means3D.device
@@ -186,13 +213,17 @@ def rasterize_forward(rs: GaussianRasterizationSettings, means3D, opacities, shs
                    "rasterize forward (geom)")
         st.D = int(D.value)
         st.binning = torch.empty(L.mvi_raster_binning_bytes(st.D, W, H) if st.D else 0, **u8)
-        _forward_render(L, fr, st, color, depth, stream, prepare_backward, dev)
+        _forward_render(L, fr, st, color, depth, stream, prepare_backward, dev, aux)
     return color, st.radii, depth, st
 
 
 def rasterize_backward(rs: GaussianRasterizationSettings, st: RasterState, grad_color, means3D, shs=None,
-                       colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, out=None, sh_grad="dense"):
+                       colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, out=None, sh_grad="dense",
+                       grad_expected_depth=None, grad_alpha=None):
     """Runs the HIP backward. Returns dict of gradients (None for inputs that were not given).
+    grad_expected_depth / grad_alpha [1,H,W]: upstream gradients of the aux outputs of a forward with aux=True (None = zero).
+    Their share is added into the accumulation rows by mvi_raster_backward_render_aux in front of the colour backward, the
+    per-Gaussian chain rule then sees the sum, and the depth gradient reaches means3D through z = [m,1].V[:,2].
     `out` may hold preallocated contiguous fp32 tensors (e.g. dist.GradBucket.views) to write into.
     sh_grad (SH input only): "dense" -> g["shs"] [P,M,3]; "factor" -> g["sh_color_factor"] [P,3] instead, the
     colour factor of the rank-1 SH gradient (see sh_backward_views; view-parallel training exchanges this);
@@ -227,24 +258,65 @@ def rasterize_backward(rs: GaussianRasterizationSettings, st: RasterState, grad_
         g["cov3D_precomp"] = buf("cov3D_precomp", P, 6)
     else:
         g["scales"], g["rotations"] = buf("scales", P, 3), buf("rotations", P, 4)
-    scratch, clean = st.take_rows(dev)               # 64-byte accumulation row per Gaussian
+    gd, ga = _aux_grads(st, grad_expected_depth, grad_alpha)
+    if gd is None and ga is None:
+        scratch, clean = st.take_rows(dev)           # 64-byte accumulation row per Gaussian
+    else:
+        scratch, clean = st.take_zeroed_rows(dev), 1
     grad_color = grad_color.to(torch.float32).contiguous()
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
+        _backward_aux_render(L, fr, st, gd, ga, scratch, stream)
         _lib.check(L.mvi_raster_backward(
             C.byref(fr.c), P, st.M, st.D, _ptr(means3D), _ptr(shs), _ptr(colors_precomp), _ptr(scales), _ptr(rotations),
             _ptr(cov3D_precomp), _ptr(st.radii), _ptr(st.geom), _ptr(st.binning), _ptr(st.image), _ptr(grad_color),
             _ptr(g["means3D"]), _ptr(g["means2D"]), _ptr(g["opacities"]), _ptr(g["shs"]), _ptr(dcolors),
             _ptr(g["scales"]), _ptr(g["rotations"]), _ptr(g["cov3D_precomp"]), _ptr(scratch), clean, stream),
             "rasterize backward")
+        _backward_depth_to_means(L, fr, st, gd, scratch, g["means3D"], stream)
     return g
 
 
+def _aux_grads(st, grad_expected_depth, grad_alpha):
+    """The two aux image gradients as contiguous fp32 [1,H,W] (None stays None = zero)."""
+    def one(t, what):
+        if t is None:
+            return None
+        if t.numel() != st.H * st.W:
+            raise ValueError(f"{what} must have {st.H} x {st.W} elements, got {tuple(t.shape)}")
+        return t.detach().to(torch.float32).contiguous()
+    return one(grad_expected_depth, "grad_expected_depth"), one(grad_alpha, "grad_alpha")
+
+
+def _backward_aux_render(L, fr, st, gd, ga, rows, stream):
+    """Adds the aux outputs' share into the (zeroed) accumulation rows; nothing to do when both gradients are None."""
+    if (gd is None and ga is None) or st.P == 0:
+        return
+    _lib.check(L.mvi_raster_backward_render_aux(C.byref(fr.c), st.P, st.D, _ptr(st.radii), _ptr(st.geom), _ptr(st.binning),
+                                                _ptr(st.image), _ptr(gd), _ptr(ga), _ptr(rows), stream),
+               "rasterize backward (render, aux)")
+
+
+def _backward_depth_to_means(L, fr, st, gd, rows, dmeans3D, stream):
+    """dL/dz (slot 9 of the rows) into the position gradient the chain rule has just written; only a depth gradient fills it."""
+    if gd is None or st.P == 0:
+        return
+    _lib.check(L.mvi_raster_backward_depth_to_means(C.byref(fr.c), st.P, _ptr(rows), _ptr(dmeans3D), stream),
+               "rasterize backward (depth to means)")
+
+
+def _no_aux(what, grad_expected_depth, grad_alpha):
+    if grad_expected_depth is not None or grad_alpha is not None:
+        raise NotImplementedError(f"{what} does not take grad_expected_depth / grad_alpha: the aux outputs are differentiated "
+                                  "by rasterize_backward and rasterize_backward_raw (dense SH gradient) only")
+
+
 def rasterize_backward_split(rs: GaussianRasterizationSettings, st: RasterState, grad_color, means3D, shs, scales, rotations,
-                             out, after_render=None):
+                             out, after_render=None, grad_expected_depth=None, grad_alpha=None):
     """rasterize_backward(..., sh_grad="factor") in two halves: after the render backward the colour factors are already
     in out["sh_color_factor"] and `after_render()` runs (dist.FactoredGradExchange starts its all-gather there), then the
     per-Gaussian chain rule fills the other gradients. Same kernels and results as the one-call form."""
+    _no_aux("rasterize_backward_split", grad_expected_depth, grad_alpha)
     L = _lib.lib()
     fr = _Frame(rs)
     dev = means3D.device
@@ -275,12 +347,13 @@ def rasterize_backward_split(rs: GaussianRasterizationSettings, st: RasterState,
 
 
 def rasterize_backward_ranged(rs: GaussianRasterizationSettings, st: RasterState, grad_color, means3D, shs, scales, rotations,
-                              exchange, means2D_out=None):
+                              exchange, means2D_out=None, grad_expected_depth=None, grad_alpha=None):
     """Backward of one view for view-parallel training with the exchange overlapped range by range
     (dist.RangedGradExchange): render backward -> the colour factors' all-gather starts -> for every Gaussian range the
     chain rule (mvi_raster_backward_geom_range) writes straight into the exchange buffer and that range's all-reduce starts
     behind it -> exchange.finish() waits and rebuilds dL/dSH. Returns the summed gradients {means3D, shs, opacities,
     scales, rotations} and this view's dL/dmeans2D [P, 3] (a per-view densification statistic: not exchanged)."""
+    _no_aux("rasterize_backward_ranged", grad_expected_depth, grad_alpha)
     L = _lib.lib()
     fr = _Frame(rs)
     dev = means3D.device
@@ -350,9 +423,9 @@ def sh_backward_views(means3D, campos, color_factors, M, sh_degree, out=None):
 
 
 def rasterize_forward_raw(rs: GaussianRasterizationSettings, xyz, features_dc, features_rest, raw_opacity, raw_scaling,
-                          raw_rotation, prepare_backward=False):
+                          raw_rotation, prepare_backward=False, aux=False):
     """HIP forward fed with the GaussianModel's un-activated parameters (gaussian_model.py:95-115 happens in the
-    kernels). Returns (color, radii, depth, RasterState) like rasterize_forward."""
+    kernels). Returns (color, radii, depth, RasterState) like rasterize_forward (aux: as there)."""
     L = _lib.lib()
     fr = _Frame(rs)
     dev = xyz.device
@@ -382,19 +455,23 @@ def rasterize_forward_raw(rs: GaussianRasterizationSettings, xyz, features_dc, f
                    "rasterize forward raw (geom)")
         st.D = int(D.value)
         st.binning = torch.empty(L.mvi_raster_binning_bytes(st.D, W, H) if st.D else 0, **u8)
-        _forward_render(L, fr, st, color, depth, stream, prepare_backward, dev)
+        _forward_render(L, fr, st, color, depth, stream, prepare_backward, dev, aux)
     return color, st.radii, depth, st
 
 
 def rasterize_backward_raw(rs: GaussianRasterizationSettings, st: RasterState, grad_color, xyz, features_dc, features_rest,
-                           raw_opacity, raw_scaling, raw_rotation, out=None, sh_grad="dense"):
+                           raw_opacity, raw_scaling, raw_rotation, out=None, sh_grad="dense", grad_expected_depth=None,
+                           grad_alpha=None):
     """HIP backward with respect to the raw parameters. Returns dict(xyz, means2D, features_dc, features_rest,
     opacity, scaling, rotation). `out` may hold preallocated contiguous fp32 tensors to write into (same keys).
     sh_grad="factor" (view-parallel training, train_views.py): dict(xyz, means2D, opacity, scaling, rotation,
     sh_color_factor [P,3]) — the SH gradient stays in the factored form the exchange moves (dist.FactoredGradExchange) and
-    features_dc / features_rest are None (mvi_raster_backward_raw_factor)."""
+    features_dc / features_rest are None (mvi_raster_backward_raw_factor).
+    grad_expected_depth / grad_alpha: as in rasterize_backward (dense form only); the depth gradient goes to xyz."""
     if sh_grad not in ("dense", "factor"):
         raise ValueError(f"sh_grad must be 'dense' or 'factor', got {sh_grad!r}")
+    if sh_grad == "factor":
+        _no_aux("rasterize_backward_raw(sh_grad='factor')", grad_expected_depth, grad_alpha)
     L = _lib.lib()
     fr = _Frame(rs)
     dev, P, M = xyz.device, st.P, st.M
@@ -410,7 +487,11 @@ def rasterize_backward_raw(rs: GaussianRasterizationSettings, st: RasterState, g
         return t
     g = dict(xyz=buf("xyz", P, 3), means2D=buf("means2D", P, 3), opacity=buf("opacity", P, 1), features_dc=None, features_rest=None,
              scaling=buf("scaling", P, 3), rotation=buf("rotation", P, 4))
-    scratch, clean = st.take_rows(dev)
+    gd, ga = _aux_grads(st, grad_expected_depth, grad_alpha)
+    if gd is None and ga is None:
+        scratch, clean = st.take_rows(dev)
+    else:
+        scratch, clean = st.take_zeroed_rows(dev), 1
     grad_color = grad_color.to(torch.float32).contiguous()
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
@@ -423,11 +504,13 @@ def rasterize_backward_raw(rs: GaussianRasterizationSettings, st: RasterState, g
                 _ptr(g["scaling"]), _ptr(g["rotation"]), _ptr(scratch), clean, stream), "rasterize backward raw (factor)")
             return g
         g["features_dc"], g["features_rest"] = buf("features_dc", P, 1, 3), buf("features_rest", P, M - 1, 3)
+        _backward_aux_render(L, fr, st, gd, ga, scratch, stream)
         _lib.check(L.mvi_raster_backward_raw(
             C.byref(fr.c), P, M, st.D, _ptr(xyz), _ptr(features_dc), _ptr(features_rest), _ptr(raw_opacity), _ptr(raw_scaling),
             _ptr(raw_rotation), _ptr(st.radii), _ptr(st.geom), _ptr(st.binning), _ptr(st.image), _ptr(grad_color),
             _ptr(g["xyz"]), _ptr(g["means2D"]), _ptr(g["opacity"]), _ptr(g["features_dc"]), _ptr(g["features_rest"]),
             _ptr(g["scaling"]), _ptr(g["rotation"]), _ptr(scratch), clean, stream), "rasterize backward raw")
+        _backward_depth_to_means(L, fr, st, gd, scratch, g["xyz"], stream)
     return g
 
 
@@ -486,6 +569,69 @@ class _Rasterize(torch.autograd.Function):
                 g["rotations"], g["cov3D_precomp"], None)
 
 
+class RasterAuxOutput(NamedTuple):
+    """What GaussianRasterizer.forward_aux / forward_raw_aux return. color, radii and depth (the median depth, not
+    differentiable) are those of forward / forward_raw bit for bit; expected_depth = sum z alpha T (unnormalised: divide by
+    alpha for the normalised depth) and alpha = 1 - T_final are differentiable."""
+    color: torch.Tensor
+    radii: torch.Tensor
+    depth: torch.Tensor
+    expected_depth: torch.Tensor
+    alpha: torch.Tensor
+
+
+class _RasterizeAux(torch.autograd.Function):
+    """_Rasterize with the two aux outputs; the backward takes all three image gradients."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, rs):
+        a = dict(means3D=_opt(means3D), shs=_opt(shs), colors_precomp=_opt(colors_precomp), opacities=_opt(opacities),
+                 scales=_opt(scales), rotations=_opt(rotations), cov3D_precomp=_opt(cov3D_precomp))
+        if a["means3D"] is None:
+            a["means3D"] = means3D.to(torch.float32).reshape(0, 3)
+        color, radii, depth, st = rasterize_forward(rs, a["means3D"], a["opacities"], a["shs"], a["colors_precomp"],
+                                                    a["scales"], a["rotations"], a["cov3D_precomp"],
+                                                    prepare_backward=any(ctx.needs_input_grad[:8]), aux=True)
+        ctx.rs, ctx.st, ctx.a = rs, st, a
+        ctx.mark_non_differentiable(radii, depth)
+        return color, radii, depth, st.expected_depth, st.alpha
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, _grad_depth, grad_expected_depth, grad_alpha):
+        a, st = ctx.a, ctx.st
+        if st.P == 0:
+            z = lambda t: None if t is None else torch.zeros_like(t)
+            return (z(a["means3D"]), None, z(a["shs"]), z(a["colors_precomp"]), z(a["opacities"]), z(a["scales"]),
+                    z(a["rotations"]), z(a["cov3D_precomp"]), None)
+        g = rasterize_backward(ctx.rs, st, grad_color, a["means3D"], a["shs"], a["colors_precomp"], a["scales"],
+                               a["rotations"], a["cov3D_precomp"], grad_expected_depth=grad_expected_depth,
+                               grad_alpha=grad_alpha)
+        return (g["means3D"], g["means2D"], g["shs"], g["colors_precomp"], g["opacities"], g["scales"],
+                g["rotations"], g["cov3D_precomp"], None)
+
+
+class _RasterizeRawAux(torch.autograd.Function):
+    """_RasterizeRaw with the two aux outputs; the backward takes all three image gradients."""
+
+    @staticmethod
+    def forward(ctx, xyz, means2D, features_dc, features_rest, raw_opacity, raw_scaling, raw_rotation, rs):
+        a = [t.detach().to(torch.float32).contiguous() for t in (xyz, features_dc, features_rest, raw_opacity, raw_scaling,
+                                                                  raw_rotation)]
+        color, radii, depth, st = rasterize_forward_raw(rs, *a, prepare_backward=any(ctx.needs_input_grad[:7]), aux=True)
+        ctx.rs, ctx.st, ctx.a = rs, st, a
+        ctx.mark_non_differentiable(radii, depth)
+        return color, radii, depth, st.expected_depth, st.alpha
+
+    @staticmethod
+    def backward(ctx, grad_color, _gr, _gd, grad_expected_depth, grad_alpha):
+        st = ctx.st
+        if st.P == 0:
+            return tuple(torch.zeros_like(t) for t in (ctx.a[0], ctx.a[0], *ctx.a[1:])) + (None,)
+        g = rasterize_backward_raw(ctx.rs, st, grad_color, *ctx.a, grad_expected_depth=grad_expected_depth, grad_alpha=grad_alpha)
+        return (g["xyz"], g["means2D"], g["features_dc"], g["features_rest"], g["opacity"].view_as(ctx.a[3]), g["scaling"],
+                g["rotation"], None)
+
+
 class GaussianRasterizer(torch.nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
@@ -510,6 +656,27 @@ class GaussianRasterizer(torch.nn.Module):
         preprocess kernels. Returns (color, radii, depth); gradients flow to the raw parameters and to means2D."""
         return _RasterizeRaw.apply(xyz, means2D, features_dc, features_rest, raw_opacity, raw_scaling, raw_rotation,
                                    self.raster_settings)
+
+    def forward_raw_aux(self, xyz, means2D, features_dc, features_rest, raw_opacity, raw_scaling, raw_rotation):
+        """forward_raw with the differentiable expected depth and alpha: returns RasterAuxOutput(color, radii, depth,
+        expected_depth, alpha); gradients of all three images flow to the raw parameters and to means2D."""
+        return RasterAuxOutput(*_RasterizeRawAux.apply(xyz, means2D, features_dc, features_rest, raw_opacity, raw_scaling,
+                                                       raw_rotation, self.raster_settings))
+
+    def forward_aux(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                    cov3D_precomp=None):
+        """forward with the differentiable expected depth and alpha (same arguments, same errors): returns
+        RasterAuxOutput(color, radii, depth, expected_depth, alpha) from ONE render — same geometry, sort and binning."""
+        if (shs is None) == (colors_precomp is None):
+            raise Exception("Please provide excatly one of either SHs or precomputed colors!")
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+            raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        empty = torch.empty(0, dtype=torch.float32, device=means3D.device)
+        return RasterAuxOutput(*_RasterizeAux.apply(
+            means3D, means2D, empty if shs is None else shs, empty if colors_precomp is None else colors_precomp, opacities,
+            empty if scales is None else scales, empty if rotations is None else rotations,
+            empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings))
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None):
