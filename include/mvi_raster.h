@@ -243,6 +243,12 @@ typedef struct mvi_raster_views {
     const uint8_t* grad_support;  /* [P] valid after a backward: 1 = the render backward added to this Gaussian's accumulation
                                    * row; 0 = every gradient of the Gaussian is exactly zero in this view (occluded, culled or
                                    * outside the image). View-parallel training exchanges only rows in the union of the supports. */
+    const uint32_t* tile_class_count; /* [8,16] tiles per (XCD band, work class), written by the render forward: tile t is in band
+                                   * x iff it lies in the x-th of eight contiguous runs of the tiles (sizes tiles / 8, the first
+                                   * tiles % 8 runs one longer), and its class is min(15, largest n_contrib of its pixels / 32) */
+    const uint32_t* tile_class_queue; /* [8,16,(tiles + 7) / 8 + 1] the tile indices of each (band, class) in the order the
+                                   * forward's blocks finished; entries behind tile_class_count[band][class] are unwritten.
+                                   * Read by the render backward under mvi_raster_backward_order(1) */
 } mvi_raster_views;
 int mvi_raster_get_views(int32_t P, int64_t num_rendered, int32_t image_width, int32_t image_height,
                          const void* geom, const void* binning, const void* image,
@@ -287,6 +293,15 @@ int mvi_raster_color_mode(int deferred);
  * 0 for the default, -1 to query; returns the previous selection, or MVI_EINVAL (nothing changed) for a size that is not
  * built. Not thread-safe. */
 int mvi_raster_forward_group(int group);
+/* Tile order of the render backward. Workgroups start in id order and a tile's backward costs its largest n_contrib, so each
+ * XCD band can hand out its tiles heaviest first: 1 = the i-th workgroup of a band takes the i-th tile of the band's class
+ * queues (mvi_raster_views.tile_class_queue, which every render forward fills) read from class 15 down; 0 = plain tile order
+ * inside the band (MVI_RASTER_BACKWARD_ORDER=0 | 1 selects at start-up). The tiles of a band, and with them the L2 in which a
+ * Gaussian's gradient atomics meet, are the same in both; only the order of the float atomics changes, as it does from run to
+ * run. Order 1 is used only for an image scratch whose queues a forward of this process filled (the library remembers the
+ * last 64 scratches by address and size); any other state runs in the plain order. Pass 0 or 1 to select, -1 to query;
+ * returns the previous selection, or MVI_EINVAL (nothing changed) for any other value. Not thread-safe. */
+int mvi_raster_backward_order(int order);
 /* Evaluates every colour still pending after a deferred forward (no-op after an eager one), so that mvi_raster_views.rgbd /
  * clamped are complete: for the parity tests and for callers that inspect colours of Gaussians that were never composited.
  * Needs the means3D / shs arrays of the forward still valid. */

@@ -32,7 +32,9 @@ class RasterViews(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "depths", "means2D", "cov3D_a", "cov3D_b", "conic_opacity", "rgbd", "tiles_touched", "clamped",
         "tile_ids_sorted", "point_list", "ranges", "final_T", "n_contrib")] + [("tile_id_bytes", C.c_int32),
-                                                                                   ("grad_support", C.c_void_p)]
+                                                                                   ("grad_support", C.c_void_p),
+                                                                                   ("tile_class_count", C.c_void_p),
+                                                                                   ("tile_class_queue", C.c_void_p)]
 
 
 class AdamGroup(C.Structure):
@@ -147,6 +149,8 @@ def lib():
     L.mvi_raster_color_mode.argtypes = [C.c_int]
     L.mvi_raster_forward_group.restype = C.c_int
     L.mvi_raster_forward_group.argtypes = [C.c_int]
+    L.mvi_raster_backward_order.restype = C.c_int
+    L.mvi_raster_backward_order.argtypes = [C.c_int]
     L.mvi_raster_resolve_colors.restype = C.c_int
     L.mvi_raster_resolve_colors.argtypes = [C.POINTER(RasterSettings), i32, vp, sz, vp]
     L.mvi_raster_dev_stamps.restype = C.c_int

@@ -140,6 +140,10 @@ int mvi_raster_forward_group(int group) {
     const int old = mvi::set_forward_group(group);
     return old < 0 ? fail(MVI_EINVAL, "forward group: no such instantiation of render_forward%s") : old;
 }
+int mvi_raster_backward_order(int order) {
+    const int old = mvi::set_backward_order(order);
+    return old < 0 ? fail(MVI_EINVAL, "backward order: 1 (heaviest first), 0 (plain band order) or -1 (query)%s") : old;
+}
 int mvi_raster_color_mode(int deferred) {
     const int old = g_defer_colors;
     if (deferred == 0 || deferred == 1) g_defer_colors = deferred;
@@ -608,6 +612,7 @@ int mvi_raster_get_views(int32_t P, int64_t D, int32_t W, int32_t H, const void*
     if (image) {
         mvi::ImageView im = mvi::carve_image(const_cast<void*>(image), W, H);
         out->ranges = im.ranges; out->final_T = im.final_T; out->n_contrib = im.n_contrib;
+        out->tile_class_count = im.class_count; out->tile_class_queue = im.class_queue;
     }
     return MVI_OK;
 }

@@ -433,8 +433,7 @@ static int binning_typed(const Frame& f, GeomView g, BinningView b, ImageView im
 // Tile ids travel as 16-bit words whenever the image has at most 65536 tiles (any image up to 4096 x 4096): a pair is then
 // 6 bytes instead of 8 in every pass of emission, partition and range finding (36 instead of 52 bytes per pair in all).
 int launch_binning(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, hipStream_t st) {
-    size_t tiles = (size_t)f.gx * f.gy;
-    if (launch_zero_fill(im.ranges, 8 * tiles, st)) return MVI_EHIP;
+    if (launch_zero_fill(im.ranges, ranges_and_counts_bytes(im), st)) return MVI_EHIP;     // the ranges and the tile class counts behind them
     if (D <= 0 || f.P <= 0) return 0;
     return b.key_bytes == 2 ? binning_typed<uint16_t>(f, g, b, im, D, st) : binning_typed<uint32_t>(f, g, b, im, D, st);
 }

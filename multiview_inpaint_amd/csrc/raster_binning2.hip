@@ -430,11 +430,15 @@ __global__ __launch_bounds__(kExThreads) void row_count_kernel(int gx, int gy, c
 // starts inside the row (col_rel[y][x], col_rel[y][gx] = row total): the tile ranges.
 __global__ __launch_bounds__(1024) void row_scan_kernel(int gx, const uint32_t* __restrict__ chunk_first,
                                                         uint32_t* __restrict__ row_table, int stride,
-                                                        uint32_t* __restrict__ row_tot, uint32_t* __restrict__ col_rel) {
+                                                        uint32_t* __restrict__ row_tot, uint32_t* __restrict__ col_rel,
+                                                        uint32_t* __restrict__ class_count) {
     __shared__ uint32_t s_first[257];
     __shared__ uint32_t s_wave[16];
     __shared__ uint32_t s_carry;
     const int tid = threadIdx.x;
+    // the render kernel's tile class counts (raster_common.h, ImageView) start every forward at zero: this kernel runs in
+    // front of it whenever there are pairs, so no launch is spent on 512 bytes
+    if (blockIdx.x == 0 && tid < kTileBands * kTileClasses) class_count[tid] = 0u;
     if (tid <= gx) s_first[tid] = chunk_first[tid];      // read behind the scan: its opening barrier serves
     const int n = (int)chunk_first[gx];
     uint32_t* row = row_table + (size_t)blockIdx.x * stride;
@@ -714,8 +718,7 @@ int launch_binning2_level1(const Frame& f, GeomView g, hipStream_t st) {
 // NOT written: the ranges come out of the row scan and no kernel reads the ids (2 bytes per pair, a third of pass 2's traffic);
 // launch_tile_ids_from_ranges (raster_binning.hip) derives them from the ranges for whoever asks (the parity tests).
 int launch_binning2(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, int64_t segments, hipStream_t st) {
-    const size_t tiles = (size_t)f.gx * f.gy;
-    if (D <= 0 || f.P <= 0) return launch_zero_fill(im.ranges, 8 * tiles, st);
+    if (D <= 0 || f.P <= 0) return launch_zero_fill(im.ranges, ranges_and_counts_bytes(im), st);    // with the tile class counts
     const bool wide = f.gx > 128 || f.gy > 128;
     ExpandArgs a1{};
     a1.n_items = f.P; a1.nbins = f.gx; a1.gx = f.gx;
@@ -744,7 +747,7 @@ int launch_binning2(const Frame& f, GeomView g, BinningView b, ImageView im, int
     hipLaunchKernelGGL(row_count_kernel, dim3(nchunk), dim3(kExThreads), 0, st, f.gx, f.gy, g.chunk_first, g.col_start,
                        (const uint16_t*)b.keys[0], b.block_hist, b.nsort);
     hipLaunchKernelGGL(row_scan_kernel, dim3(f.gy), dim3(1024), 0, st, f.gx, g.chunk_first, b.block_hist, b.nsort,
-                       b.digit_tot, b.col_rel);
+                       b.digit_tot, b.col_rel, im.class_count);
     // bins = tile rows: up to 80 rows the small instantiation (~50 KB of LDS, three blocks per CU instead of two)
     if (f.gy <= kEx2SmallNB)
         hipLaunchKernelGGL((expand_scatter_kernel<2, kEx2SmallNB, kEx2Items, kEx2SmallCap>), dim3(nchunk), dim3(kExThreads), 0,

@@ -68,6 +68,7 @@ bool binning_v2_enabled();                          // false when MVI_BINNING_LE
 void set_dev_stamps(int pass, void* buf);            // diagnostics: shader-clock stamps of the partition kernel's phases
 int set_binning_version(int v);                     // 1 | 2 (anything else: query only); returns the previous version
 int set_forward_group(int g);                       // render_forward's strip-walk group: a built size | 0 = default | -1 = query
+int set_backward_order(int order);                  // render_backward's tile order: 1 heaviest first | 0 plain band order | -1 = query
 inline bool binning_v2_ok(int gx, int gy) { return gx <= 256 && gy <= 256 && binning_v2_enabled(); }
 
 // Deferred SH colours. With SH input the forward preprocess does NOT evaluate SH -> RGB for every visible Gaussian (192 bytes
@@ -128,10 +129,22 @@ struct GeomView {
     int nsortP;
     size_t bytes;
 };
+// Work classes of the tiles, recorded by render_forward for render_backward's dispatch order (raster_render.hip): a tile's
+// class is min(kTileClasses - 1, largest n_contrib of its pixels / kTileClassWidth), and every XCD band (xcd_band_tile) keeps
+// one queue of tile indices per class.
+constexpr int kTileBands = 8;
+constexpr int kTileClasses = 16;
+constexpr int kTileClassWidth = 32;
+// The kernels take ONE pointer (the render forward has no scalar register to spare): the queues lie directly behind the counts,
+// and a queue's length follows from the number of tiles.
+__host__ __device__ inline int tile_queue_stride(int tiles) { return (tiles + kTileBands - 1) / kTileBands + 1; }   // >= any band's size
+template <typename T> __host__ __device__ inline T* tile_class_queues(T* class_count) { return class_count + kTileBands * kTileClasses; }
 struct ImageView {
-    uint32_t* ranges;     // [2*tiles]
-    float* final_T;       // [H*W]
-    uint32_t* n_contrib;  // [H*W]
+    uint32_t* ranges;       // [2*tiles]
+    uint32_t* class_count;  // [kTileBands][kTileClasses] tiles per (band, class); directly behind `ranges`, zeroed with them
+    uint32_t* class_queue;  // [kTileBands][kTileClasses][tile_queue_stride(tiles)] tile indices in arrival order; = tile_class_queues(class_count)
+    float* final_T;         // [H*W]
+    uint32_t* n_contrib;    // [H*W]
     size_t bytes;
 };
 struct BinningView {
@@ -209,10 +222,17 @@ inline ImageView carve_image(void* base, int W, int H) {
     size_t px = (size_t)W * H;
     auto take = [&](size_t b) { char* r = p ? p + o : nullptr; o += align256(b); return r; };
     v.ranges = (uint32_t*)take(8 * (tiles ? tiles : 1));
+    v.class_count = (uint32_t*)take(4 * kTileBands * kTileClasses);        // a multiple of 256 bytes: the queues follow directly
+    v.class_queue = (uint32_t*)take(4 * (size_t)kTileBands * kTileClasses * (size_t)tile_queue_stride((int)tiles));
     v.final_T = (float*)take(4 * (px ? px : 1));
     v.n_contrib = (uint32_t*)take(4 * (px ? px : 1));
     v.bytes = o;
     return v;
+}
+// bytes from the start of `ranges` to the end of `class_count`: what the binning zeroes in front of the render kernel where it
+// zero-fills the ranges (binning version 2 with pairs writes every range itself: its row scan zeroes the counts)
+inline size_t ranges_and_counts_bytes(const ImageView& v) {
+    return (size_t)((char*)v.class_count - (char*)v.ranges) + 4 * (size_t)kTileBands * kTileClasses;
 }
 inline int tile_bits(int W, int H) {
     unsigned tiles = (unsigned)(((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile));
@@ -478,6 +498,21 @@ __device__ __forceinline__ float row_sum_to_lane15(float v) {
     v = dpp_add<0x114, 0xf>(v);   // row_shr:4
     v = dpp_add<0x118, 0xf>(v);   // row_shr:8
     return v;
+}
+// Largest value over the 64 lanes: the four row steps of row_sum_to_lane15 (a lane that a step leaves out reads 0, the identity
+// of an unsigned maximum as of a sum), then the four row results meet on the scalar unit. The result is wave-uniform.
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_umax(uint32_t v) {
+    return max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ uint32_t wave_umax(uint32_t v) {
+    v = dpp_umax<0xb1>(v);    // quad_perm [1,0,3,2]
+    v = dpp_umax<0x4e>(v);    // quad_perm [2,3,0,1]
+    v = dpp_umax<0x114>(v);   // row_shr:4
+    v = dpp_umax<0x118>(v);   // row_shr:8
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 15), b = (uint32_t)__builtin_amdgcn_readlane((int)v, 31);
+    const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)v, 47), d = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+    return max(max(a, b), max(c, d));
 }
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

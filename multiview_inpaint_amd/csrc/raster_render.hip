@@ -10,6 +10,7 @@
 // quadratic form over the box, quad_overlap). Only kept entries are evaluated per pixel. The test is conservative
 // (margin on 2 ln(255 o)), so results are identical to evaluating every entry.
 #include <cstdlib>
+#include <mutex>
 
 #include "raster_common.h"
 #include "raster_render_shared.h"
@@ -40,7 +41,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G == 1 ?
     const float2* __restrict__ xy, float4* rgbd, const float4* __restrict__ conic_opacity,
     float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color,
     float* __restrict__ out_depth, ZeroRegions zero, const ColorSource* __restrict__ color_src, uint8_t* clamped,
-    float* __restrict__ out_expected_depth, float* __restrict__ out_alpha) {
+    float* __restrict__ out_expected_depth, float* __restrict__ out_alpha, uint32_t* __restrict__ class_count) {
+    __shared__ uint32_t s_wmax[4];
     __shared__ float2 s_xy[kBlock];
     __shared__ float s_t2[kBlock];
     __shared__ float4 s_co[kBlock];
@@ -181,6 +183,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G == 1 ?
             }
         }
     }
+    // The tile's work class for the backward's dispatch order: the backward replays the list up to the largest n_contrib of
+    // the tile, which only this kernel knows. One lane appends the tile to the queue of its class in its XCD band (the band
+    // of xcd_band_tile is blockIdx.x & 7, here and in the backward); the counts start at zero (ranges_and_counts_bytes).
+    // A pixel outside the image has last = 0. The barrier and the counter's atomic come BEFORE the image stores, the queue
+    // store behind them: the barrier then has no stores to drain, and the atomic's round trip runs beside the stores' own.
+    const uint32_t wmax = wave_umax(last);          // wave-uniform, on the scalar side
+    if (lane == 0) s_wmax[wave] = wmax;
+    __syncthreads();
+    uint32_t cls = 0, slot = 0;
+    if (tid == 0) {
+        const uint32_t m = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+        cls = (blockIdx.x & (kTileBands - 1)) * kTileClasses + min((uint32_t)(kTileClasses - 1), m / kTileClassWidth);
+        slot = atomicAdd(&class_count[cls], 1u);
+    }
     if (inside) {
         size_t pix = (size_t)pyi * f.W + pxi, hw = (size_t)f.H * f.W;
         final_T[pix] = T_out;
@@ -193,6 +209,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G == 1 ?
             out_expected_depth[pix] = Dexp;
             out_alpha[pix] = 1.0f - T_out;
         }
+    }
+    if (tid == 0) {
+        const uint32_t stride = (uint32_t)tile_queue_stride(f.gx * f.gy);
+        if (slot < stride) tile_class_queues(class_count)[(size_t)cls * stride + slot] = (uint32_t)tile;   // always, from zeroed counts
     }
 }
 
@@ -265,6 +285,46 @@ int set_forward_group(int g) {
     return old;
 }
 
+// Tile order of the render backward (mvi_raster_backward_order): 1 = every XCD band hands out its tiles heaviest class first,
+// from the queues the forward filled; 0 = plain tile order inside the band (xcd_band_tile). 1 is the default: on the bench view
+// (8160 tiles, 3.2 per resident block slot) it took render_backward_kernel from 364 to 338 us and the step from 0.845 to 0.816 ms,
+// every repetition below every one of the parent's, for 3 us more in render_forward (profiles/render_backward_order_ab.txt).
+constexpr int kBackwardOrderDefault = 1;
+static int g_backward_order = [] { const char* e = getenv("MVI_RASTER_BACKWARD_ORDER");
+                                   return e && (e[0] == '0' || e[0] == '1') && e[1] == 0 ? e[0] - '0' : kBackwardOrderDefault; }();
+int set_backward_order(int order) {
+    const int old = g_backward_order;
+    if (order == -1) return old;
+    if (order != 0 && order != 1) return MVI_EINVAL;
+    g_backward_order = order;
+    return old;
+}
+// Which image scratches hold class queues that a render_forward of this process filled, PER IMAGE SCRATCH and by size (the
+// pattern of raster_api.hip's SegmentHint): an entry describes the scratch's contents. Unknown scratch (never rendered into
+// here, copied elsewhere, or evicted): the backward takes the plain order, which needs nothing from the forward.
+namespace {
+struct QueueNote { const void* image; int W, H; uint64_t stamp; };
+constexpr int kQueueNotes = 64;
+QueueNote g_queue_notes[kQueueNotes] = {};
+uint64_t g_queue_clock = 0;
+std::mutex g_queue_mutex;
+void note_queue_filled(const void* image, int W, int H) {
+    std::lock_guard<std::mutex> lock(g_queue_mutex);
+    int slot = 0;
+    for (int i = 0; i < kQueueNotes; ++i) {
+        if (g_queue_notes[i].image == image) { slot = i; break; }
+        if (g_queue_notes[i].stamp < g_queue_notes[slot].stamp) slot = i;     // else the least recently written
+    }
+    g_queue_notes[slot] = {image, W, H, ++g_queue_clock};
+}
+bool queue_filled(const void* image, int W, int H) {
+    std::lock_guard<std::mutex> lock(g_queue_mutex);
+    for (int i = 0; i < kQueueNotes; ++i)
+        if (g_queue_notes[i].image == image && g_queue_notes[i].stamp) return g_queue_notes[i].W == W && g_queue_notes[i].H == H;
+    return false;
+}
+}  // namespace
+
 int launch_zero_fill(void* p, size_t bytes, hipStream_t st);
 int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D,
                           float* out_color, float* out_depth, hipStream_t st, float* zero_rows, float* out_expected_depth,
@@ -295,7 +355,7 @@ int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView i
 #define MVI_RENDER_FORWARD(G, AUX)                                                                                          \
     hipLaunchKernelGGL((render_forward_kernel<G, AUX>), dim3(blocks), dim3(kBlock), 0, st, f, im.ranges, plist, g.xy, g.rgbd, \
                        g.conic_opacity, im.final_T, im.n_contrib, out_color, out_depth, z, g.color_src, g.clamped,            \
-                       out_expected_depth, out_alpha)
+                       out_expected_depth, out_alpha, im.class_count)
     switch (g_forward_group * 2 + (out_alpha ? 1 : 0)) {
         case 2: MVI_RENDER_FORWARD(1, false); break;
         case 3: MVI_RENDER_FORWARD(1, true); break;
@@ -304,7 +364,9 @@ int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView i
         default: return MVI_EINVAL;                              // a kernel that is not built is an error, never another kernel
     }
 #undef MVI_RENDER_FORWARD
-    return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
+    if (hipGetLastError() != hipSuccess) return MVI_EHIP;
+    note_queue_filled(im.ranges, f.W, f.H);                      // `ranges` is the first byte of the image scratch
+    return 0;
 }
 
 __global__ __launch_bounds__(256) void zero_regions_kernel(ZeroRegions z) { zero_share(z, threadIdx.x, 256); }
@@ -359,16 +421,42 @@ int launch_wave_sum9_probe(const float* in, float* out, int n_waves, hipStream_t
 // operation order as the forward kernel (products rounded, one fma per sum), element-wise.
 // Registers decide the occupancy (LDS: 10.5 KB per block, 12 blocks per CU fit). The entry loop keeps ONE entry in registers,
 // read from LDS at the top of its iteration: 67 VGPRs and no scratch at five waves per SIMD (76 before the moments were factored,
-// at five AND at six). Five is the default:
-// on the MI355X six measured the same kernel time and did not pass the keep rule (profiles/render_backward_six_waves_ab.txt).
+// at five AND at six). MVI_RB_WAVES is the register allocator's target; the kernel now takes 67 VGPRs and no scratch at 5 and at 6.
+// Five is the default. The work recorded as "six waves per SIMD"
+// measured six and kept five (the same kernel time, the keep rule not passed: profiles/render_backward_six_waves_ab.txt), and
+// six measured again on top of the heaviest-first tile order overlaps five in the step and in the kernel
+// (profiles/render_backward_order_ab.txt).
 #ifndef MVI_RB_WAVES
 #define MVI_RB_WAVES 5             // waves per SIMD the register allocation aims at (A/B builds: -DMVI_RB_WAVES=6)
 #endif
+// Tile of workgroup `bid` when the band's tiles are handed out heaviest first: the hardware starts workgroups in id order, a
+// block's work is its tile's largest n_contrib, and in plain tile order the heavy tiles that happen to start in the last of
+// the launch's ~3 rounds run on alone over an emptying GPU. Band x = bid & 7 (the XCD, as in xcd_band_tile: band membership
+// and the L2 a Gaussian's row atomics meet in are unchanged); its i-th workgroup takes the i-th tile of the band's queues read
+// from the heaviest class down. The 16 counts are wave-uniform (scalar loads), and they sum to the band's size, so the map is
+// a bijection; queue position and tile are clamped all the same, so that no scratch content sends a block outside the image.
+__device__ __forceinline__ int heaviest_first_tile(int bid, int tiles, const uint32_t* __restrict__ class_count) {
+    const int queue_stride = tile_queue_stride(tiles);
+    const int x = bid & (kTileBands - 1);
+    uint32_t rel = (uint32_t)bid >> 3;
+    const uint32_t* cc = class_count + x * kTileClasses;
+    int c = kTileClasses - 1;
+#pragma unroll
+    for (int k = kTileClasses - 1; k > 0; --k) {
+        const uint32_t n = cc[k];
+        if (c == k && rel >= n) { rel -= n; c = k - 1; }     // c == k: no heavier class holds position `rel`
+    }
+    rel = min(rel, (uint32_t)(queue_stride - 1));
+    const uint32_t t = tile_class_queues(class_count)[(size_t)(x * kTileClasses + c) * queue_stride + rel];
+    return (int)min(t, (uint32_t)(tiles - 1));
+}
+template <bool QUEUE>
 __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVES, MVI_RB_WAVES))) void render_backward_kernel(
     Frame f, const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ point_list,
     const float2* __restrict__ xy, const float4* __restrict__ rgbd, const float4* __restrict__ conic_opacity,
     const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
-    const float* __restrict__ dL_dpix, float* __restrict__ grad_rows, uint8_t* __restrict__ touched, ZeroRegions zero) {
+    const float* __restrict__ dL_dpix, float* __restrict__ grad_rows, uint8_t* __restrict__ touched, ZeroRegions zero,
+    const uint32_t* __restrict__ class_count) {
 #pragma clang fp contract(off)
     // the dense gradient outputs of the per-Gaussian chain rule are zeroed HERE (this kernel is bound by vector issue, its
     // memory pipes are idle): preprocess_backward then only writes the few per cent of rows that received a gradient
@@ -379,7 +467,8 @@ __global__ __launch_bounds__(kB2) __attribute__((amdgpu_waves_per_eu(MVI_RB_WAVE
     __shared__ float s_acc[kB2][9];                                   // raw moment sums per staged entry
     __shared__ uint32_t s_blast[2];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int tile = xcd_band_tile(blockIdx.x, f.gx * f.gy);
+    const int tile = QUEUE ? heaviest_first_tile(blockIdx.x, f.gx * f.gy, class_count)
+                           : xcd_band_tile(blockIdx.x, f.gx * f.gy);
     const int tile_y = tile / f.gx, tile_x = tile - tile_y * f.gx;
     const int hx0 = tile_x * kTile, hy0 = tile_y * kTile + 8 * wave;                  // this wave's 16 x 8 half tile
     const int pxi = hx0 + (lane & 15), py0 = hy0 + 2 * (lane >> 4), py1 = py0 + 1;
@@ -545,8 +634,13 @@ int launch_render_backward(const Frame& f, GeomView g, BinningView b, ImageView 
     if (zero) z = *zero;
     if (f.W <= 0 || f.H <= 0 || D <= 0) return launch_zero_regions(z, st);
     const uint32_t* plist = b.vals[b.passes & 1];
-    hipLaunchKernelGGL(render_backward_kernel, dim3(f.gx * f.gy), dim3(kB2), 0, st, f, im.ranges, plist, g.xy,
-                       g.rgbd, g.conic_opacity, im.final_T, im.n_contrib, dL_dpix, grad_rows, g.touched, z);
+    // heaviest first only from queues that a forward of this process left in THIS scratch; otherwise the plain order
+    if (g_backward_order == 1 && queue_filled(im.ranges, f.W, f.H))
+        hipLaunchKernelGGL(render_backward_kernel<true>, dim3(f.gx * f.gy), dim3(kB2), 0, st, f, im.ranges, plist, g.xy, g.rgbd,
+                           g.conic_opacity, im.final_T, im.n_contrib, dL_dpix, grad_rows, g.touched, z, im.class_count);
+    else
+        hipLaunchKernelGGL(render_backward_kernel<false>, dim3(f.gx * f.gy), dim3(kB2), 0, st, f, im.ranges, plist, g.xy, g.rgbd,
+                           g.conic_opacity, im.final_T, im.n_contrib, dL_dpix, grad_rows, g.touched, z, (const uint32_t*)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 

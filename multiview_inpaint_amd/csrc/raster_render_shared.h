@@ -39,7 +39,8 @@ __device__ __forceinline__ bool quad_overlap(float2 c, float4 co, float t2, floa
 // Workgroups are handed to the 8 XCDs round-robin by linear id, and every XCD has its own L2. Tile t of a launch of
 // `tiles` workgroups is chosen so that XCD x works through ONE contiguous band of tiles (rows of the image): the ~11
 // tiles a Gaussian touches then gather its 40 bytes through the same L2 (and their gradient atomics meet there)
-// instead of through up to 8 of them.
+// instead of through up to 8 of them. (render_backward_kernel may take the tiles of its band in another ORDER, heaviest first:
+// heaviest_first_tile in raster_render.hip; the band of a workgroup, bid & 7, is the same there.)
 __device__ __forceinline__ int xcd_band_tile(int bid, int tiles) {
     const int q = tiles >> 3, r = tiles & 7, x = bid & 7, i = bid >> 3;
     return x * q + (x < r ? x : r) + i;
