@@ -241,10 +241,12 @@ __global__ __launch_bounds__(kGnBlock) void gn_apply_kernel(const T* __restrict_
             const int cl = E < (1 << 24) ? div_small((uint32_t)e, (uint32_t)S, inv_S) : (int)(e / S);   // S % KV == 0 on this path: one channel per vector
             const int c = c0 + cl;
             const float add = cb ? cb[c] : 0.f;
-            float w = weight[c] * rstd, b = bias[c] + (add - mean) * w;
+            // centred first: folded into one fma, x (w rstd) + (bias - mean w rstd), the shift is rounded at the size of |mean| rstd
+            // instead of the spread — a constant group (variance 0, rstd = eps^-1/2) came out as bias +- 4e-5 instead of bias
+            const float w = weight[c] * rstd, off = add - mean, b = bias[c];
 #pragma unroll
             for (int k = 0; k < KV; ++k) {
-                float t = v[k] * w + b;
+                float t = (v[k] + off) * w + b;
                 v[k] = silu ? t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * -1.4426950408889634f)) : t;
             }
             if (!q.stack3) {
@@ -302,7 +304,7 @@ __global__ __launch_bounds__(256) void gn_apply_tokens_kernel(const T* __restric
     constexpr int VPRC = kGnTok / V;                      // vectors per token row of the tile (store side)
     constexpr int kPad = 16 / (int)sizeof(T);             // row pitch 128 + 16 bytes' worth: 16-byte aligned rows, transposed reads conflict-free
     __shared__ __attribute__((aligned(16))) T s_t[kGnTok][kGnTokS + kPad];
-    __shared__ float s_sc[kGnTok], s_sh[kGnTok];
+    __shared__ float s_sc[kGnTok], s_off[kGnTok], s_b[kGnTok];     // y = act((x + off) sc + b): centred first, see gn_apply_kernel
     int bid = blockIdx.x;
     const int stile = bid % s_tiles; bid /= s_tiles;
     const int ctile = bid % c_tiles;
@@ -339,7 +341,8 @@ __global__ __launch_bounds__(256) void gn_apply_tokens_kernel(const T* __restric
             const float add = q.chan_bias ? q.chan_bias[n * C + c] : 0.f;
             const float w = weight[c] * rstd;
             s_sc[threadIdx.x] = w;
-            s_sh[threadIdx.x] = bias[c] + (add - mean) * w;
+            s_off[threadIdx.x] = add - mean;
+            s_b[threadIdx.x] = bias[c];
         }
     }
     // the tile's loads do not depend on the scale / shift: issue them before the barrier
@@ -358,10 +361,10 @@ __global__ __launch_bounds__(256) void gn_apply_tokens_kernel(const T* __restric
         const int cr = i / VPRS, sv = i % VPRS;
         float v[V];
         Io<T>::load(reinterpret_cast<const T*>(&raw[j]), v);
-        const float w = s_sc[cr], b = s_sh[cr];
+        const float w = s_sc[cr], off = s_off[cr], b = s_b[cr];
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-            const float t = v[k] * w + b;
+            const float t = (v[k] + off) * w + b;
             v[k] = silu ? t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * -1.4426950408889634f)) : t;
         }
         Io<T>::store(&s_t[cr][sv * V], v);
@@ -464,10 +467,10 @@ __global__ __launch_bounds__(kGnResBlock) void gn_resident_kernel(const T* __res
         Io<T>::load(reinterpret_cast<const T*>(&r[i]), v);
         const int cl = chan_of(vi);
         const int c = c0 + cl;
-        const float w = weight[c] * rstd, b = bias[c] + ((cb ? cb[cl] : 0.f) - mean) * w;
+        const float w = weight[c] * rstd, off = (cb ? cb[cl] : 0.f) - mean, b = bias[c];      // centred first: see gn_apply_kernel
 #pragma unroll
         for (int k = 0; k < KV; ++k) {
-            const float t = v[k] * w + b;
+            const float t = (v[k] + off) * w + b;
             // t * sigmoid(t) with the hardware exp2 / rcp (1 ulp each): 5 instructions instead of the ~15 of expf + IEEE division
             v[k] = silu ? t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * -1.4426950408889634f)) : t;
         }
@@ -675,10 +678,10 @@ __global__ __launch_bounds__(kGnClusterBlock) __attribute__((amdgpu_waves_per_eu
         Io<T>::load(reinterpret_cast<const T*>(&r[i]), v);
         const int cl = chan_of(vi);
         const int c = c0 + cl;
-        const float w = weight[c] * rstd, b = bias[c] + ((cb ? cb[cl] : 0.f) - mean) * w;
+        const float w = weight[c] * rstd, off = (cb ? cb[cl] : 0.f) - mean, b = bias[c];      // centred first: see gn_apply_kernel
 #pragma unroll
         for (int k = 0; k < KV; ++k) {
-            const float t = v[k] * w + b;
+            const float t = (v[k] + off) * w + b;
             v[k] = silu ? t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * -1.4426950408889634f)) : t;
         }
         if (vi < v1) {

@@ -9,9 +9,11 @@
 //   stats : block = VPR x RP threads (VPR = C / vec 16-byte vectors per token, RP rows per pass) over up to 16 chunks of 8 RP tokens;
 //           a thread owns the SAME vec channels in every row; shifted sums per channel (see the kernel), assembled into the
 //           block's (count, mean, M2) per group;
-//   merge : one block per sample: Chan-merges the chunks of every group, then writes per-channel scale / shift
-//           (weight * rstd, bias + (chan_bias - mean) * weight * rstd) — 2 C floats per sample;
-//   apply : same thread layout as stats, y = act(x * scale[c] + shift[c]).
+//   merge : one block per sample: Chan-merges the chunks of every group, then writes per-channel scale / offset
+//           (weight * rstd, chan_bias - mean) — 2 C floats per sample;
+//   apply : same thread layout as stats, y = act((x + offset[c]) * scale[c] + bias[c]) — centred FIRST: folded into one fma,
+//           x scale + (bias - mean scale), the shift is rounded at the size of |mean| rstd instead of the spread, and a constant
+//           group (variance 0, rstd = eps^-1/2) came out as bias +- 4e-5 instead of bias.
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -27,7 +29,9 @@ constexpr int kGtMergeThreads = 1024;
 // A block walks `sets` consecutive chunks of 8 rp tokens (a thread owns the SAME vec channels in every row it reads) and keeps, per
 // channel, the sums S1 = sum(x - x0) and S2 = sum((x - x0)^2) SHIFTED by the block's first token x0 of that channel — the shifted-data
 // form of the variance: S1 and S2 are of the size of the spread, so nothing cancels when the group's moments are assembled from them
-// (chan_bias drops out of both; it only moves the mean). One LDS reduction per block instead of six barriers per 8 rp tokens: the
+// (chan_bias drops out of both; it only moves the mean). That holds while x0 is a typical token: with x0 D spreads away the three
+// terms below are rows D^2 sigma^2 each and cancel, the variance's relative error grows by 1 + 3 D^2 (harmless at D = 64, measured in
+// tests/test_norm_elementwise_gpu.py; the clamp below is in reach from D ~ 10^3). One LDS reduction per block instead of six barriers per 8 rp tokens: the
 // first form of this pass ran at 2.5 TB/s.
 template <typename T>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(5, 8))) void gt_stats_kernel(const T* __restrict__ x, const float* __restrict__ chan_bias, float* __restrict__ part,
@@ -223,19 +227,19 @@ __global__ __launch_bounds__(1024) void gt_fused_kernel(const T* __restrict__ a,
     }
 }
 
-// one block per sample: Chan merge per group, then per-channel scale / shift
+// one block per sample: Chan merge per group, then per-channel scale / offset (weight rstd, chan_bias - mean)
 // frames > 1: the temporal GroupNorm of VideoResBlock.time_stack (statistics over the `frames` consecutive samples of a video,
 // video_model.py:71-75): a block merges the chunks of all its frames — they are consecutive in `part` — and writes every frame's
-// scale / shift (the frames differ in chan_bias only).
+// scale / offset (the frames differ in chan_bias only).
 // stats (nullable; NULL on the inference path): [videos * G, 2] fp32 = (mean of x + chan_bias, rstd) per (video, group), the table
 // the backward reads (mvi_groupnorm_tok2tok_forward_stats); written by the block of the video's first frame.
-__global__ __launch_bounds__(kGtMergeThreads) void gt_merge_kernel(const float* __restrict__ part, const float* __restrict__ weight, const float* __restrict__ bias,
+__global__ __launch_bounds__(kGtMergeThreads) void gt_merge_kernel(const float* __restrict__ part, const float* __restrict__ weight,
                                                        const float* __restrict__ chan_bias, float* __restrict__ scale_shift, int C, int G,
                                                        int chunks_per_frame, float eps, int frames, float* __restrict__ stats) {
     __shared__ float s_mean[kGtMaxGroups], s_rstd[kGtMaxGroups];
     __shared__ float s_p[kGtMergeThreads][3];
     // one block per FRAME: it merges the chunks of its whole video (redundantly with its frames - 1 siblings: a few hundred partials
-    // from L2) and writes its own frame's scale / shift — one block per video left 2 blocks walking frames x C channels (25-37 us)
+    // from L2) and writes its own frame's scale / offset — one block per video left 2 blocks walking frames x C channels (25-37 us)
     const int64_t frame = blockIdx.x;
     const int64_t n = frame / frames * frames;              // first frame of the video
     const int chunks = chunks_per_frame * frames;
@@ -292,21 +296,21 @@ __global__ __launch_bounds__(kGtMergeThreads) void gt_merge_kernel(const float* 
         const float w = weight[c] * s_rstd[g];
         const float add = chan_bias ? chan_bias[frame * C + c] : 0.f;
         scale_shift[(frame * C + c) * 2 + 0] = w;
-        scale_shift[(frame * C + c) * 2 + 1] = bias[c] + (add - s_mean[g]) * w;
+        scale_shift[(frame * C + c) * 2 + 1] = add - s_mean[g];
     }
 }
 
 template <typename T>
-__global__ __launch_bounds__(1024) void gt_apply_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ scale_shift, int C,
-                                                        int64_t S, int vpr, int rp, int silu) {
+__global__ __launch_bounds__(1024) void gt_apply_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ scale_shift,
+                                                        const float* __restrict__ bias, int C, int64_t S, int vpr, int rp, int silu) {
     constexpr int V = Io<T>::kVec;
     const int tid = threadIdx.x, v = tid % vpr, r0 = tid / vpr;
     const int64_t n = blockIdx.y;
     const int64_t row0 = (int64_t)blockIdx.x * (kGtPasses * rp);
     const float* ss = scale_shift + (n * C + v * V) * 2;
-    float sc[V], sh[V];
+    float sc[V], sh[V], bs[V];
 #pragma unroll
-    for (int k = 0; k < V; ++k) { sc[k] = ss[2 * k]; sh[k] = ss[2 * k + 1]; }
+    for (int k = 0; k < V; ++k) { sc[k] = ss[2 * k]; sh[k] = ss[2 * k + 1]; bs[k] = bias[v * V + k]; }
     const T* xb = x + (n * S) * C + (int64_t)v * V;
     T* yb = y + (n * S) * C + (int64_t)v * V;
     uint4 raw[kGtPasses];                       // as loaded (4 registers per row, decoded one row at a time): see gt_stats_kernel
@@ -323,7 +327,7 @@ __global__ __launch_bounds__(1024) void gt_apply_kernel(const T* __restrict__ x,
             Io<T>::load(reinterpret_cast<const T*>(&raw[p]), t);
 #pragma unroll
             for (int k = 0; k < V; ++k) {
-                const float u = t[k] * sc[k] + sh[k];
+                const float u = (t[k] + sh[k]) * sc[k] + bs[k];
                 t[k] = silu ? u * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u * -1.4426950408889634f)) : u;
             }
             Io<T>::store(yb + row * C, t);
@@ -337,16 +341,17 @@ __global__ __launch_bounds__(1024) void gt_apply_kernel(const T* __restrict__ x,
 // kMode 0: (hi | lo) bf16, rows of 2 C; 1: hi only, bf16, rows of C; 2: one f16 value, rows of C (the operands of the terms = 1 launches).
 template <int kMode>
 __global__ __launch_bounds__(1024) void gt_apply_split_kernel(const float* __restrict__ x, uint16_t* __restrict__ y2, const float* __restrict__ scale_shift,
-                                                              int C, int64_t S, int vpr, int rp, int silu) {
+                                                              const float* __restrict__ bias, int C, int64_t S, int vpr, int rp, int silu) {
     constexpr int V = 4;
     const int tid = threadIdx.x, v = tid % vpr, r0 = tid / vpr;
     const int64_t n = blockIdx.y;
     const int64_t row0 = (int64_t)blockIdx.x * (kGtPasses * rp);
-    float sc[V], sh[V];
+    float sc[V], sh[V], bs[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
         sc[k] = scale_shift ? scale_shift[(n * C + v * V + k) * 2] : 1.f;
         sh[k] = scale_shift ? scale_shift[(n * C + v * V + k) * 2 + 1] : 0.f;
+        bs[k] = scale_shift ? bias[v * V + k] : 0.f;
     }
     const float* xb = x + (n * S) * C + (int64_t)v * V;
     constexpr int kRow = kMode == 0 ? 2 : 1;                       // output row = kRow C elements
@@ -365,7 +370,7 @@ __global__ __launch_bounds__(1024) void gt_apply_split_kernel(const float* __res
             uint16_t hi[V], lo[V];
 #pragma unroll
             for (int k = 0; k < V; ++k) {
-                float u = t[k] * sc[k] + sh[k];
+                float u = (t[k] + sh[k]) * sc[k] + bs[k];
                 if (silu) u = u * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u * -1.4426950408889634f));
                 if (kMode == 2) {
                     const __half h = __float2half(u);
@@ -403,11 +408,11 @@ static int gt_launch_split(const float* x, void* y2, const float* w, const float
         ss = ws + (size_t)N * chunks * G * 3;
         const size_t lds = ((size_t)2 * rp * C + C) * sizeof(float);
         hipLaunchKernelGGL((gt_stats_kernel<float>), dim3((unsigned)schunks, (unsigned)N), block, lds, st, x, cb, part, C, S, G, vpr, rp, schunks, sets);
-        hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, b, cb, ss, C, G, schunks, eps, frames, (float*)nullptr);
+        hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, cb, ss, C, G, schunks, eps, frames, (float*)nullptr);
     }
-    if (mode == 0) hipLaunchKernelGGL(gt_apply_split_kernel<0>, grid, block, 0, st, x, (uint16_t*)y2, ss, C, S, vpr, rp, silu);
-    else if (mode == 1) hipLaunchKernelGGL(gt_apply_split_kernel<1>, grid, block, 0, st, x, (uint16_t*)y2, ss, C, S, vpr, rp, silu);
-    else hipLaunchKernelGGL(gt_apply_split_kernel<2>, grid, block, 0, st, x, (uint16_t*)y2, ss, C, S, vpr, rp, silu);
+    if (mode == 0) hipLaunchKernelGGL(gt_apply_split_kernel<0>, grid, block, 0, st, x, (uint16_t*)y2, ss, b, C, S, vpr, rp, silu);
+    else if (mode == 1) hipLaunchKernelGGL(gt_apply_split_kernel<1>, grid, block, 0, st, x, (uint16_t*)y2, ss, b, C, S, vpr, rp, silu);
+    else hipLaunchKernelGGL(gt_apply_split_kernel<2>, grid, block, 0, st, x, (uint16_t*)y2, ss, b, C, S, vpr, rp, silu);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 
@@ -426,8 +431,8 @@ static int gt_launch(const void* x, void* y, const float* w, const float* b, con
     const dim3 grid((unsigned)chunks, (unsigned)N), block((unsigned)(vpr * rp));
     const size_t lds = ((size_t)2 * rp * C + C) * sizeof(float);
     hipLaunchKernelGGL((gt_stats_kernel<T>), dim3((unsigned)schunks, (unsigned)N), block, lds, st, (const T*)x, cb, part, C, S, G, vpr, rp, schunks, sets);
-    hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, b, cb, ss, C, G, schunks, eps, frames, stats);
-    hipLaunchKernelGGL((gt_apply_kernel<T>), grid, block, 0, st, (const T*)x, (T*)y, ss, C, S, vpr, rp, silu);
+    hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, cb, ss, C, G, schunks, eps, frames, stats);
+    hipLaunchKernelGGL((gt_apply_kernel<T>), grid, block, 0, st, (const T*)x, (T*)y, ss, b, C, S, vpr, rp, silu);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 
@@ -441,8 +446,8 @@ static int gt_launch_pre(const void* x, void* y, const float* w, const float* b,
     const int chunks = (int)((S + kGtPasses * rp - 1) / (kGtPasses * rp));
     float* ss = ws;                                               // [N, C, 2]
     const dim3 grid((unsigned)chunks, (unsigned)N), block((unsigned)(vpr * rp));
-    hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, b, cb, ss, C, G, chunks_per_sample, eps, frames, (float*)nullptr);
-    hipLaunchKernelGGL((gt_apply_kernel<T>), grid, block, 0, st, (const T*)x, (T*)y, ss, C, S, vpr, rp, silu);
+    hipLaunchKernelGGL(gt_merge_kernel, dim3((unsigned)N), dim3(kGtMergeThreads), 0, st, part, w, cb, ss, C, G, chunks_per_sample, eps, frames, (float*)nullptr);
+    hipLaunchKernelGGL((gt_apply_kernel<T>), grid, block, 0, st, (const T*)x, (T*)y, ss, b, C, S, vpr, rp, silu);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 
