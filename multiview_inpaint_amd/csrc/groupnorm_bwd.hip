@@ -66,6 +66,9 @@ __global__ __launch_bounds__(kGbBlock) void gn_bwd_tile_kernel(const T* __restri
     static_assert(!kTok || VEC, "the token-major layout exists on the vector path only");
     constexpr int NCH = kGbC / W;                         // 16-byte chunks per token row of the LDS image
     __shared__ __attribute__((aligned(16))) T s_d[kTok ? TS * kGbC : 8];
+    // xh = (x + s_b) s_a with s_b = chan_bias - mean: centred FIRST, as the forward's apply passes are. Folded into one fma,
+    // x rstd + (chan_bias - mean) rstd, the shift is rounded at the size of |mean| rstd instead of the spread: a constant group
+    // then has an xh of a few 1e-6 instead of 0, a dweight that is not 0, and every dx of the group is off
     __shared__ float s_a[kGbC], s_b[kGbC], s_w[kGbC], s_bias[kGbC], s_k2[kGbC], s_k3[kGbC];
     int bid = blockIdx.x;
     const int stile = bid % q.s_tiles; bid /= q.s_tiles;
@@ -80,7 +83,7 @@ __global__ __launch_bounds__(kGbBlock) void gn_bwd_tile_kernel(const T* __restri
         const float mean = q.stats[2 * vg], rstd = q.stats[2 * vg + 1];
         const float add = q.chan_bias ? q.chan_bias[row * C + c] : 0.f;
         s_a[threadIdx.x] = rstd;
-        s_b[threadIdx.x] = (add - mean) * rstd;
+        s_b[threadIdx.x] = add - mean;
         s_w[threadIdx.x] = q.weight[c];
         s_bias[threadIdx.x] = q.bias[c];
         if constexpr (APPLY) { s_k2[threadIdx.x] = coef[2 * vg]; s_k3[threadIdx.x] = coef[2 * vg + 1]; }
@@ -177,7 +180,7 @@ __global__ __launch_bounds__(kGbBlock) void gn_bwd_tile_kernel(const T* __restri
         float ov[W];
 #pragma unroll
         for (int k = 0; k < W; ++k) {
-            const float xh = xv[k] * a + b;
+            const float xh = (xv[k] + b) * a;
             const float gg = q.silu ? gv[k] * silu_grad(w * xh + bi) : gv[k];
             if constexpr (APPLY) {
                 ov[k] = (a * w) * gg - s_k2[cr] - xh * s_k3[cr];
@@ -330,10 +333,11 @@ static int gb_run(const void* x, const void* dy, const GbGeom& q, const GbPlan& 
 
 // ---- token-major x, dy, dx [N, S, C] ------------------------------------------------------------------------------------------------
 // The thread layout of groupnorm_tokens.hip: a block is vpr x rp threads (vpr = C / vec vectors per token row, rp rows per pass) on a
-// tile of kGtPasses rp tokens, and a thread owns the SAME vec channels in every row — its per-channel constants (rstd, (chan_bias -
-// mean) rstd, weight, bias, coef: looked up per CHANNEL, a vector may span groups) live in registers. kGkRows rows of x and of dy are
-// in flight per thread and step (the step loop stays rolled: unrolled, the compiler hoists every step's loads and spills); every
-// load is issued at a clamped row, rows past the end are masked where they are used.
+// tile of kGtPasses rp tokens, and a thread owns the SAME vec channels in every row — its per-channel constants (rstd, chan_bias - mean
+// (xh = (x + that) rstd: centred first, see gn_bwd_tile_kernel), weight, bias, coef: looked up per CHANNEL, a vector may span groups)
+// live in registers. kGkRows rows of x and of dy are in flight per thread and step (the step loop stays rolled: unrolled, the
+// compiler hoists every step's loads and spills); every load is issued at a clamped row, rows past the end are masked where they
+// are used.
 constexpr int kGkRows = 4;
 
 template <int V> struct GkChan { float a[V], b[V], w[V], bi[V]; };
@@ -347,7 +351,7 @@ template <int V> __device__ __forceinline__ void gk_channel_constants(const GbGe
         const float mean = q.stats[2 * vg], rstd = q.stats[2 * vg + 1];
         const float add = q.chan_bias ? q.chan_bias[n * q.C + c] : 0.f;
         k.a[i] = rstd;
-        k.b[i] = (add - mean) * rstd;
+        k.b[i] = add - mean;
         k.w[i] = q.weight[c];
         k.bi[i] = q.bias[c];
         if (coef) { k2[i] = coef[2 * vg]; k3[i] = coef[2 * vg + 1]; }
@@ -394,7 +398,7 @@ __global__ __launch_bounds__(1024) void gn_bwd_tok_reduce_kernel(const T* __rest
             const float m = row < S ? 1.f : 0.f;
 #pragma unroll
             for (int i = 0; i < V; ++i) {
-                const float xh = xv[i] * k.a[i] + k.b[i];
+                const float xh = (xv[i] + k.b[i]) * k.a[i];
                 const float gg = m * (q.silu ? gv[i] * silu_grad(k.w[i] * xh + k.bi[i]) : gv[i]);
                 p0[i] += gg; p1[i] += gg * xh; p2[i] += m * xh;
             }
@@ -449,7 +453,7 @@ __global__ __launch_bounds__(1024) void gn_bwd_tok_apply_kernel(const T* __restr
             Io<T>::load(reinterpret_cast<const T*>(&rd[p]), gv);
 #pragma unroll
             for (int i = 0; i < V; ++i) {
-                const float xh = xv[i] * k.a[i] + k.b[i];
+                const float xh = (xv[i] + k.b[i]) * k.a[i];
                 const float gg = q.silu ? gv[i] * silu_grad(k.w[i] * xh + k.bi[i]) : gv[i];
                 ov[i] = (k.a[i] * k.w[i]) * gg - k2[i] - xh * k3[i];
             }
