@@ -206,6 +206,19 @@ int mvi_raster_backward_render_aux(const mvi_raster_settings* s, int32_t P, int6
 int mvi_raster_backward_depth_to_means(const mvi_raster_settings* s, int32_t P, const float* grad_rows_scratch,
                                        float* dL_dmeans3D, void* stream);
 
+/* Mask lifting: per-Gaussian blend weights of a finished forward (any of the forward_render entries; before or after its
+ * backward), summed over exactly the (pixel, Gaussian) pairs that forward composited:
+ *     total_i = sum_p alpha_i(p) T_i(p)          hit_i,c = sum_p alpha_i(p) T_i(p) weights[c][p]
+ * acc [P][acc_stride] fp32 is ADDED into (never zeroed here): slot 0 += total, slots 1..channels += hit per channel; slots beyond
+ * are left alone. weights [channels][H][W] fp32, any values; NULL with channels == 0 (totals only). channels is 0..8, acc_stride
+ * at least 1 + channels (a row that does not straddle a 64-byte line is one atomic request per Gaussian and tile). Reads xy,
+ * conic_opacity, the point list, the tile ranges, final_T and n_contrib; reads no colours (pending deferred colours do not
+ * matter) and writes nothing but acc: the accumulation rows and the gradient support of a backward are untouched. Summing several
+ * views is calling it once per view on the same acc. P == 0, num_rendered == 0 or an empty image: returns 0, nothing launched. */
+int mvi_raster_lift_weights(const mvi_raster_settings* s, int32_t P, int64_t num_rendered, const void* geom, const void* binning,
+                            const void* image, const float* weights, int32_t channels, float* acc, int32_t acc_stride,
+                            void* stream);
+
 /* mvi_raster_backward_geom for the Gaussians [first, first + count) only (any first row): every pointer is the
  * base of the FULL [P, ...] array, as in mvi_raster_backward_geom; only rows of the range are read and written. Lets a
  * view-parallel trainer run the chain rule in a few ranges and start the all-reduce of a finished range's gradients

@@ -509,6 +509,26 @@ int mvi_raster_backward_depth_to_means(const mvi_raster_settings* s, int32_t P, 
     return MVI_OK;
 }
 
+int mvi_raster_lift_weights(const mvi_raster_settings* s, int32_t P, int64_t D, const void* geom, const void* binning,
+                            const void* image, const float* weights, int32_t channels, float* acc, int32_t acc_stride,
+                            void* stream) {
+    mvi::Frame f;
+    if (int rc = make_frame(s, P, 0, f)) return rc;
+    if (channels < 0 || channels > 8) return fail(MVI_EINVAL, "lift_weights: channels must be 0..8%s (got %lld)", "", channels);
+    if (acc_stride < 1 + channels)
+        return fail(MVI_EINVAL, "lift_weights: acc_stride %s%lld is below 1 + channels = %lld", "", acc_stride, 1 + channels);
+    if (channels > 0 && !weights) return fail(MVI_EINVAL, "lift_weights: weights is NULL with channels > 0%s");
+    if (D < 0 || D > 0xFFFFFFFFll) return fail(MVI_EINVAL, "num_rendered out of range%s: %lld", "", D);
+    if (P == 0 || D == 0 || f.W == 0 || f.H == 0) return MVI_OK;              // nothing was composited: nothing to add
+    if (!geom || !binning || !image || !acc) return fail(MVI_EINVAL, "NULL geom/binning/image/acc in lift_weights%s");
+    mvi::GeomView g = mvi::carve_geom(const_cast<void*>(geom), P);
+    mvi::ImageView im = mvi::carve_image(const_cast<void*>(image), f.W, f.H);
+    mvi::BinningView b = mvi::carve_binning(const_cast<void*>(binning), D, f.W, f.H);
+    if (mvi::launch_lift_weights(f, g, b, im, D, weights, channels, acc, acc_stride, (hipStream_t)stream))
+        return hip_fail("lift_weights", hipGetLastError());
+    return MVI_OK;
+}
+
 static int backward_geom_range_impl(const mvi_raster_settings* s, int32_t P, int32_t M, int32_t first, int32_t count,
                                     const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
                                     const float* rotations, const float* cov3D_precomp, const int32_t* radii, const void* geom,

@@ -611,6 +611,9 @@ int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView i
 int launch_render_backward_aux(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, const float* dL_dexpected_depth,
                                const float* dL_dalpha, float* grad_rows, hipStream_t st);
 int launch_depth_to_means(const Frame& f, const float* grad_rows, float* dL_dmeans3D, hipStream_t st);
+// raster_lift.hip: acc[id][0] += sum alpha T, acc[id][1 + c] += sum alpha T weights[c] over the pairs the forward composited
+int launch_lift_weights(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, const float* weights, int channels,
+                        float* acc, int acc_stride, hipStream_t st);
 int launch_resolve_colors(const Frame& f, GeomView g, hipStream_t st);      // evaluates every colour still pending
 // fills g.depths, g.cov_a / g.cov_b and g.tiles_touched, which the forward leaves unwritten, from the forward's inputs
 int launch_materialize_geom_views(const Frame& f, const float* means3D, const float* scales, const float* rotations,

@@ -388,6 +388,54 @@ def rasterize_backward_ranged(rs: GaussianRasterizationSettings, st: RasterState
     return g
 
 
+LIFT_MAX_CHANNELS = 8          # one wave sum of nine values per evaluated entry: the total and eight hits
+LIFT_ROW = 16                  # floats per Gaussian in a buffer lift_weights allocates: a 64-byte row, one atomic request
+
+
+def lift_weights(st: RasterState, weights=None, acc=None) -> torch.Tensor:
+    """Per-Gaussian blend weights of the forward that left `st` behind (any forward: no-grad, prepare_backward, aux; before or
+    after its backward), over exactly the (pixel, Gaussian) pairs it composited:
+        out[i, 0] = sum_p alpha_i(p) T_i(p)            out[i, 1 + c] = sum_p alpha_i(p) T_i(p) weights[c, p]
+    weights: CUDA fp32 [C, H, W] with C <= 8, or [H, W] (C = 1), or None (C = 0: totals only); any values. Returns fp32
+    [P, 1 + C], a view of a zeroed [P, 16] buffer (64-byte rows). acc: a tensor this function returned for the same P and C (or any
+    fp32 [P, 1 + C] tensor with unit inner stride): the view is ADDED into it and it is returned, which is how several views are
+    summed. out[:, 1 + c] / out[:, 0] is the share of a Gaussian's contribution that fell inside mask c (mask_lift.select)."""
+    L = _lib.lib()
+    dev = st.geom.device
+    if weights is None:
+        Cn, w = 0, None
+    else:
+        if not torch.is_tensor(weights) or not weights.is_cuda:
+            raise RuntimeError("lift_weights: weights must be a CUDA tensor; the rasterizer has no CPU path")
+        if weights.dtype != torch.float32:
+            raise TypeError(f"lift_weights: weights must be float32, got {weights.dtype}")
+        if weights.device != dev:
+            raise RuntimeError(f"lift_weights: weights are on {weights.device}, the forward ran on {dev}")
+        w = weights.detach()
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or tuple(w.shape[1:]) != (st.H, st.W):
+            raise ValueError(f"lift_weights: weights must be [C, {st.H}, {st.W}] or [{st.H}, {st.W}], got {tuple(weights.shape)}")
+        Cn = int(w.shape[0])
+        if Cn > LIFT_MAX_CHANNELS:
+            raise ValueError(f"lift_weights: at most {LIFT_MAX_CHANNELS} channels per call, got {Cn}")
+        w = w.contiguous()
+    if acc is None:
+        acc = torch.zeros(st.P, LIFT_ROW, dtype=torch.float32, device=dev)[:, :1 + Cn]
+    elif (not torch.is_tensor(acc) or acc.dtype != torch.float32 or acc.device != dev or tuple(acc.shape) != (st.P, 1 + Cn) or
+          (st.P > 0 and Cn > 0 and acc.stride(1) != 1) or (st.P > 1 and acc.stride(0) < 1 + Cn)):
+        raise ValueError(f"lift_weights: acc must be a fp32 [{st.P}, {1 + Cn}] tensor on {dev} with unit inner stride and "
+                         "rows that do not overlap")
+    if st.P == 0 or st.D == 0 or st.W == 0 or st.H == 0:
+        return acc
+    stride = int(acc.stride(0)) if st.P > 1 else 1 + Cn
+    with torch.cuda.device(dev):
+        _lib.check(L.mvi_raster_lift_weights(C.byref(st.frame.c), st.P, st.D, _ptr(st.geom), _ptr(st.binning), _ptr(st.image),
+                                             _ptr(w), Cn, _ptr(acc), stride,
+                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "lift_weights")
+    return acc
+
+
 def sh_backward_views(means3D, campos, color_factors, M, sh_degree, out=None):
     """Sum over views of the SH gradient rebuilt from per-view colour factors:
     out[g,k,c] = sum_v Y_k(normalize(means3D[g] - campos[v])) * color_factors[v,g,c]  ->  [P,M,3].
@@ -649,6 +697,19 @@ class GaussianRasterizer(torch.nn.Module):
             _lib.check(L.mvi_raster_mark_visible(p.shape[0], _ptr(p), _ptr(fr.keep[1]), _ptr(fr.keep[2]), _ptr(out), stream),
                        "mark_visible")
         return out.bool()
+
+    def lift(self, weights, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None, acc=None):
+        """lift_weights for callers that hold no RasterState: a no-grad forward of this view (zero precomputed colours — the
+        lift reads none) followed by the lift. weights [C,H,W] | [H,W] | None and acc as in lift_weights; returns [P, 1 + C]."""
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+            raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        with torch.no_grad():
+            m3 = _dev_f32(means3D, "means3D").reshape(-1, 3)
+            _, _, _, st = rasterize_forward(self.raster_settings, m3, _dev_f32(opacities, "opacities"),
+                                            colors_precomp=torch.zeros_like(m3), scales=_opt(scales), rotations=_opt(rotations),
+                                            cov3D_precomp=_opt(cov3D_precomp))
+            return lift_weights(st, weights, acc)
 
     def forward_raw(self, xyz, means2D, features_dc, features_rest, raw_opacity, raw_scaling, raw_rotation):
         """The same render fed with the GaussianModel's parameter tensors as stored (_xyz, _features_dc, _features_rest,
