@@ -12,8 +12,9 @@ Every test writes one line per launch through svd_helpers.report: entry point, s
 elements whose cap is below a quarter ulp (profiles/norm_elementwise_gpu.txt is that output of a run on an MI355X).
 
 Out of scope here: the GroupNorm statistics left by the convolution epilogue (taken BEFORE the rounding of the convolution's output: another
-contract, tests/test_unet_ops_gpu.py and tests/test_gemm_exact_gpu.py hold it), the split hi / lo output of the first-stage encoder
-(tests/test_vae_encode_split_gpu.py), and the fused GEGLU projections (tests/test_gemm_exact_gpu.py)."""
+contract, tests/test_unet_ops_gpu.py and tests/test_gemm_exact_gpu.py hold it), the split hi / lo output of the first stage
+(mvi_groupnorm_silu_tok2tok_split: tests/test_split3_exact_gpu.py holds both halves elementwise and the plain split bit for bit;
+tests/test_vae_encode_split_gpu.py the encoder walk built on it), and the fused GEGLU projections (tests/test_gemm_exact_gpu.py)."""
 import pytest
 import torch
 

@@ -1,7 +1,10 @@
 """The first-stage ENCODER at fp32 accuracy on the bf16 matrix pipe (svd/vae_split.py encode; opt-in through
 svd/vae.py encode_first_stage(mode="split3") / MVI_VAE_ENCODE=split3): the stride-2 split-operand convolution of Downsample
 (mvi_conv3x3_s2_split3_f32), conv_in as an fp32 stem that writes token rows (mvi_conv3x3_small_cin_f32_tokens), the walk on a small
-and on the full-size encoder, and the public entry. fp32 contract: 1e-4 relative, as tests/test_vae_gpu.py."""
+and on the full-size encoder, and the public entry. fp32 contract: 1e-4 relative, as tests/test_vae_gpu.py.
+The max-norm bars here are on Gaussian data; the exact-answer tests of the three split-operand convolutions (one right fp32 bit pattern
+per output, borders, padded column groups, the stride-2 origin) and of the split hi / lo producer are tests/test_split3_exact_gpu.py,
+on the data of tests/split3_exact_helpers.py (tests/test_split3_exact_cpu.py shows what those comparisons reject)."""
 import ctypes as C
 import os
 
