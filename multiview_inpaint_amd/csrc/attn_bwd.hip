@@ -246,19 +246,11 @@ void attn_bwd_kernel(const T* __restrict__ res1, const T* __restrict__ res2, con
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 const uint32_t to = tr_a + (uint32_t)(32 * sb * kStride * 2 + 32 * dt);
-                {
-                    s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(img1 + to));
-                    s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(img1 + to + 16 * kStride * 2));
-                    const u32x2 a = *reinterpret_cast<u32x2*>(&lo4), bb = *reinterpret_cast<u32x2*>(&hi4);
-                    const frag t1 = as_frag<frag>(u32x4{a[0], a[1], bb[0], bb[1]});
+                const frag t1 = read_frag_tr<frag>(img1 + to, 16 * kStride * 2);
 #pragma unroll
-                    for (int rt = 0; rt < 2; ++rt) acc1[dt][rt] = M::mfma(t1, as_frag<frag>(dsf[rt]), acc1[dt][rt]);   // dQ^T += K^T dS^T | dK^T += Q^T dS
-                }
+                for (int rt = 0; rt < 2; ++rt) acc1[dt][rt] = M::mfma(t1, as_frag<frag>(dsf[rt]), acc1[dt][rt]);       // dQ^T += K^T dS^T | dK^T += Q^T dS
                 if (!kDQ) {
-                    s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(img2 + to));
-                    s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(img2 + to + 16 * kStride * 2));
-                    const u32x2 a = *reinterpret_cast<u32x2*>(&lo4), bb = *reinterpret_cast<u32x2*>(&hi4);
-                    const frag t2 = as_frag<frag>(u32x4{a[0], a[1], bb[0], bb[1]});
+                    const frag t2 = read_frag_tr<frag>(img2 + to, 16 * kStride * 2);
 #pragma unroll
                     for (int rt = 0; rt < 2; ++rt) acc2[dt][rt] = M::mfma(t2, as_frag<frag>(pf[rt]), acc2[dt][rt]);    // dV^T += dO^T P
                 }

@@ -267,10 +267,7 @@ void attn_flash8m16_kernel(const T* __restrict__ q, const T* __restrict__ k, con
 #pragma unroll
         for (int dt = dt0; dt < dt0 + 2; ++dt) {
             const int off = slot * kTileBytes + kb * 4096;
-            s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(lds + va[dt] + off));
-            s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(lds + va[dt] + off + 2048));
-            const u32x2 a = *reinterpret_cast<u32x2*>(&lo4), bb = *reinterpret_cast<u32x2*>(&hi4);
-            vs[dt] = u32x4{a[0], a[1], bb[0], bb[1]};
+            vs[dt] = read_frag_tr<u32x4>(lds + va[dt] + off, 2048);
         }
     };
     // exp / pack / row sum of query tile qt of a block: the P fragment (B operand of the P V MFMAs of that query tile)
@@ -487,18 +484,11 @@ int attn_flash8m16_launch(const void* q, const void* k, const void* v, void* out
     const int64_t total = (int64_t)B * H * q_blocks;
     if (total > 0x7FFFFFFFll) return MVI_EINVAL;
     if ((int64_t)Sk * kv_rs * 2 > 0xFFFFFFFFll) return MVI_EINVAL;       // 32-bit byte offsets inside one batch entry
-    // more than 64 KiB of dynamic LDS needs the opt-in attribute, once per device and instantiation
-    static unsigned long long attr_set = 0ull;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MVI_EHIP;
-    if (!((attr_set >> dev) & 1ull)) {
-        const void* all[4] = {reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false>),
-                              reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, true, true>), reinterpret_cast<const void*>(&attn_flash8m16_kernel<T, false, true>)};
-        for (const void* f : all)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + 16) != hipSuccess) return MVI_EHIP;
-        attr_set |= 1ull << dev;
-    }
-    auto kern = lse ? (fold ? &attn_flash8m16_kernel<T, false, true> : &attn_flash8m16_kernel<T, true, true>)
+    // all four forms before the first launch of any
+    if (allow_large_lds<&attn_flash8m16_kernel<T, true>>(kLdsBytes + 16) || allow_large_lds<&attn_flash8m16_kernel<T, false>>(kLdsBytes + 16) ||
+        allow_large_lds<&attn_flash8m16_kernel<T, true, true>>(kLdsBytes + 16) || allow_large_lds<&attn_flash8m16_kernel<T, false, true>>(kLdsBytes + 16))
+        return MVI_EHIP;
+    auto kern =lse ? (fold ? &attn_flash8m16_kernel<T, false, true> : &attn_flash8m16_kernel<T, true, true>)
                     : (fold ? &attn_flash8m16_kernel<T, false> : &attn_flash8m16_kernel<T, true>);
     hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(64 * kWaves), kLdsBytes + 16, st, (const T*)q, (const T*)k, (const T*)v,
                        (T*)out, H, Sq, Sk, q_log2 ? 1.0f : scale * 1.4426950408889634f, q_blocks, (int)total, q_rs, kv_rs, o_rs, lse);

@@ -22,19 +22,17 @@
 // 12 for the six B fragments, 24 MFMAs: 0.83 reads per MFMA against the 1.17 of a 16-channel wave (csrc/conv3x3_wgrad.hip: 0.72 with
 // nine taps). 64-channel tiles because the time-stack widths are 320 k; 40 KiB of LDS, so four blocks (8 waves) share a CU.
 //
-// Split: the output-tile grid alone is (C_out / 64)(C_in / 64) blocks, 25 at 320 x 320. The units (B x ceil(S / 64)) are cut into
-// R contiguous ranges, R = min(units, 1024 / tiles, 64) — a pure host function of the shape (split_of). R = 1: blocks store dweight.
-// R > 1: block (tile, r) stores its fp32 partial to workspace[r], and a second launch adds the R partials in index order. No atomics;
-// run-to-run identical bits. Addresses are 64-bit throughout.
+// Split (wgrad_split.h): the output-tile grid alone is (C_out / 64)(C_in / 64) blocks, 25 at 320 x 320. Unit: (video, chunk), B x ceil(S / 64)
+// of them; target 1024 blocks; a partial is 3 C_out C_in floats. Addresses are 64-bit throughout.
 //
 // -Rpass-analysis=kernel-resource-usage (hipcc 7, -O3, the flags of attn_bwd.hip), per instance:
 //   conv3t_wgrad_kernel<bf16> and <f16>: 212 VGPRs, 0 AGPRs, 69 SGPRs, no scratch, occupancy 2 waves per SIMD, 40 960 bytes of
 //   static LDS per block (four blocks per CU = the 160 KiB).
-//   conv3t_wgrad_reduce_kernel: 12 VGPRs, 17 SGPRs, no LDS, no scratch.
 #include <cstdint>
 
 #include "mfma_common.h"
 #include "unet_host.h"
+#include "wgrad_split.h"
 
 namespace mvi {
 namespace ctw {
@@ -50,7 +48,6 @@ constexpr int kSlot = kKc * kRow;               // one staged chunk
 constexpr int kLds = 4 * kSlot;                 // dy + the ring of three x chunks
 constexpr int kPassRows = kThreads / 8;         // rows a pass of the block stages (8 pieces of 16 bytes per 64-channel row)
 constexpr int kPasses = kKc / kPassRows;
-constexpr int kMaxSplit = 64;
 constexpr int kTargetBlocks = 1024;             // four 2-wave blocks (the 160 KiB of LDS) on each of the 256 CUs
 
 template <typename T> using Mma = MmaBuiltin16<T>;
@@ -133,12 +130,7 @@ void conv3t_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, floa
                 const uint32_t so = (uint32_t)(32 * st * kRow);
                 frag a[4];
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-                    s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(ldy + so + tr + 32 * mt));
-                    s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(ldy + so + tr + 32 * mt + 16 * kRow));
-                    const u32x2 l = *reinterpret_cast<u32x2*>(&lo4), h = *reinterpret_cast<u32x2*>(&hi4);
-                    a[mt] = as_frag<frag>(u32x4{l[0], l[1], h[0], h[1]});
-                }
+                for (int mt = 0; mt < 4; ++mt) a[mt] = read_frag_tr<frag>(ldy + so + tr + 32 * mt, 16 * kRow);
 #pragma unroll
                 for (int t = 0; t < 3; ++t) {
                     const int f = u + t - 1;                       // the x frame of tap t
@@ -146,10 +138,7 @@ void conv3t_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, floa
                     const uint32_t to = (uint32_t)((f % 3) * kSlot) + so + tr_b;
 #pragma unroll
                     for (int nt = 0; nt < kNT; ++nt) {
-                        s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(lx + to + 32 * nt));
-                        s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(lx + to + 32 * nt + 16 * kRow));
-                        const u32x2 l = *reinterpret_cast<u32x2*>(&lo4), h = *reinterpret_cast<u32x2*>(&hi4);
-                        const frag bb = as_frag<frag>(u32x4{l[0], l[1], h[0], h[1]});
+                        const frag bb = read_frag_tr<frag>(lx + to + 32 * nt, 16 * kRow);
 #pragma unroll
                         for (int mt = 0; mt < 4; ++mt) acc[t][nt][mt] = M::mfma(a[mt], bb, acc[t][nt][mt]);
                     }
@@ -176,50 +165,30 @@ void conv3t_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, floa
                 for (int t = 0; t < 3; ++t) op[((int64_t)(16 * mt + i) * C_in + 16 * nt) * 3 + t] = acc[t][nt][mt][i];
 }
 
-// out[i] = part[0][i] + part[1][i] + ... in that order
-__global__ __launch_bounds__(256) void conv3t_wgrad_reduce_kernel(const f32x4* __restrict__ part, f32x4* __restrict__ out, int64_t n4,
-                                                                  int splits) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    f32x4 a = part[i];
-    for (int s = 1; s < splits; ++s) a += part[s * n4 + i];
-    out[i] = a;
-}
-
 static bool shape_ok(int64_t B, int32_t T, int32_t S, int32_t C_in, int32_t C_out) {
     return B >= 0 && T >= 1 && S >= 1 && C_in > 0 && C_out > 0 && C_in % kBN == 0 && C_out % kBM == 0 && B < (1ll << 31) &&
            (int64_t)(C_in / kBN) * (C_out / kBM) <= 0x7FFFFFFFll;
 }
 
-// The split policy: a pure function of the shape (the shape of cwg::split_of: about two blocks per CU, capped).
-static int split_of(int64_t B, int32_t S, int32_t C_in, int32_t C_out, int* chunks_per_video) {
-    const int cpv = (S + kKc - 1) / kKc;
-    const int64_t units = B * cpv, tiles = (int64_t)(C_in / kBN) * (C_out / kBM);
-    int64_t R = kTargetBlocks / tiles;
-    if (R > kMaxSplit) R = kMaxSplit;
-    if (R > units) R = units;
-    if (chunks_per_video) *chunks_per_video = cpv;
-    return R < 2 ? 1 : (int)R;
+// chunks of one video: what the kernel indexes by
+static int chunks_per_video(int32_t S) { return (S + kKc - 1) / kKc; }
+
+static int splits_of(int64_t B, int cpv, int32_t C_in, int32_t C_out) {
+    return split_count(B * cpv, (int64_t)(C_in / kBN) * (C_out / kBM), kTargetBlocks);
 }
 
 template <typename T>
 static int launch(const void* x, const void* dy, float* dweight, int64_t B, int frames, int S, int C_in, int C_out, void* ws, size_t ws_bytes,
                   hipStream_t st) {
-    int cpv = 0;
-    int R = split_of(B, S, C_in, C_out, &cpv);
+    const int cpv = chunks_per_video(S);
+    int R = splits_of(B, cpv, C_in, C_out);
     const int64_t total = (int64_t)C_out * C_in * 3;
-    if (R > 1 && (!ws || ws_bytes < (size_t)R * total * sizeof(float))) R = 1;          // no workspace: the unsplit launch
+    if (R > 1 && (!ws || ws_bytes < (size_t)R * total * sizeof(float))) R = 1;          // a short workspace: the unsplit launch (linear_wgrad.hip refuses)
     const unsigned tiles = (unsigned)((C_in / kBN) * (C_out / kBM));
     hipLaunchKernelGGL(conv3t_wgrad_kernel<T>, dim3(tiles, (unsigned)R), dim3(kThreads), 0, st, (const T*)x, (const T*)dy,
                        R > 1 ? (float*)ws : dweight, frames, S, C_in, C_out, cpv, B * cpv, R);
     if (hipGetLastError() != hipSuccess) return MVI_EHIP;
-    if (R > 1) {
-        const int64_t n4 = total / 4;
-        hipLaunchKernelGGL(conv3t_wgrad_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const f32x4*)ws, (f32x4*)dweight,
-                           n4, R);
-        if (hipGetLastError() != hipSuccess) return MVI_EHIP;
-    }
-    return 0;
+    return R > 1 ? wgrad_reduce((const float*)ws, dweight, nullptr, total, 0, R, st) : 0;
 }
 
 }  // namespace ctw
@@ -231,7 +200,7 @@ extern "C" int mvi_conv3t_wgrad_supported(int32_t C_in, int32_t C_out, int32_t d
 
 extern "C" size_t mvi_conv3t_wgrad_workspace_bytes(int64_t B, int32_t T, int32_t pixels, int32_t C_in, int32_t C_out) {
     if (!mvi::ctw::shape_ok(B, T, pixels, C_in, C_out) || B == 0) return 0;
-    const int R = mvi::ctw::split_of(B, pixels, C_in, C_out, nullptr);
+    const int R = mvi::ctw::splits_of(B, mvi::ctw::chunks_per_video(pixels), C_in, C_out);
     return R > 1 ? (size_t)R * (size_t)C_out * C_in * 3 * sizeof(float) : 0;
 }
 
@@ -239,7 +208,7 @@ extern "C" int mvi_conv3t_wgrad(const void* x, const void* dy, float* dweight, i
                                 int32_t C_out, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
     if (!mvi_conv3t_wgrad_supported(C_in, C_out, dtype) || !mvi::ctw::shape_ok(B, T, pixels, C_in, C_out))
         return mvi::unet_fail(MVI_EINVAL, "conv3t wgrad: needs C_in and C_out multiples of 64, bf16 or f16, T >= 1, pixels >= 1");
-    if (!dweight || ((!x || !dy) && B > 0)) return mvi::unet_fail(MVI_EINVAL, "conv3t wgrad: NULL pointer");
+    if (!dweight || ((!x || !dy) && B > 0)) return mvi::unet_fail(MVI_EINVAL, "conv3t wgrad: NULL pointer");   // (mvi_conv3x3_wgrad rejects these with B == 0 too)
     if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dweight | (uintptr_t)workspace) % 16)
         return mvi::unet_fail(MVI_EINVAL, "conv3t wgrad: x, dy, dweight and workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;

@@ -19,15 +19,12 @@
 // needed the accumulators of one tap at a time and so either nine loads of dy or a write of partials per chunk.
 // LDS rows are 160 bytes apart (40 banks: the 8 rows of a 32-lane half of a transposed read cover the 64 banks once).
 //
-// Split: the output-tile grid alone is (C_out / 64)(C_in / 64) blocks, 25 at 320 x 320. The chunks (N x ceil(H P / 160)) are cut into
-// S contiguous ranges, S = min(chunks, 512 / tiles, 64) — a pure host function of the shape (split_of). S = 1: blocks store dweight.
-// S > 1: block (tile, s) stores its fp32 partial to workspace[s], and a second launch adds the S partials in index order. No atomics;
-// run-to-run identical bits. Addresses are 64-bit throughout.
+// Split (wgrad_split.h): the output-tile grid alone is (C_out / 64)(C_in / 64) blocks, 25 at 320 x 320. Unit: a chunk, N x ceil(H P / 160)
+// of them (kS2: N x ceil((H / 2)(W / 2 + 1) / 64)); target 512 blocks; a partial is 9 C_out C_in floats. Addresses are 64-bit throughout.
 //
 // -Rpass-analysis=kernel-resource-usage (hipcc 7, -O3, the flags of attn_bwd.hip), per instance:
 //   conv3x3_wgrad_kernel<bf16> and <f16>: 196 VGPRs, 0 AGPRs, 69 SGPRs, no scratch, occupancy 2 waves per SIMD;
 //   LDS dynamic, 160 (2 kKc + 2 P + 2) bytes: 72 640 at W = 64 (two blocks per CU), 56 000 at W = 12; W <= 256 (134 400).
-//   conv3x3_wgrad_reduce_kernel: 12 VGPRs, no LDS, no scratch.
 //
 // kS2: the weight gradient of the STRIDE-2 convolution (mvi_conv3x3_s2_wgrad; H, W even, dy [N, (H / 2)(W / 2), C_out]):
 //     dweight[co][ci][ky][kx] = sum over (n, r, c) of dy[n, r, c, co] * x[n, 2 r + ky - 1, 2 c + kx - 1, ci]      (outside the image: 0)
@@ -42,11 +39,11 @@
 // zeros for every value and measured 0.04 - 0.08 of the matrix peak; this one costs four x images, two of them a row
 // longer than the chunk, so its chunk is kKcS2 = 64 positions: 160 (5 kKcS2 + 2 P + 8) bytes = 73 280 at W = 128, two blocks per CU.
 //   conv3x3_wgrad_kernel<bf16, true> and <f16, true>: 196 VGPRs, 0 AGPRs, 88 SGPRs, no scratch, occupancy 2 waves per SIMD.
-#include <atomic>
 #include <cstdint>
 
 #include "mfma_common.h"
 #include "unet_host.h"
+#include "wgrad_split.h"
 
 namespace mvi {
 namespace cwg {
@@ -59,7 +56,6 @@ constexpr int kSteps = kKc / 32;
 constexpr int kKcS2 = 64;                       // kS2: dy positions per chunk (the four x planes have to fit beside them)
 constexpr int kRow = 160;                       // LDS row stride in bytes: 64 channels + 32 bytes of padding
 constexpr int kMaxW = 256;
-constexpr int kMaxSplit = 64;
 constexpr int kTargetBlocks = 512;              // two blocks on each of the 256 CUs
 
 template <typename T> using Mma = MmaBuiltin16<T>;
@@ -177,60 +173,61 @@ void conv3x3_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, flo
             for (int t = 0; t < 9; ++t) op[(int64_t)(16 * mt + i) * C_in * 9 + t] = acc[t][mt][i];
 }
 
-// out[i] = part[0][i] + part[1][i] + ... in that order
-__global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_kernel(const f32x4* __restrict__ part, f32x4* __restrict__ out, int64_t n4,
-                                                                   int splits) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    f32x4 a = part[i];
-    for (int s = 1; s < splits; ++s) a += part[s * n4 + i];
-    out[i] = a;
-}
-
 static bool shape_ok(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out) {
     return N >= 0 && H >= 1 && W >= 1 && W <= kMaxW && C_in > 0 && C_out > 0 && C_in % kBN == 0 && C_out % kBM == 0 &&
            (int64_t)H * (W + 2) < (1ll << 30) && (int64_t)(C_in / kBN) * (C_out / kBM) <= 0x7FFFFFFFll;
 }
 
-// The split policy: a pure function of the shape.
-static int split_of(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out, int* chunks_per_image, bool s2 = false) {
-    const int cpi = s2 ? (int)(((int64_t)(H / 2) * (W / 2 + 1) + kKcS2 - 1) / kKcS2) : (int)(((int64_t)H * (W + 2) + kKc - 1) / kKc);
-    const int64_t chunks = N * cpi, tiles = (int64_t)(C_in / kBN) * (C_out / kBM);
-    int64_t S = kTargetBlocks / tiles;
-    if (S > kMaxSplit) S = kMaxSplit;
-    if (S > chunks) S = chunks;
-    if (chunks_per_image) *chunks_per_image = cpi;
-    return S < 2 ? 1 : (int)S;
+// chunks of one image: what the kernel indexes by
+static int chunks_per_image(int32_t H, int32_t W, bool s2) {
+    return s2 ? (int)(((int64_t)(H / 2) * (W / 2 + 1) + kKcS2 - 1) / kKcS2) : (int)(((int64_t)H * (W + 2) + kKc - 1) / kKc);
 }
 
-template <typename T, bool kS2 = false>
+static int splits_of(int64_t N, int cpi, int32_t C_in, int32_t C_out) {
+    return split_count(N * cpi, (int64_t)(C_in / kBN) * (C_out / kBM), kTargetBlocks);
+}
+
+template <bool kS2> static size_t workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out) {
+    if (!shape_ok(N, H, W, C_in, C_out) || N == 0 || (kS2 && ((H & 1) || (W & 1)))) return 0;
+    const int S = splits_of(N, chunks_per_image(H, W, kS2), C_in, C_out);
+    return S > 1 ? (size_t)S * (size_t)C_out * C_in * 9 * sizeof(float) : 0;
+}
+
+template <typename T, bool kS2>
 static int launch(const void* x, const void* dy, float* dweight, int64_t N, int H, int W, int C_in, int C_out, void* ws, size_t ws_bytes,
                   hipStream_t st) {
-    int cpi = 0;
-    int S = split_of(N, H, W, C_in, C_out, &cpi, kS2);
+    const int cpi = chunks_per_image(H, W, kS2);
+    int S = splits_of(N, cpi, C_in, C_out);
     const int64_t total = (int64_t)C_out * C_in * 9;
-    if (S > 1 && (!ws || ws_bytes < (size_t)S * total * sizeof(float))) S = 1;          // no workspace: the unsplit launch
+    if (S > 1 && (!ws || ws_bytes < (size_t)S * total * sizeof(float))) S = 1;          // a short workspace: the unsplit launch (linear_wgrad.hip refuses)
     const int lds_bytes = (kS2 ? s2_lds_rows(W) : kKc + x_rows(W)) * kRow;
-    static std::atomic<unsigned long long> attr_set{0};          // per device and instantiation: the opt-in for > 64 KiB of dynamic LDS
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MVI_EHIP;
-    auto kern = &conv3x3_wgrad_kernel<T, kS2>;
-    if (!(attr_set.load(std::memory_order_acquire) >> dev & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return MVI_EHIP;
-        attr_set.fetch_or(1ull << dev, std::memory_order_release);
-    }
+    if (allow_large_lds<&conv3x3_wgrad_kernel<T, kS2>>(160 * 1024)) return MVI_EHIP;
     const unsigned tiles = (unsigned)((C_in / kBN) * (C_out / kBM));
-    hipLaunchKernelGGL(kern, dim3(tiles, (unsigned)S), dim3(64 * kWaves), lds_bytes, st, (const T*)x, (const T*)dy,
+    hipLaunchKernelGGL((conv3x3_wgrad_kernel<T, kS2>), dim3(tiles, (unsigned)S), dim3(64 * kWaves), lds_bytes, st, (const T*)x, (const T*)dy,
                        S > 1 ? (float*)ws : dweight, H, W, C_in, C_out, cpi, N * cpi, S);
     if (hipGetLastError() != hipSuccess) return MVI_EHIP;
-    if (S > 1) {
-        const int64_t n4 = total / 4;
-        hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const f32x4*)ws, (f32x4*)dweight,
-                           n4, S);
-        if (hipGetLastError() != hipSuccess) return MVI_EHIP;
-    }
-    return 0;
+    return S > 1 ? wgrad_reduce((const float*)ws, dweight, nullptr, total, 0, S, st) : 0;
+}
+
+// The body of both entry points. kS2: x [N, H W, C_in], dy [N, (H / 2)(W / 2), C_out], H and W even; gate, split policy (over dy's own
+// position space), workspace and determinism as stride 1. Messages are MSG(" text") behind the entry point's own prefix.
+template <bool kS2>
+static int entry(const void* x, const void* dy, float* dweight, int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out, int32_t dtype,
+                 void* workspace, size_t workspace_bytes, void* stream) {
+#define MSG(text) (kS2 ? "conv3x3 s2 wgrad:" text : "conv3x3 wgrad:" text)
+    if (!mvi_conv3x3_wgrad_supported(C_in, C_out, dtype) || !shape_ok(N, H, W, C_in, C_out) || (kS2 && ((H & 1) || (W & 1))))
+        return unet_fail(MVI_EINVAL, kS2 ? "conv3x3 s2 wgrad: needs C_in and C_out multiples of 64, bf16 or f16, even H and W, W <= 256"
+                                         : "conv3x3 wgrad: needs C_in and C_out multiples of 64, bf16 or f16, 1 <= W <= 256");
+    if (!x || !dy || !dweight) return unet_fail(MVI_EINVAL, MSG(" NULL pointer"));       // also with N == 0 (conv3t and linear accept that)
+    if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dweight | (uintptr_t)workspace) % 16)
+        return unet_fail(MVI_EINVAL, MSG(" x, dy, dweight and workspace must be 16-byte aligned"));
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) return hipMemsetAsync(dweight, 0, (size_t)C_out * C_in * 9 * sizeof(float), st) == hipSuccess ? MVI_OK : MVI_EHIP;
+    const int rc = dispatch_dtype16(dtype, MSG(" unknown dtype"), [&](auto t) {
+        return launch<typename decltype(t)::type, kS2>(x, dy, dweight, N, H, W, C_in, C_out, workspace, workspace_bytes, st);
+    });
+    return rc == MVI_EHIP ? unet_fail(rc, MSG(" kernel launch failed")) : rc;
+#undef MSG
 }
 
 }  // namespace cwg
@@ -241,47 +238,22 @@ extern "C" int mvi_conv3x3_wgrad_supported(int32_t C_in, int32_t C_out, int32_t 
 }
 
 extern "C" size_t mvi_conv3x3_wgrad_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out) {
-    if (!mvi::cwg::shape_ok(N, H, W, C_in, C_out) || N == 0) return 0;
-    const int S = mvi::cwg::split_of(N, H, W, C_in, C_out, nullptr);
-    return S > 1 ? (size_t)S * (size_t)C_out * C_in * 9 * sizeof(float) : 0;
+    return mvi::cwg::workspace_bytes<false>(N, H, W, C_in, C_out);
 }
 
 extern "C" int mvi_conv3x3_wgrad(const void* x, const void* dy, float* dweight, int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out,
                                  int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!mvi_conv3x3_wgrad_supported(C_in, C_out, dtype) || !mvi::cwg::shape_ok(N, H, W, C_in, C_out))
-        return mvi::unet_fail(MVI_EINVAL, "conv3x3 wgrad: needs C_in and C_out multiples of 64, bf16 or f16, 1 <= W <= 256");
-    if (!x || !dy || !dweight) return mvi::unet_fail(MVI_EINVAL, "conv3x3 wgrad: NULL pointer");
-    if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dweight | (uintptr_t)workspace) % 16)
-        return mvi::unet_fail(MVI_EINVAL, "conv3x3 wgrad: x, dy, dweight and workspace must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (N == 0) return hipMemsetAsync(dweight, 0, (size_t)C_out * C_in * 9 * sizeof(float), st) == hipSuccess ? MVI_OK : MVI_EHIP;
-    const int rc = mvi::dispatch_dtype16(dtype, "conv3x3 wgrad: unknown dtype", [&](auto t) {
-        return mvi::cwg::launch<typename decltype(t)::type>(x, dy, dweight, N, H, W, C_in, C_out, workspace, workspace_bytes, st);
-    });
-    return rc == MVI_EHIP ? mvi::unet_fail(rc, "conv3x3 wgrad: kernel launch failed") : rc;
+    return mvi::cwg::entry<false>(x, dy, dweight, N, H, W, C_in, C_out, dtype, workspace, workspace_bytes, stream);
 }
 
-// The stride-2 form (kS2 at the kernel): x [N, H W, C_in], dy [N, (H / 2)(W / 2), C_out], H and W even; gate, split policy (a pure function
-// of (N, H, W, C_in, C_out): the stride-1 kernel's over dy's own position space), workspace and determinism as mvi_conv3x3_wgrad.
+// The stride-2 form (kS2 at the kernel).
 extern "C" int mvi_conv3x3_s2_wgrad_supported(int32_t C_in, int32_t C_out, int32_t dtype) { return mvi_conv3x3_wgrad_supported(C_in, C_out, dtype); }
 
 extern "C" size_t mvi_conv3x3_s2_wgrad_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t C_in, int32_t C_out) {
-    if (!mvi::cwg::shape_ok(N, H, W, C_in, C_out) || N == 0 || (H & 1) || (W & 1)) return 0;
-    const int S = mvi::cwg::split_of(N, H, W, C_in, C_out, nullptr, true);
-    return S > 1 ? (size_t)S * (size_t)C_out * C_in * 9 * sizeof(float) : 0;
+    return mvi::cwg::workspace_bytes<true>(N, H, W, C_in, C_out);
 }
 
 extern "C" int mvi_conv3x3_s2_wgrad(const void* x, const void* dy, float* dweight, int64_t N, int32_t H, int32_t W, int32_t C_in,
                                     int32_t C_out, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!mvi_conv3x3_wgrad_supported(C_in, C_out, dtype) || !mvi::cwg::shape_ok(N, H, W, C_in, C_out) || (H & 1) || (W & 1))
-        return mvi::unet_fail(MVI_EINVAL, "conv3x3 s2 wgrad: needs C_in and C_out multiples of 64, bf16 or f16, even H and W, W <= 256");
-    if (!x || !dy || !dweight) return mvi::unet_fail(MVI_EINVAL, "conv3x3 s2 wgrad: NULL pointer");
-    if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dweight | (uintptr_t)workspace) % 16)
-        return mvi::unet_fail(MVI_EINVAL, "conv3x3 s2 wgrad: x, dy, dweight and workspace must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (N == 0) return hipMemsetAsync(dweight, 0, (size_t)C_out * C_in * 9 * sizeof(float), st) == hipSuccess ? MVI_OK : MVI_EHIP;
-    const int rc = mvi::dispatch_dtype16(dtype, "conv3x3 s2 wgrad: unknown dtype", [&](auto t) {
-        return mvi::cwg::launch<typename decltype(t)::type, true>(x, dy, dweight, N, H, W, C_in, C_out, workspace, workspace_bytes, st);
-    });
-    return rc == MVI_EHIP ? mvi::unet_fail(rc, "conv3x3 s2 wgrad: kernel launch failed") : rc;
+    return mvi::cwg::entry<true>(x, dy, dweight, N, H, W, C_in, C_out, dtype, workspace, workspace_bytes, stream);
 }

@@ -266,16 +266,9 @@ static int ff_k320_launch(const void* x, const void* w, const float* bias, void*
     const int64_t n_blocks = (rows + kRows - 1) / kRows;
     if (n_blocks > 0x7FFFFFFFll) return MVI_EINVAL;
     const int lds_bytes = kRing * kTileBytes + (kGeglu ? 2 : 1) * inner * (int)sizeof(float) + (kGeglu ? 0 : kWaves * 4096);
-    static unsigned long long attr_set = 0;                      // per device and instantiation: the opt-in for > 64 KiB of dynamic LDS
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MVI_EHIP;
-    auto kern = &ff_geglu_k320_kernel<T, kGeglu>;
-    if (!(attr_set >> dev & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return MVI_EHIP;
-        attr_set |= 1ull << dev;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_blocks), dim3(64 * kWaves), lds_bytes, st, (const T*)x, (const T*)w, bias, (T*)out, rows, inner,
+    constexpr auto kern = &ff_geglu_k320_kernel<T, kGeglu>;
+    if (allow_large_lds<kern>(160 * 1024)) return MVI_EHIP;
+    hipLaunchKernelGGL(kern,dim3((unsigned)n_blocks), dim3(64 * kWaves), lds_bytes, st, (const T*)x, (const T*)w, bias, (T*)out, rows, inner,
                        x_rs, o_rs, (int)n_blocks);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }

@@ -22,7 +22,6 @@
 // dweight = dh^T x and dbias = colsum(dh); without it nothing tensor-sized is written besides dx. kDx = false (dx NULL: x does not
 // require grad, the parameters do): recomputation, gate and the dh store only, no contraction.
 // Ragged last block: rows past the end load the last valid row (x, dy) and store nothing. No lane is masked around a transposed read.
-#include <atomic>
 #include <cstdint>
 #include <type_traits>
 
@@ -150,10 +149,7 @@ void ff_geglu_bwd_kernel(const T* __restrict__ x, const T* __restrict__ w, const
 #pragma unroll
             for (int sb = 0; sb < 2; ++sb) {
                 const uint32_t to = tr_a + (uint32_t)(32 * sb * kStride * 2 + 32 * dt);
-                s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(img + to));
-                s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((MVI_AS3 s16x4*)(img + to + 16 * kStride * 2));
-                const u32x2 a = *reinterpret_cast<u32x2*>(&lo4), bb = *reinterpret_cast<u32x2*>(&hi4);
-                const frag wt = as_frag<frag>(u32x4{a[0], a[1], bb[0], bb[1]});
+                const frag wt = read_frag_tr<frag>(img + to, 16 * kStride * 2);
                 acc[dt] = M::mfma(wt, as_frag<frag>(sb ? dgf : daf), acc[dt]);
             }
         }
@@ -189,16 +185,9 @@ static int launch(const void* x, const void* w, const float* bias, const void* d
     const int64_t n_blocks = (rows + kRB - 1) / kRB;
     if (n_blocks > 0x7FFFFFFFll) return MVI_EINVAL;
     const int lds_bytes = 2 * kImg + 2 * inner * (int)sizeof(float);
-    static std::atomic<unsigned long long> attr_set{0};          // per device and instantiation: the opt-in for > 64 KiB of dynamic LDS
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MVI_EHIP;
-    auto kern = &ff_geglu_bwd_kernel<T, kStoreDh, kDx>;
-    if (!(attr_set.load(std::memory_order_acquire) >> dev & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return MVI_EHIP;
-        attr_set.fetch_or(1ull << dev, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_blocks), dim3(64 * kWaves), lds_bytes, st, (const T*)x, (const T*)w, bias, (const T*)dy, (T*)dx,
+    constexpr auto kern = &ff_geglu_bwd_kernel<T, kStoreDh, kDx>;
+    if (allow_large_lds<kern>(160 * 1024)) return MVI_EHIP;
+    hipLaunchKernelGGL(kern,dim3((unsigned)n_blocks), dim3(64 * kWaves), lds_bytes, st, (const T*)x, (const T*)w, bias, (const T*)dy, (T*)dx,
                        (T*)dh, rows, inner, x_rs, dy_rs, dx_rs, dh_rs);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }

@@ -817,16 +817,9 @@ static int linear_n320_launch(const void* x, const void* w, const float* bias, v
     using namespace ln3;
     const int64_t n_blocks = (rows + kRows - 1) / kRows * cg.groups * cg.ksplit;
     if (n_blocks > 0x7FFFFFFFll) return MVI_EINVAL;
-    static unsigned long long attr_set = 0;                      // per device and instantiation: the opt-in for > 64 KiB of dynamic LDS
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MVI_EHIP;
-    auto kern = &linear_n320_kernel<T, kConv, kSplit, kStats, kGeglu, kLn, NOUT, kUps, kPersist, kZs>;
+    constexpr auto kern = &linear_n320_kernel<T, kConv, kSplit, kStats, kGeglu, kLn, NOUT, kUps, kPersist, kZs>;
     constexpr int kLdsBytes = kRing * NOUT * kKC * 2 + kWaves * 4096 + (kPersist ? 2048 : 0);       // (+ the staged bias of the next tile)
-    if (!(attr_set >> dev & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return MVI_EHIP;
-        attr_set |= 1ull << dev;
-    }
+    if (allow_large_lds<kern>(160 * 1024)) return MVI_EHIP;
     // kPersist: one block per CU walks the tiles (the caller checked persist_ok: more tiles than CUs, an even number of chunks)
     const unsigned grid = kPersist ? (unsigned)persist_grid() : (unsigned)n_blocks;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kWaves), kLdsBytes, st, (const T*)x, (const T*)w, bias, (T*)out, rows, K, x_rs,

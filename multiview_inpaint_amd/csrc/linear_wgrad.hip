@@ -22,11 +22,10 @@
 // fragment with a fragment of ONES as well (4 more MFMAs per step): every column of that accumulator tile is the column sum of dy.
 // It goes through the same split and reduction; dy is never read a second time.
 //
-// Split: the tile grid alone is ceil(N / 128) ceil(K / 128) blocks (9 at 320 x 320, 24 at 960 x 320). The row chunks are cut into S
-// contiguous ranges, S = min(chunks, 512 / tiles, 64), rounded down to a multiple of 8 above 8 — a pure host function of the shape (split_of). S = 1: blocks store dweight
-// and dbias. S > 1: block (tile, s) stores its fp32 partials to workspace[s] ([S][N K] then [S][N]), and a second launch adds the
-// S partials in index order. No atomics; run-to-run identical bits. Addresses are 64-bit; the per-lane DMA offset is 32-bit and
-// relative to the chunk's first row (gate: 64 rows of either operand span less than 4 GiB).
+// Split (wgrad_split.h): the tile grid alone is ceil(N / 128) ceil(K / 128) blocks (9 at 320 x 320, 24 at 960 x 320). Unit: a row
+// chunk, ceil(rows / 64) of them; target 512 blocks, in whole groups of 8 slices above 8; the partials are [S][N K] floats, then [S][N]
+// for dbias. Addresses are 64-bit; the per-lane DMA offset is 32-bit and relative to the chunk's first row (gate: 64 rows of either
+// operand span less than 4 GiB).
 //
 // -Rpass-analysis=kernel-resource-usage (hipcc 7, -O3, the flags of attn_bwd.hip): DESIGN.md section 4, "Projections under autograd".
 #include <cstdint>
@@ -34,6 +33,7 @@
 
 #include "mfma_common.h"
 #include "unet_host.h"
+#include "wgrad_split.h"
 
 namespace mvi {
 namespace lwg {
@@ -47,7 +47,6 @@ constexpr int kOpBytes = kRc * kRowB;           // one operand's chunk: 16 KiB =
 constexpr int kBufBytes = 2 * kOpBytes;         // x | dy
 constexpr int kLdsBytes = 2 * kBufBytes;        // double-buffered: 64 KiB, two blocks per CU
 constexpr int kPiecesPerWave = kOpBytes / 1024 / kWaves;
-constexpr int kMaxSplit = 64;
 constexpr int kXcds = 8;
 constexpr int kTargetBlocks = 512;              // two blocks on each of the 256 CUs
 constexpr int kVmcnt0 = 0x0F70;                 // s_waitcnt vmcnt(0) alone: expcnt and lgkmcnt fields at their maximum
@@ -68,7 +67,7 @@ void linear_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, floa
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, g = lane >> 4;
     const int wn = wave >> 1, wk = wave & 1;
-    // Blocks are dealt round-robin over the 8 XCDs. With 8 or more slices (then a multiple of 8: split_of) block 8 j + c is tile
+    // Blocks are dealt round-robin over the 8 XCDs. With 8 or more slices (then a multiple of 8: splits_of) block 8 j + c is tile
     // j % tiles of slice 8 (j / tiles) + c: all tiles of a row slice run on ONE XCD and share its rows through that L2 (speed only:
     // 0.153 -> 0.108 ms at 258048 x 320 -> 320). Fewer slices: tile-fastest order, every XCD busy.
     const int bj = splits >= kXcds ? (int)blockIdx.x >> 3 : (int)blockIdx.x;
@@ -178,19 +177,6 @@ void linear_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, floa
     }
 }
 
-// out[i] = part[0][i] + part[1][i] + ... in that order; the bias partials ([S][N], behind the [S][N K] weight partials) likewise
-__global__ __launch_bounds__(256) void linear_wgrad_reduce_kernel(const f32x4* __restrict__ part, f32x4* __restrict__ dweight,
-                                                                  f32x4* __restrict__ dbias, int64_t nk4, int64_t n4, int splits) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nk4 + n4) return;
-    const bool w = i < nk4;
-    const f32x4* const p = w ? part + i : part + (int64_t)splits * nk4 + (i - nk4);
-    const int64_t step = w ? nk4 : n4;
-    f32x4 a = p[0];
-    for (int s = 1; s < splits; ++s) a += p[s * step];
-    if (w) dweight[i] = a; else dbias[i - nk4] = a;
-}
-
 static bool shape_ok(int64_t rows, int32_t K, int32_t N) {
     return rows >= 0 && K > 0 && N > 0 && K % 64 == 0 && N % 64 == 0 && rows < (1ll << 40) &&
            (int64_t)((K + kBK - 1) / kBK) * ((N + kBN - 1) / kBN) <= 0x7FFFFFFFll / (kXcds * kMaxSplit);
@@ -199,15 +185,9 @@ static bool shape_ok(int64_t rows, int32_t K, int32_t N) {
 // a row stride (elements): at least the row, rows 16-byte aligned, 64 rows inside the DMA's 32-bit lane offset
 static bool stride_ok(int64_t stride, int32_t width) { return stride >= width && stride % 8 == 0 && stride < (1ll << 24); }
 
-// The split policy: a pure function of the shape.
-static int split_of(int64_t rows, int32_t K, int32_t N, int64_t* chunks_out) {
-    const int64_t chunks = (rows + kRc - 1) / kRc, tiles = (int64_t)((K + kBK - 1) / kBK) * ((N + kBN - 1) / kBN);
-    int64_t S = kTargetBlocks / tiles;
-    if (S > kMaxSplit) S = kMaxSplit;
-    if (S > chunks) S = chunks;
-    if (S > kXcds) S -= S % kXcds;               // whole groups of 8 slices: the kernel's XCD-aware block order
-    if (chunks_out) *chunks_out = chunks;
-    return S < 2 ? 1 : (int)S;
+// whole groups of 8 slices above 8: the kernel's XCD-aware block order
+static int splits_of(int64_t rows, int32_t K, int32_t N) {
+    return split_count((rows + kRc - 1) / kRc, (int64_t)((K + kBK - 1) / kBK) * ((N + kBN - 1) / kBN), kTargetBlocks, kXcds);
 }
 
 static size_t workspace_of(int S, int32_t K, int32_t N) { return S > 1 ? (size_t)S * ((size_t)N * K + (size_t)N) * sizeof(float) : 0; }
@@ -223,13 +203,7 @@ static int launch(const void* x, const void* dy, float* dweight, float* dbias, i
     hipLaunchKernelGGL(linear_wgrad_kernel<T>, dim3((unsigned)tiles * (unsigned)S), dim3(64 * kWaves), 0, st, (const T*)x,
                        (const T*)dy, wpart, bpart, rows, K, N, xs, dys, k_tiles, tiles, chunks, S);
     if (hipGetLastError() != hipSuccess) return MVI_EHIP;
-    if (S > 1) {
-        const int64_t nk4 = (int64_t)N * K / 4, n4 = dbias ? N / 4 : 0;
-        hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((unsigned)((nk4 + n4 + 255) / 256)), dim3(256), 0, st, (const f32x4*)ws,
-                           (f32x4*)dweight, (f32x4*)dbias, nk4, n4, S);
-        if (hipGetLastError() != hipSuccess) return MVI_EHIP;
-    }
-    return 0;
+    return S > 1 ? wgrad_reduce((const float*)ws, dweight, dbias, (int64_t)N * K, dbias ? N : 0, S, st) : 0;
 }
 
 }  // namespace lwg
@@ -241,7 +215,7 @@ extern "C" int mvi_linear_wgrad_supported(int32_t K, int32_t out_features, int32
 
 extern "C" size_t mvi_linear_wgrad_workspace_bytes(int64_t rows, int32_t K, int32_t out_features) {
     if (!mvi::lwg::shape_ok(rows, K, out_features) || rows == 0) return 0;
-    return mvi::lwg::workspace_of(mvi::lwg::split_of(rows, K, out_features, nullptr), K, out_features);
+    return mvi::lwg::workspace_of(mvi::lwg::splits_of(rows, K, out_features), K, out_features);
 }
 
 // workspace NULL (and workspace_bytes 0): the unsplit launch, one block per tile over all rows. Otherwise it holds at least
@@ -257,9 +231,9 @@ extern "C" int mvi_linear_wgrad(const void* x, const void* dy, float* dweight, f
     if (!dweight || (rows > 0 && (!x || !dy))) return mvi::unet_fail(MVI_EINVAL, "linear wgrad: NULL pointer");      // (no rows: nothing is read)
     if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dweight | (uintptr_t)dbias | (uintptr_t)workspace) % 16)
         return mvi::unet_fail(MVI_EINVAL, "linear wgrad: x, dy, dweight, dbias and workspace must be 16-byte aligned");
-    int S = mvi::lwg::split_of(rows, K, N, nullptr);
+    int S = mvi::lwg::splits_of(rows, K, N);
     if (!workspace && workspace_bytes == 0) S = 1;
-    else if (!workspace || workspace_bytes < mvi::lwg::workspace_of(S, K, N))
+    else if (!workspace || workspace_bytes < mvi::lwg::workspace_of(S, K, N))      // a short workspace is refused (the convolutions run unsplit)
         return mvi::unet_fail(MVI_EINVAL, "linear wgrad: workspace shorter than mvi_linear_wgrad_workspace_bytes");
     hipStream_t st = (hipStream_t)stream;
     if (rows == 0) {

@@ -1,8 +1,11 @@
 // The host side that the UNet kernel files share: the status codes and dtype tags of the C ABI, the error record, and the
-// dtype -> template-argument dispatch of the entry points.
+// dtype -> template-argument dispatch of the entry points, and the opt-in of a kernel to more than 64 KiB of dynamic LDS.
 #pragma once
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
+#include <hip/hip_runtime.h>
+
+#include <atomic>
 
 #include "../../include/mvi_raster.h"        // MVI_OK / MVI_E*
 #include "../../include/mvi_unet_ops.h"      // MVI_DT_*
@@ -30,6 +33,22 @@ template <typename F> int dispatch_dtype16(int dtype, const char* what, F&& f) {
         case MVI_DT_F16: return f(DtypeTag<__half>{});
         default: return unet_fail(MVI_EINVAL, what);
     }
+}
+
+// A launch with more than 64 KiB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize set on the kernel, once per device.
+// kKern is the kernel's address, so the flag word (one bit per device) is per kernel by construction. Launchers run on any thread
+// (autograd's backward has one per device): the bit is published with release and read with acquire; two threads that both find it
+// clear both set the attribute, which is harmless. 0 or MVI_EHIP.
+template <auto kKern> int allow_large_lds(int bytes) {
+    static std::atomic<unsigned long long> attr_set{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return MVI_EHIP;
+    if (!(attr_set.load(std::memory_order_acquire) >> dev & 1ull)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kKern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+            return MVI_EHIP;
+        attr_set.fetch_or(1ull << dev, std::memory_order_release);
+    }
+    return 0;
 }
 
 }  // namespace mvi

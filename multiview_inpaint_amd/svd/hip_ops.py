@@ -78,6 +78,12 @@ def _contig(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _aligned(t):
+    """t contiguous at a 16-byte aligned address (the kernels read 16-byte vectors); a copy only where it is not."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
@@ -474,7 +480,7 @@ def _rows_operands(x, weight, bias, clone_misaligned_weight):
     if xc.stride(1) != 1 or xc.stride(0) % 8 or xc.data_ptr() % 16:
         xc = xc.contiguous()
     if clone_misaligned_weight:
-        wc = weight if weight.is_contiguous() and weight.data_ptr() % 16 == 0 else weight.contiguous().clone()
+        wc = _aligned(weight)
     else:
         wc = _contig(weight)
     rows = xc.shape[0]
@@ -705,8 +711,7 @@ def linear_n320_add_layer_norm(x, weight, bias, ln_weight, ln_bias, eps, resid=N
     if row is not None:
         if row.dtype != x.dtype or row.shape[-1] != N:
             raise ValueError("linear_n320_add_layer_norm: row must be [G, 320] / [G, 1, 320] of x's dtype")
-        rowc = row.reshape(-1, N)
-        rowc = rowc if rowc.is_contiguous() and rowc.data_ptr() % 16 == 0 else rowc.contiguous().clone()
+        rowc = _aligned(row.reshape(-1, N))
         G = rowc.shape[0]
         if G == 0 or rows % G:
             raise ValueError(f"linear_n320_add_layer_norm: {rows} rows do not split into {G} equal runs")
@@ -783,7 +788,7 @@ def _conv_taps_n320(kind, tok, weight_taps, bias, N, H, W, taps, stride=1, split
     rows = N * Ho * Wo
     if tok.numel() != N * H * W * C or weight_taps.shape[1] != taps * C or weight_taps.dtype != tok.dtype:
         raise ValueError(f"{kind}: token-major activations [.., C_in] of N H W rows and weight [C_out, {taps} C_in] of one dtype expected")
-    xc = tok if tok.is_contiguous() and tok.data_ptr() % 16 == 0 else tok.contiguous().clone()
+    xc = _aligned(tok)
     wc = _contig(weight_taps)
     Co = wc.shape[0]
     cap = int(L.mvi_ff_geglu_out_rows(rows))
@@ -865,6 +870,18 @@ def conv3x3_dgrad(dy_tok, weight_t_taps, H, W, split=True):
     return conv3x3_n320(dy_tok, weight_t_taps, None, H, W, split=split, kind="conv3x3_dgrad")
 
 
+def _conv_wgrad(entry, workspace_bytes, dims, tok, dy_tok, out_shape, kind, flops, split):
+    """The launch of the three convolution weight gradients: entry(x, dy, dweight, *dims, dtype, workspace, workspace_bytes, stream) on
+    aligned operands, with the workspace workspace_bytes(*dims) asks for unless split is False. -> dweight, fp32 [*out_shape]."""
+    xc, dc = _aligned(tok), _aligned(dy_tok)
+    dw = torch.empty(out_shape, dtype=torch.float32, device=tok.device)
+    ws_bytes = int(workspace_bytes(*dims)) if split else 0
+    ws = _workspace(tok.device, ws_bytes) if ws_bytes else None
+    with torch.cuda.device(tok.device), _Timed(kind, flops, tok.device):
+        _check(entry(xc.data_ptr(), dc.data_ptr(), dw.data_ptr(), *dims, _DT.get(tok.dtype, -1), _ptr(ws), ws_bytes, _stream(tok.device)), kind)
+    return dw
+
+
 def conv3x3_wgrad_supported(C_in, C_out, dtype):
     return dtype in (torch.bfloat16, torch.float16) and bool(_lib.lib().mvi_conv3x3_wgrad_supported(int(C_in), int(C_out), _DT[dtype]))
 
@@ -883,15 +900,8 @@ def conv3x3_wgrad(tok, dy_tok, H, W, split=True):
         raise ValueError("conv3x3_wgrad: tok [N, H W, C_in] and dy_tok [N, H W, C_out] of one dtype expected")
     N, S, C = tok.shape
     Co = dy_tok.shape[2]
-    xc = tok if tok.is_contiguous() and tok.data_ptr() % 16 == 0 else tok.contiguous().clone()
-    dc = dy_tok if dy_tok.is_contiguous() and dy_tok.data_ptr() % 16 == 0 else dy_tok.contiguous().clone()
-    dw = torch.empty(Co, C, 3, 3, dtype=torch.float32, device=tok.device)
-    ws_bytes = int(L.mvi_conv3x3_wgrad_workspace_bytes(N, H, W, C, Co)) if split else 0
-    ws = _workspace(tok.device, ws_bytes) if ws_bytes else None
-    with torch.cuda.device(tok.device), _Timed("conv3x3_wgrad", 2.0 * N * S * 9 * C * Co, tok.device):
-        _check(L.mvi_conv3x3_wgrad(xc.data_ptr(), dc.data_ptr(), dw.data_ptr(), N, H, W, C, Co, _DT.get(tok.dtype, -1), _ptr(ws), ws_bytes,
-                                   _stream(tok.device)), "conv3x3_wgrad")
-    return dw
+    return _conv_wgrad(L.mvi_conv3x3_wgrad, L.mvi_conv3x3_wgrad_workspace_bytes, (N, H, W, C, Co), tok, dy_tok, (Co, C, 3, 3),
+                       "conv3x3_wgrad", 2.0 * N * S * 9 * C * Co, split)
 
 
 # ---- the stride-2 and the upsampling 3x3 convolution under autograd (ops._Conv3x3DownTokensFn / _Conv3x3UpTokensFn) ---------------------
@@ -910,7 +920,7 @@ def conv3x3_s2_dgrad(dy_tok, weight_t_taps, H, W):
     N, _, Co = dy_tok.shape
     if weight_t_taps.dim() != 2 or weight_t_taps.shape[1] != 9 * Co or weight_t_taps.dtype != dy_tok.dtype:
         raise ValueError("conv3x3_s2_dgrad: packed transposed weight [C_in, 9 C_out] of dy's dtype expected")
-    dc = dy_tok if dy_tok.is_contiguous() and dy_tok.data_ptr() % 16 == 0 else dy_tok.contiguous().clone()
+    dc = _aligned(dy_tok)
     wc = _contig(weight_t_taps)
     Ci = wc.shape[0]
     rows = N * H * W
@@ -941,15 +951,8 @@ def conv3x3_s2_wgrad(tok, dy_tok, H, W, split=True):
         raise ValueError("conv3x3_s2_wgrad: tok [N, H W, C_in] and dy_tok [N, (H / 2)(W / 2), C_out] of one dtype expected")
     N, S, C = tok.shape
     Co = dy_tok.shape[2]
-    xc = tok if tok.is_contiguous() and tok.data_ptr() % 16 == 0 else tok.contiguous().clone()
-    dc = dy_tok if dy_tok.is_contiguous() and dy_tok.data_ptr() % 16 == 0 else dy_tok.contiguous().clone()
-    dw = torch.empty(Co, C, 3, 3, dtype=torch.float32, device=tok.device)
-    ws_bytes = int(L.mvi_conv3x3_s2_wgrad_workspace_bytes(N, H, W, C, Co)) if split else 0
-    ws = _workspace(tok.device, ws_bytes) if ws_bytes else None
-    with torch.cuda.device(tok.device), _Timed("conv3x3_s2_wgrad", 2.0 * N * dy_tok.shape[1] * 9 * C * Co, tok.device):
-        _check(L.mvi_conv3x3_s2_wgrad(xc.data_ptr(), dc.data_ptr(), dw.data_ptr(), N, H, W, C, Co, _DT.get(tok.dtype, -1), _ptr(ws), ws_bytes,
-                                      _stream(tok.device)), "conv3x3_s2_wgrad")
-    return dw
+    return _conv_wgrad(L.mvi_conv3x3_s2_wgrad, L.mvi_conv3x3_s2_wgrad_workspace_bytes, (N, H, W, C, Co), tok, dy_tok, (Co, C, 3, 3),
+                       "conv3x3_s2_wgrad", 2.0 * N * dy_tok.shape[1] * 9 * C * Co, split)
 
 
 def pool2x2_sum(g_tok, h, w):
@@ -959,7 +962,7 @@ def pool2x2_sum(g_tok, h, w):
     if g_tok.dim() != 3 or g_tok.shape[1] != 4 * h * w:
         raise ValueError("pool2x2_sum: g_tok [N, (2 h)(2 w), C] expected")
     N, _, C = g_tok.shape
-    gc = g_tok if g_tok.is_contiguous() and g_tok.data_ptr() % 16 == 0 else g_tok.contiguous().clone()
+    gc = _aligned(g_tok)
     out = torch.empty(N, h * w, C, dtype=g_tok.dtype, device=g_tok.device)
     with torch.cuda.device(g_tok.device), _Timed("pool2x2_sum", 3.0 * N * h * w * C, g_tok.device):
         _check(L.mvi_rows_pool2x2_sum(gc.data_ptr(), out.data_ptr(), N, h, w, C, _DT.get(g_tok.dtype, -1), _stream(g_tok.device)), "pool2x2_sum")
@@ -1016,15 +1019,8 @@ def conv3t_wgrad(tok, dy_tok, T, split=True):
     BT, S, C = tok.shape
     B = BT // T
     Co = dy_tok.shape[2]
-    xc = tok if tok.is_contiguous() and tok.data_ptr() % 16 == 0 else tok.contiguous().clone()
-    dc = dy_tok if dy_tok.is_contiguous() and dy_tok.data_ptr() % 16 == 0 else dy_tok.contiguous().clone()
-    dw = torch.empty(Co, C, 3, 1, 1, dtype=torch.float32, device=tok.device)
-    ws_bytes = int(L.mvi_conv3t_wgrad_workspace_bytes(B, T, S, C, Co)) if split else 0
-    ws = _workspace(tok.device, ws_bytes) if ws_bytes else None
-    with torch.cuda.device(tok.device), _Timed("conv3t_wgrad", 2.0 * BT * S * 3 * C * Co, tok.device):
-        _check(L.mvi_conv3t_wgrad(xc.data_ptr(), dc.data_ptr(), dw.data_ptr(), B, T, S, C, Co, _DT.get(tok.dtype, -1), _ptr(ws), ws_bytes,
-                                  _stream(tok.device)), "conv3t_wgrad")
-    return dw
+    return _conv_wgrad(L.mvi_conv3t_wgrad, L.mvi_conv3t_wgrad_workspace_bytes, (B, T, S, C, Co), tok, dy_tok, (Co, C, 3, 1, 1),
+                       "conv3t_wgrad", 2.0 * BT * S * 3 * C * Co, split)
 
 
 def stem_conv3x3_supported(conv, x):
@@ -1084,11 +1080,6 @@ def _stem_out_shape(x, weight, stride):
     return N, weight.shape[0], (H - 1) // stride + 1, (W - 1) // stride + 1
 
 
-def _stem_aligned(t):
-    t = t.contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
 def stem_conv3x3_dz(x, weight, bias, dy, silu=True, stride=1, with_y=False):
     """dz = dy * silu'(conv2d(x, weight, bias, stride, padding=1)) with z recomputed in the forward kernel (silu=False: dz = dy);
     x [N, C_in, H, W], dy [N, C_out, H_out, W_out] -> dz like dy. with_y: (dz, y), y the forward's output from the same launch.
@@ -1099,7 +1090,7 @@ def stem_conv3x3_dz(x, weight, bias, dy, silu=True, stride=1, with_y=False):
         raise ValueError("stem_conv3x3_dz: dy [N, C_out, H_out, W_out] in x's dtype expected")
     wc = _stem_packed_weight(weight, W, stride)
     b = None if bias is None else _f32(bias)
-    xc, dc = _stem_aligned(x), _stem_aligned(dy)
+    xc, dc = _aligned(x), _aligned(dy)
     dz = torch.empty_like(dc)
     y = torch.empty_like(dc) if with_y else None
     with torch.cuda.device(x.device), _Timed("stem_conv_dz", float(x.numel() + 2 * dz.numel()) * x.element_size(), x.device):
@@ -1124,7 +1115,7 @@ def stem_conv3x3_wgrad(x, dz, stride=1, need_dbias=True):
     Co = dz.shape[1]
     if tuple(dz.shape[2:]) != ((H - 1) // stride + 1, (W - 1) // stride + 1):
         raise ValueError("stem_conv3x3_wgrad: dz does not have the convolution's output size")
-    xc, dc = _stem_aligned(x), _stem_aligned(dz)
+    xc, dc = _aligned(x), _aligned(dz)
     dw = torch.empty(Co, Cin, 3, 3, dtype=torch.float32, device=x.device)
     db = torch.empty(Co, dtype=torch.float32, device=x.device) if need_dbias else None
     ws_bytes = int(L.mvi_stem_conv3x3_wgrad_workspace_bytes(N, Cin, Co, H, W, int(stride)))
@@ -1151,7 +1142,7 @@ def stem_conv3x3_dgrad(dz, weight):
             _check(L.mvi_stem_conv3x3_pack(wt.data_ptr(), packed.data_ptr(), C_, C_, int(W), 1, _DT[w.dtype], _stream(w.device)), "stem_conv3x3_pack")
         return packed
     wp = pack(weight) if weight.requires_grad else derived1(("stem_packed_transposed", 1), weight, pack)
-    dc = _stem_aligned(dz)
+    dc = _aligned(dz)
     dx = torch.empty_like(dc)
     with torch.cuda.device(dz.device), _Timed("stem_conv_dgrad", 2.0 * dz.numel() * dz.element_size(), dz.device):
         _check(L.mvi_stem_conv3x3_silu(dc.data_ptr(), wp.data_ptr(), None, dx.data_ptr(), N, C_, C_, H, W, 1, 0, _DT.get(dz.dtype, -1),
