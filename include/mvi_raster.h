@@ -219,6 +219,23 @@ int mvi_raster_lift_weights(const mvi_raster_settings* s, int32_t P, int64_t num
                             const void* image, const float* weights, int32_t channels, float* acc, int32_t acc_stride,
                             void* stream);
 
+/* Feature splat: the transpose of the lift. Up to eight per-Gaussian feature channels composited into the view of a finished
+ * forward (any of the forward_render entries; before or after its backward), over exactly the (pixel, Gaussian) pairs that
+ * forward composited, with its weights:
+ *     out[c][p] = sum_i alpha_i(p) T_i(p) features[i][c]
+ * features [P][feat_stride] fp32, read at columns 0..channels-1 with 4-byte loads (any row stride >= channels, any 4-byte
+ * alignment: a column range of the lift's rows goes in as it is); any values. channels is 1..8. out [channels][H][W] fp32: every
+ * element is WRITTEN (a pixel nothing reaches gets 0), nobody has to zero it; there is no background term. One fma per channel and
+ * composited entry in list order, front to back: with the colours of a colors_precomp forward as features and a zero background,
+ * out is that forward's colour image bit for bit. Reads xy, conic_opacity, the point list, the tile ranges and n_contrib; reads
+ * neither final_T nor colours (pending deferred colours do not matter) and writes nothing but out: the accumulation rows, the
+ * gradient support and the tile queues of a backward are untouched. No atomics: the same inputs give the same bits. Its gradient
+ * with respect to features is mvi_raster_lift_weights on dL/dout (slots 1..channels). P == 0, num_rendered == 0 or an empty
+ * image: returns 0, nothing launched, out untouched. */
+int mvi_raster_splat_features(const mvi_raster_settings* s, int32_t P, int64_t num_rendered, const void* geom, const void* binning,
+                              const void* image, const float* features, int32_t channels, int32_t feat_stride, float* out,
+                              void* stream);
+
 /* mvi_raster_backward_geom for the Gaussians [first, first + count) only (any first row): every pointer is the
  * base of the FULL [P, ...] array, as in mvi_raster_backward_geom; only rows of the range are read and written. Lets a
  * view-parallel trainer run the chain rule in a few ranges and start the all-reduce of a finished range's gradients

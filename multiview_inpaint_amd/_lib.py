@@ -111,6 +111,8 @@ def lib():
     L.mvi_raster_backward_depth_to_means.argtypes = [C.POINTER(RasterSettings), i32, vp, vp, vp]
     L.mvi_raster_lift_weights.restype = C.c_int
     L.mvi_raster_lift_weights.argtypes = [C.POINTER(RasterSettings), i32, i64, vp, vp, vp, vp, i32, vp, i32, vp]
+    L.mvi_raster_splat_features.restype = C.c_int
+    L.mvi_raster_splat_features.argtypes = [C.POINTER(RasterSettings), i32, i64, vp, vp, vp, vp, i32, i32, vp, vp]
     L.mvi_raster_backward.restype = C.c_int
     L.mvi_raster_backward.argtypes = [C.POINTER(RasterSettings), i32, i32, i64] + [vp] * 20 + [i32, vp]
     L.mvi_raster_backward_render.restype = C.c_int

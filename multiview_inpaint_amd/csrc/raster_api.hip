@@ -529,6 +529,26 @@ int mvi_raster_lift_weights(const mvi_raster_settings* s, int32_t P, int64_t D, 
     return MVI_OK;
 }
 
+int mvi_raster_splat_features(const mvi_raster_settings* s, int32_t P, int64_t D, const void* geom, const void* binning,
+                              const void* image, const float* features, int32_t channels, int32_t feat_stride, float* out,
+                              void* stream) {
+    mvi::Frame f;
+    if (int rc = make_frame(s, P, 0, f)) return rc;
+    if (channels < 1 || channels > 8) return fail(MVI_EINVAL, "splat_features: channels must be 1..8%s (got %lld)", "", channels);
+    if (feat_stride < channels)
+        return fail(MVI_EINVAL, "splat_features: feat_stride %s%lld is below channels = %lld", "", feat_stride, channels);
+    if (!features) return fail(MVI_EINVAL, "splat_features: features is NULL%s");
+    if (D < 0 || D > 0xFFFFFFFFll) return fail(MVI_EINVAL, "num_rendered out of range%s: %lld", "", D);
+    if (P == 0 || D == 0 || f.W == 0 || f.H == 0) return MVI_OK;              // nothing was composited: out is left alone
+    if (!geom || !binning || !image || !out) return fail(MVI_EINVAL, "NULL geom/binning/image/out in splat_features%s");
+    mvi::GeomView g = mvi::carve_geom(const_cast<void*>(geom), P);
+    mvi::ImageView im = mvi::carve_image(const_cast<void*>(image), f.W, f.H);
+    mvi::BinningView b = mvi::carve_binning(const_cast<void*>(binning), D, f.W, f.H);
+    if (mvi::launch_splat_features(f, g, b, im, D, features, channels, feat_stride, out, (hipStream_t)stream))
+        return hip_fail("splat_features", hipGetLastError());
+    return MVI_OK;
+}
+
 static int backward_geom_range_impl(const mvi_raster_settings* s, int32_t P, int32_t M, int32_t first, int32_t count,
                                     const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
                                     const float* rotations, const float* cov3D_precomp, const int32_t* radii, const void* geom,

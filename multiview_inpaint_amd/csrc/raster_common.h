@@ -614,6 +614,9 @@ int launch_depth_to_means(const Frame& f, const float* grad_rows, float* dL_dmea
 // raster_lift.hip: acc[id][0] += sum alpha T, acc[id][1 + c] += sum alpha T weights[c] over the pairs the forward composited
 int launch_lift_weights(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, const float* weights, int channels,
                         float* acc, int acc_stride, hipStream_t st);
+// raster_splat.hip: out[c][p] = sum alpha T features[id][c] over the pairs the forward composited (the lift's transpose)
+int launch_splat_features(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, const float* features, int channels,
+                          int feat_stride, float* out, hipStream_t st);
 int launch_resolve_colors(const Frame& f, GeomView g, hipStream_t st);      // evaluates every colour still pending
 // fills g.depths, g.cov_a / g.cov_b and g.tiles_touched, which the forward leaves unwritten, from the forward's inputs
 int launch_materialize_geom_views(const Frame& f, const float* means3D, const float* scales, const float* rotations,

@@ -10,6 +10,15 @@ themselves say which Gaussians are the object, by a vote weighted with what ever
 over exactly the (pixel, Gaussian) pairs the forward composites (raster.lift_weights, csrc/raster_lift.hip). A Gaussian belongs
 to mask c when hit / total exceeds a ratio; `total` alone is the visibility / importance score that pruning schemes use.
 Building cameras from a dataset stays the caller's job: a view is (GaussianRasterizationSettings, weights).
+
+The other direction carries a selection of Gaussians (or any per-Gaussian weights) into a view:
+
+    soft_c(p) = sum_i alpha_i(p) T_i(p) m_i,c                             (raster.splat_features, csrc/raster_splat.hip)
+
+the transpose of the vote, over the same (pixel, Gaussian) pairs. Its use: hint masks for views that have no 2-D mask. The views
+the SVD stage inpaints are synthesised sequence and orbit cameras (gs-simp/gen_seq.py, scene/__init__.py:129-255); the reference
+gets their hint mask from the hand-made box mesh (gen_seq.py:47-54, box_region here). With project_selection a selection made
+from masks serves instead, and propagate_masks is the whole way in one call: masks in some views -> selection -> masks in any view.
 """
 import numpy as np
 import torch
@@ -37,6 +46,62 @@ def select(acc, channel=0, ratio=0.5, min_total=0.0):
         raise ValueError(f"select: acc must be [P, 1 + C] with channel < C, got {tuple(acc.shape)} and channel {channel}")
     total = acc[:, 0]
     return (total > min_total) & (acc[:, 1 + channel] > ratio * total)
+
+
+def _selection_features(selection, normalize):
+    """selection [P] | [P, K], bool or float -> (fp32 [P, K (+ 1)] features, K); with normalize a column of ones rides along."""
+    if not torch.is_tensor(selection) or selection.ndim not in (1, 2) or (selection.ndim == 2 and selection.shape[1] < 1):
+        raise ValueError("project_selection: selection must be a [P] or [P, K] tensor with K >= 1, got "
+                         f"{tuple(selection.shape) if torch.is_tensor(selection) else type(selection).__name__}")
+    if selection.dtype != torch.bool and not selection.dtype.is_floating_point:
+        raise TypeError(f"project_selection: selection must be bool or floating point, got {selection.dtype}")
+    m = selection.to(torch.float32)
+    if m.ndim == 1:
+        m = m[:, None]
+    K = int(m.shape[1])
+    if normalize:
+        m = torch.cat([m, torch.ones_like(m[:, :1])], dim=1)
+    return m, K
+
+
+def normalize_soft_masks(soft, alpha):
+    """soft [K,H,W] / alpha [H,W] where alpha > 0, 0 elsewhere: the share of a pixel's composited weight the selection owns.
+    Pure torch; works on CPU tensors too."""
+    if soft.ndim != 3 or alpha.ndim != 2 or tuple(soft.shape[1:]) != tuple(alpha.shape):
+        raise ValueError(f"normalize_soft_masks: soft must be [K,H,W] and alpha [H,W], got {tuple(soft.shape)} and {tuple(alpha.shape)}")
+    pos = alpha > 0
+    return torch.where(pos[None], soft / torch.where(pos, alpha, torch.ones_like(alpha))[None], torch.zeros_like(soft))
+
+
+def project_selection(selection, views, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None, normalize=False):
+    """Soft masks of a selection of Gaussians in `views`, an iterable of GaussianRasterizationSettings: a list of fp32 [K,H,W]
+    images sum_i alpha_i(p) T_i(p) m_i,k (raster.GaussianRasterizer.splat), one per view. selection: [P] or [P, K], bool
+    (membership) or float (soft weights), on the Gaussians' device. normalize: every mask is divided by the view's alpha image
+    sum alpha T (a column of ones splatted as one more channel) where that is > 0 and is 0 elsewhere: the share of the pixel's
+    composited weight that the selection owns, in [0, 1] for weights in [0, 1]."""
+    m, K = _selection_features(selection, normalize)
+    P = int(means3D.reshape(-1, 3).shape[0])
+    if int(m.shape[0]) != P:
+        raise ValueError(f"project_selection: selection has {int(m.shape[0])} rows for {P} Gaussians")
+    m = m.to(means3D.device)
+    masks = []
+    for rs in views:
+        img = raster.GaussianRasterizer(rs).splat(m, means3D, opacities, scales=scales, rotations=rotations,
+                                                  cov3D_precomp=cov3D_precomp)
+        masks.append(normalize_soft_masks(img[:K], img[K]) if normalize else img)
+    return masks
+
+
+def propagate_masks(src_views, dst_views, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None, channel=0,
+                    ratio=0.5, min_total=0.0, normalize=False):
+    """Masks in some views -> selection -> masks in any view: lift_views over src_views (as in lift_views: (settings, weights)
+    pairs), select(channel, ratio, min_total), project_selection into dst_views (settings). Returns (selection bool [P], masks:
+    a list of fp32 [1,H,W], one per destination view)."""
+    acc = lift_views(src_views, means3D, opacities, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+    selection = select(acc, channel, ratio, min_total)
+    masks = project_selection(selection, dst_views, means3D, opacities, scales=scales, rotations=rotations,
+                              cov3D_precomp=cov3D_precomp, normalize=normalize)
+    return selection, masks
 
 
 def delete_by_masks(ply_in, ply_out, views, ratio=0.5, min_total=0.0, device="cuda"):

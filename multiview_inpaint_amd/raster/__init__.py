@@ -436,6 +436,83 @@ def lift_weights(st: RasterState, weights=None, acc=None) -> torch.Tensor:
     return acc
 
 
+SPLAT_MAX_CHANNELS = 8         # channels of one launch: eight sums per pixel in registers; more run as chunks of eight
+
+
+def _splat_launch(st, f2d, out):
+    """One launch per chunk of SPLAT_MAX_CHANNELS columns of f2d [P, C] (unit inner stride) into the planes of out [C, H, W]."""
+    L = _lib.lib()
+    dev = st.geom.device
+    stride = int(f2d.stride(0)) if st.P > 1 else int(f2d.shape[1])
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        for c0 in range(0, int(f2d.shape[1]), SPLAT_MAX_CHANNELS):
+            c = min(SPLAT_MAX_CHANNELS, int(f2d.shape[1]) - c0)
+            _lib.check(L.mvi_raster_splat_features(C.byref(st.frame.c), st.P, st.D, _ptr(st.geom), _ptr(st.binning), _ptr(st.image),
+                                                   _ptr(f2d[:, c0:]), c, stride, _ptr(out[c0:]), stream), "splat_features")
+
+
+class _SplatFeatures(torch.autograd.Function):
+    """splat_features under autograd: differentiable in the features only (the geometry is a finished, detached forward); the
+    backward is the lift of the image gradient, SPLAT_MAX_CHANNELS planes per launch."""
+
+    @staticmethod
+    def forward(ctx, features, st):
+        ctx.st, ctx.shape = st, features.shape
+        return splat_features(st, features.detach())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        st = ctx.st
+        g = grad_out.detach().to(torch.float32).contiguous()
+        Cn = int(g.shape[0])
+        parts = [lift_weights(st, g[c0:c0 + SPLAT_MAX_CHANNELS])[:, 1:1 + min(SPLAT_MAX_CHANNELS, Cn - c0)]
+                 for c0 in range(0, Cn, SPLAT_MAX_CHANNELS)]
+        grad = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        return grad.reshape(ctx.shape), None
+
+
+def splat_features(st: RasterState, features, out=None) -> torch.Tensor:
+    """Per-Gaussian features composited into the view of the forward that left `st` behind (any forward: no-grad,
+    prepare_backward, aux; before or after its backward), the transpose of lift_weights:
+        out[c, p] = sum_i alpha_i(p) T_i(p) features[i, c]
+    over exactly the (pixel, Gaussian) pairs that forward composited; no background term. features: CUDA fp32 [P, C] or [P]
+    (C = 1), any values, any C >= 1 (more than 8 channels run as chunks of 8 over the same state). A tensor with unit inner
+    stride and a row stride >= C is read in place (lift_weights(...)[:, 1:] goes in as it is); anything else is made
+    contiguous. Returns fp32 [C, H, W], every element written; out: a contiguous fp32 [C, H, W] tensor on the state's device to
+    write into. With the colours of a colors_precomp forward as features and a zero background the result is that forward's
+    colour image bit for bit. Differentiable in `features` (the backward is lift_weights of the image gradient); nothing else
+    receives a gradient, and out= cannot be combined with a differentiable call."""
+    if not torch.is_tensor(features) or not features.is_cuda:
+        raise RuntimeError("splat_features: features must be a CUDA tensor; the rasterizer has no CPU path")
+    dev = st.geom.device
+    if features.dtype != torch.float32:
+        raise TypeError(f"splat_features: features must be float32, got {features.dtype}")
+    if features.device != dev:
+        raise RuntimeError(f"splat_features: features are on {features.device}, the forward ran on {dev}")
+    if features.ndim not in (1, 2) or int(features.shape[0]) != st.P or (features.ndim == 2 and features.shape[1] < 1):
+        raise ValueError(f"splat_features: features must be [{st.P}, C] with C >= 1 or [{st.P}], got {tuple(features.shape)}")
+    Cn = 1 if features.ndim == 1 else int(features.shape[1])
+    if features.requires_grad and torch.is_grad_enabled():
+        if out is not None:
+            raise ValueError("splat_features: out= cannot be combined with features that require a gradient")
+        return _SplatFeatures.apply(features, st)
+    if out is None:
+        out = torch.empty(Cn, st.H, st.W, dtype=torch.float32, device=dev)
+    elif (not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (Cn, st.H, st.W) or
+          not out.is_contiguous()):
+        raise ValueError(f"splat_features: out must be a contiguous fp32 [{Cn}, {st.H}, {st.W}] tensor on {dev}")
+    if st.P == 0 or st.D == 0 or st.W == 0 or st.H == 0:
+        return out.zero_()
+    f2d = features.detach()
+    if f2d.ndim == 1:
+        f2d = f2d[:, None]
+    if f2d.stride(1) != 1 or (st.P > 1 and f2d.stride(0) < Cn):
+        f2d = f2d.contiguous()
+    _splat_launch(st, f2d, out)
+    return out
+
+
 def sh_backward_views(means3D, campos, color_factors, M, sh_degree, out=None):
     """Sum over views of the SH gradient rebuilt from per-view colour factors:
     out[g,k,c] = sum_v Y_k(normalize(means3D[g] - campos[v])) * color_factors[v,g,c]  ->  [P,M,3].
@@ -710,6 +787,19 @@ class GaussianRasterizer(torch.nn.Module):
                                             colors_precomp=torch.zeros_like(m3), scales=_opt(scales), rotations=_opt(rotations),
                                             cov3D_precomp=_opt(cov3D_precomp))
             return lift_weights(st, weights, acc)
+
+    def splat(self, features, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None):
+        """splat_features for callers that hold no RasterState: a no-grad forward of this view (zero precomputed colours — the
+        splat reads none) followed by the splat. features [P, C] | [P]; returns [C, H, W]. Differentiable in features only."""
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+            raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        with torch.no_grad():
+            m3 = _dev_f32(means3D, "means3D").reshape(-1, 3)
+            _, _, _, st = rasterize_forward(self.raster_settings, m3, _dev_f32(opacities, "opacities"),
+                                            colors_precomp=torch.zeros_like(m3), scales=_opt(scales), rotations=_opt(rotations),
+                                            cov3D_precomp=_opt(cov3D_precomp))
+        return splat_features(st, features)
 
     def forward_raw(self, xyz, means2D, features_dc, features_rest, raw_opacity, raw_scaling, raw_rotation):
         """The same render fed with the GaussianModel's parameter tensors as stored (_xyz, _features_dc, _features_rest,
