@@ -795,8 +795,8 @@ def _conv_taps_n320(kind, tok, weight_taps, bias, N, H, W, taps, stride=1, split
     full = torch.empty(cap, Co, dtype=tok.dtype, device=tok.device)
     b = None if bias is None else _f32(bias)
     # > 0: a small image, K split over several blocks per tile
-    ws_bytes = 0 if not split else int(L.mvi_conv3x3_n320_workspace_bytes(N, H, W, C, Co, stride) if taps == 9
-                                       else L.mvi_conv3t_n320_workspace_bytes(N, H, W, C, Co))
+    ws_bytes = 0 if not split or up2 else int(L.mvi_conv3x3_n320_workspace_bytes(N, H, W, C, Co, stride) if taps == 9
+                                              else L.mvi_conv3t_n320_workspace_bytes(N, H, W, C, Co))      # (the upsampling form never splits)
     ws = _workspace(tok.device, ws_bytes) if ws_bytes else None
     wsp = _ptr(ws)
     if gn is not None:
@@ -825,17 +825,38 @@ def _conv_taps_n320(kind, tok, weight_taps, bias, N, H, W, taps, stride=1, split
     return full[:rows]
 
 
-def conv3x3_n320_fills_chip(N, H, W, C_in, C_out, min_blocks, stride=1):
-    """Does a launch of this shape put at least min_blocks blocks on the chip (256 output pixels x 320 channels each, times the K
-    split small images get)?"""
+# The forms of the implicit-GEMM convolution launch: form -> (stride, whether csrc/linear_n320.hip K-splits it). "up2" (the convolution
+# of the nearest-2x upsampled image) and "s2_dgrad" (the zero-stuffed input gradient of the stride-2 form) are instantiations of their
+# own that never split (conv_taps_n320 sets cg.ksplit = 1 for them); "t3" is the (3,1,1) frame form with (N, H, W) = (B, T, S).
+_CONV_N320_FORMS = {"s1": (1, True), "s2": (2, True), "up2": (1, False), "s2_dgrad": (1, False), "t3": (1, True)}
+
+
+def conv_n320_launch_ok(form, N, H, W, C_in, C_out, dtype, min_blocks, ksplit_counts=None):
+    """Does csrc/linear_n320.hip take this convolution launch and fill the chip? THE routing gate of every caller in ops.py and layers.py.
+    N images of H x W pixels with C_in channels as the launch's wrapper is handed them — "up2": the SOURCE of the upsampled image;
+    "s2_dgrad": the full-size H x W image dx has, C_in the channels of dy; "t3": B videos of T frames of S pixels. True when
+      * the kernel's channel / dtype gate passes (mvi_conv3x3_n320_supported),
+      * there is at least one output row,
+      * the image the kernel addresses stays within 32-bit byte offsets (conv_taps_n320: N H W C_in 2 <= 0xFFFFFFFF, H x W doubled
+        for "up2"),
+      * its 256-row x 320-channel blocks number min_blocks or more, or the form K-splits and the library would split this shape
+        (its *_workspace_bytes is positive).
+    ksplit_counts overrides the form's own answer to "can it split" (one caller: layers.Upsample)."""
+    stride, splits = _CONV_N320_FORMS[form]
+    if not conv3x3_n320_supported(C_in, C_out, dtype):      # (first: the library's split policy divides by the block count)
+        return False
+    if form == "up2":
+        H, W = 2 * H, 2 * W
     rows = N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1)
-    blocks = -(-rows // 256) * (C_out // 320)
-    return blocks >= min_blocks or int(_lib.lib().mvi_conv3x3_n320_workspace_bytes(N, H, W, C_in, C_out, stride)) > 0
-
-
-def conv3t_n320_fills_chip(B, T, S, C_in, C_out, min_blocks):
-    blocks = -(-B * T * S // 256) * (C_out // 320)
-    return blocks >= min_blocks or int(_lib.lib().mvi_conv3t_n320_workspace_bytes(B, T, S, C_in, C_out)) > 0
+    if rows <= 0 or N * H * W * C_in * 2 > 0xFFFFFFFF:
+        return False
+    if -(-rows // 256) * (C_out // 320) >= min_blocks:
+        return True
+    if not (splits if ksplit_counts is None else ksplit_counts):
+        return False
+    L = _lib.lib()
+    return int(L.mvi_conv3t_n320_workspace_bytes(N, H, W, C_in, C_out) if form == "t3"
+               else L.mvi_conv3x3_n320_workspace_bytes(N, H, W, C_in, C_out, stride)) > 0
 
 
 def conv3x3_n320(tok, weight_taps, bias, H, W, stride=1, split=True, gn=None, up2=False, kind="conv3x3_n320"):
@@ -853,7 +874,7 @@ def conv3x3_n320(tok, weight_taps, bias, H, W, stride=1, split=True, gn=None, up
     return r.view(N, -1, weight_taps.shape[0])
 
 
-# ---- the 3x3 convolution under autograd (ops._Conv3x3TokensFn): dgrad on the forward kernel, wgrad in csrc/conv3x3_wgrad.hip ----------
+# ---- the 3x3 convolution under autograd (ops._ConvTokensFn "s1"): dgrad on the forward kernel, wgrad in csrc/conv3x3_wgrad.hip ---------
 
 CONV3X3_WGRAD_MAX_W = 256                       # csrc/conv3x3_wgrad.hip: the x chunk with its two halo rows has to fit in LDS
 
@@ -904,7 +925,7 @@ def conv3x3_wgrad(tok, dy_tok, H, W, split=True):
                        "conv3x3_wgrad", 2.0 * N * S * 9 * C * Co, split)
 
 
-# ---- the stride-2 and the upsampling 3x3 convolution under autograd (ops._Conv3x3DownTokensFn / _Conv3x3UpTokensFn) ---------------------
+# ---- the stride-2 and the upsampling 3x3 convolution under autograd (ops._ConvTokensFn "s2" / "up2") ------------------------------------
 
 def conv3x3_s2_dgrad_supported(C_in, C_out, dtype):
     return dtype in (torch.bfloat16, torch.float16) and bool(_lib.lib().mvi_conv3x3_s2_dgrad_supported(int(C_in), int(C_out), _DT[dtype]))
@@ -969,6 +990,12 @@ def pool2x2_sum(g_tok, h, w):
     return out
 
 
+def conv3x3_up2_dgrad(dy_tok, weight_t_taps, h, w):
+    """dx [N, h w, C_in] of the convolution of the nearest-2x upsampled h x w image from dy [N, (2 h)(2 w), C_out]: conv3x3_dgrad at
+    2 h x 2 w, then pool2x2_sum."""
+    return pool2x2_sum(conv3x3_dgrad(dy_tok, weight_t_taps, 2 * h, 2 * w), h, w)
+
+
 def conv3t_n320(tok, weight_taps, bias, T, split=True, gn=None, kind="conv3t_n320"):
     """(3, 1, 1) / padding (1, 0, 0) convolution over the frame axis of token-major activations tok [(b T), S, C_in] (frames of a video
     consecutive) -> [(b T), S, C_out]; weight_taps from conv3t_n320_weight. gn: as conv3x3_n320 (a sample = a frame).
@@ -982,7 +1009,7 @@ def conv3t_n320(tok, weight_taps, bias, T, split=True, gn=None, kind="conv3t_n32
     return r.view(BT, S, -1)
 
 
-# ---- the (3,1,1) frame convolution under autograd (ops._Conv3tTokensFn): dgrad on the forward kernel, wgrad in csrc/conv3t_wgrad.hip ----
+# ---- the (3,1,1) frame convolution under autograd (ops._ConvTokensFn "t3"): dgrad on the forward kernel, wgrad in csrc/conv3t_wgrad.hip --
 
 CONV3T_WGRAD_CHUNK = 64                         # csrc/conv3t_wgrad.hip (kKc): pixels of one video a block stages per frame
 

@@ -271,7 +271,12 @@ class Upsample(nn.Module):
         s = self.scale_factor
         if isinstance(x, Tok):
             N, C, H, W = x.shape
-            if self.dims != 3 and s == 2 and self.use_conv and _conv_n320_route_ok(self.conv, N, C, 2 * H, 2 * W, x.dtype):
+            # ksplit_counts=True: this gate admits shapes whose blocks alone do not reach the line but which the stride-1 launch at
+            # 2 H x 2 W would K-split — although the upsampling launch never splits. N = 1, source 6x8, 1280 -> 1280: 4 blocks, a positive
+            # mvi_conv3x3_n320_workspace_bytes, so an unsplit 4-block launch runs here where ops.conv3x3_up_tokens refuses. Whether
+            # such shapes should go to the kernel is a speed question nobody has measured.
+            if self.dims != 3 and s == 2 and self.use_conv and _conv_n320_route_ok(self.conv, N, C, H, W, x.dtype, form="up2",
+                                                                                   ksplit_counts=True):
                 from . import hip_ops                   # (the upsampling is in the kernel's addressing: no 4x tensor)
                 return Tok(hip_ops.conv3x3_n320(x.t, _tap_major_weight(self.conv.weight), self.conv.bias, H, W, up2=True), 2 * H, 2 * W)
             return to_tok(self.forward(x.planes()))
@@ -594,14 +599,16 @@ CONV_N320_MIN_BLOCKS = 128         # fewer blocks of 256 rows x 320 channels tha
                                    # then (level 3: 64 blocks x 4), or, for a K too short to split, the library runs
 
 
-def _tap_major_weight(w):
-    """A convolution weight in csrc/linear_n320.hip's implicit-GEMM order, [C_out][taps C_in] tap-major — 3x3 Conv2d weights
-    ([C_out, C_in, 3, 3] -> 9 taps) and (3,1,1) Conv3d weights ([C_out, C_in, 3, 1, 1] -> 3 taps) — once per parameter version."""
-    from . import hip_ops
-    if w.dim() == 5:
-        return derived1("tap_major", w, lambda w: hip_ops.conv3t_n320_weight(w.detach()))
-    # the packing order of the 3x3 weights is a process-global switch of the kernel: part of the signature (hip_ops.conv3x3_k_order)
-    return derived1("tap_major", w, lambda w: hip_ops.conv3x3_n320_weight(w.detach()), hip_ops.conv3x3_k_order())
+_tap_major_weight = ops.conv_packed_weight         # the weight in csrc/linear_n320.hip's implicit-GEMM order, once per parameter version
+
+
+def _plain_conv3x3(conv, dtype, strides=(1,)):
+    """Is conv an nn.Conv2d with a weight of this dtype, kernel 3x3, a stride (the same on both axes) among `strides`, padding 1,
+    dilation 1, groups 1 — the convolution every token-major route of this file computes? (No SVD network has a dilated or grouped
+    3x3 convolution; the test keeps one from being mis-computed should a caller bring it.)"""
+    return (isinstance(conv, nn.Conv2d) and conv.weight.dtype == dtype and tuple(conv.kernel_size) == (3, 3)
+            and conv.stride[0] == conv.stride[1] and conv.stride[0] in strides and tuple(conv.padding) == (1, 1)
+            and tuple(conv.dilation) == (1, 1) and conv.groups == 1)
 
 
 def conv3x3_planes_via_tokens(conv, x, upsample=1, tokens_out=False):
@@ -611,9 +618,7 @@ def conv3x3_planes_via_tokens(conv, x, upsample=1, tokens_out=False):
     on the GPU outside autograd, a shape the kernel takes (C_out = 320 g, C_in = 64 k), enough output pixels to fill the chip (or a K
     long enough to split). Used by Upsample, Downsample and the last convolution of the ControlNet hint stem."""
     if not (CONV_N320 and NHWC_CONVS and x.is_cuda and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float16)
-            and not torch.is_grad_enabled() and isinstance(conv, nn.Conv2d) and conv.weight.dtype == x.dtype
-            and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) in ((1, 1), (2, 2)) and tuple(conv.padding) == (1, 1)
-            and tuple(conv.dilation) == (1, 1) and conv.groups == 1):
+            and not torch.is_grad_enabled() and _plain_conv3x3(conv, x.dtype, (1, 2))):
         return None
     from . import hip_ops
     N, C, H, W = x.shape
@@ -628,20 +633,19 @@ def conv3x3_planes_via_tokens(conv, x, upsample=1, tokens_out=False):
     return hip_ops.tokens_to_planes_add(t, None, spatial=(Ho, Wo))
 
 
-def _conv_n320_shape_ok(conv, N, C, Hi, Wi, dtype):
+def _conv_n320_shape_ok(conv, N, C, Hi, Wi, dtype, form=None, ksplit_counts=None):
     """A 3x3 / padding 1 convolution of stride 1 or 2 over N images of Hi x Wi tokens with C channels: the shapes csrc/linear_n320.hip takes
-    and enough output pixels to fill the chip."""
+    and enough output pixels to fill the chip (hip_ops.conv_n320_launch_ok; C a multiple of 8 for the layout passes: implied by its
+    multiple of 64). form: the launch, where it is not the plain one of conv's stride."""
     from . import hip_ops
-    return (C % 8 == 0 and hip_ops.conv3x3_n320_supported(C, conv.out_channels, dtype) and N * Hi * Wi * C * 2 < 2 ** 32
-            and hip_ops.conv3x3_n320_fills_chip(N, Hi, Wi, C, conv.out_channels, CONV_N320_MIN_BLOCKS, stride=conv.stride[0]))
+    return hip_ops.conv_n320_launch_ok(form or ("s2" if conv.stride[0] == 2 else "s1"), N, Hi, Wi, C, conv.out_channels, dtype,
+                                       CONV_N320_MIN_BLOCKS, ksplit_counts)
 
 
-def _conv_n320_route_ok(conv, N, C, Hi, Wi, dtype):
+def _conv_n320_route_ok(conv, N, C, Hi, Wi, dtype, **launch):
     """conv3x3_planes_via_tokens' conditions for a token-major input (Tok) of N x (Hi Wi) x C."""
     return (CONV_N320 and NHWC_CONVS and dtype in (torch.bfloat16, torch.float16) and not torch.is_grad_enabled()
-            and isinstance(conv, nn.Conv2d) and conv.weight.dtype == dtype and tuple(conv.kernel_size) == (3, 3)
-            and tuple(conv.stride) in ((1, 1), (2, 2)) and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1)
-            and conv.groups == 1 and _conv_n320_shape_ok(conv, N, C, Hi, Wi, dtype))
+            and _plain_conv3x3(conv, dtype, (1, 2)) and _conv_n320_shape_ok(conv, N, C, Hi, Wi, dtype, **launch))
 
 
 TIME_STACK_TOKENS = os.environ.get("MVI_SVD_TIME_STACK_TOKENS", "1") != "0"
@@ -660,8 +664,7 @@ def _conv_tokens(conv, tok, H, W, gn=None):
     N, S, C = tok.shape
     if CONV_N320:
         from . import hip_ops
-        if (hip_ops.conv3x3_n320_supported(C, conv.out_channels, tok.dtype) and N * S * C * 2 < 2 ** 32
-                and hip_ops.conv3x3_n320_fills_chip(N, H, W, C, conv.out_channels, CONV_N320_MIN_BLOCKS)):
+        if hip_ops.conv_n320_launch_ok("s1", N, H, W, C, conv.out_channels, tok.dtype, CONV_N320_MIN_BLOCKS):
             if gn is not None and GN_STATS_FROM_CONV and hip_ops.conv_n320_gnstats_supported(N * S, 9, C, conv.out_channels, S, gn[0]):
                 return hip_ops.conv3x3_n320(tok, _tap_major_weight(conv.weight), None, H, W, gn=gn)
             y = hip_ops.conv3x3_n320(tok, _tap_major_weight(conv.weight), None, H, W)
@@ -677,9 +680,7 @@ def _conv_tokens(conv, tok, H, W, gn=None):
 def _nhwc_path_ok(self, x):
     conv1, conv2 = self.in_layers[2], self.out_layers[3]
     return (NHWC_CONVS and x.is_cuda and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float16) and not torch.is_grad_enabled()
-            and isinstance(conv1, nn.Conv2d) and isinstance(conv2, nn.Conv2d) and conv1.weight.dtype == x.dtype
-            and all(tuple(c.kernel_size) == (3, 3) and tuple(c.stride) == (1, 1) and tuple(c.padding) == (1, 1) and c.groups == 1
-                    for c in (conv1, conv2))
+            and _plain_conv3x3(conv1, x.dtype) and _plain_conv3x3(conv2, x.dtype)
             and x.shape[1] % 8 == 0 and conv1.out_channels % 8 == 0 and conv2.out_channels % 8 == 0 and (x.shape[2] * x.shape[3]) % 8 == 0
             and _tok2tok_ok(x.shape[0], conv1.out_channels, x.shape[2] * x.shape[3], self.out_layers[0].num_groups, x.dtype))
 
@@ -717,9 +718,7 @@ def _resample_conv_bwd_ok(conv, x, up):
     """Under autograd: does this Downsample.op (up = False) / Upsample.conv (up = True) pass the conditions of its ops.conv3x3_*_tokens
     (switches, the kernels' gates, the speed decision; the upsampling form only with a frozen convolution)?"""
     if not (RESAMPLE_CONV_BWD and ops.RESAMPLE_CONV_BACKWARD and torch.is_grad_enabled() and x.is_cuda and x.dim() == 4
-            and x.dtype in (torch.bfloat16, torch.float16) and isinstance(conv, nn.Conv2d) and conv.weight.dtype == x.dtype
-            and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == ((1, 1) if up else (2, 2)) and tuple(conv.padding) == (1, 1)
-            and tuple(conv.dilation) == (1, 1) and conv.groups == 1):
+            and x.dtype in (torch.bfloat16, torch.float16) and _plain_conv3x3(conv, x.dtype, (1,) if up else (2,))):
         return False
     trains = any(p.requires_grad for p in conv.parameters())
     if not (x.requires_grad or trains):
@@ -739,10 +738,7 @@ def _conv_bwd_path_ok(self, x, emb):
     speed decision)?"""
     conv1, conv2 = self.in_layers[2], self.out_layers[3]
     if not (RESBLOCK_CONV_BWD and ops.CONV3X3_BACKWARD and torch.is_grad_enabled() and x.is_cuda and x.dim() == 4
-            and x.dtype in (torch.bfloat16, torch.float16) and isinstance(conv1, nn.Conv2d) and isinstance(conv2, nn.Conv2d)
-            and conv1.weight.dtype == x.dtype and conv2.weight.dtype == x.dtype
-            and all(tuple(c.kernel_size) == (3, 3) and tuple(c.stride) == (1, 1) and tuple(c.padding) == (1, 1)
-                    and tuple(c.dilation) == (1, 1) and c.groups == 1 for c in (conv1, conv2))
+            and x.dtype in (torch.bfloat16, torch.float16) and _plain_conv3x3(conv1, x.dtype) and _plain_conv3x3(conv2, x.dtype)
             and x.shape[1] % 8 == 0 and conv1.out_channels % 8 == 0 and (x.shape[2] * x.shape[3]) % 8 == 0):
         return False
     if not (x.requires_grad or emb.requires_grad or any(p.requires_grad for p in self.parameters())):
@@ -927,9 +923,8 @@ class VideoResBlock(ResBlock):
         bt, c, h, w = x.shape
         co = self.out_channels
         return (bt % t == 0 and c1.weight.dtype == x.dtype and c1.in_channels == co and c1.out_channels == co and c2.out_channels == co
-                and hip_ops.conv3x3_n320_supported(co, co, x.dtype) and bt * h * w * co * 2 < 2 ** 32
-                and _tok2tok_ok(bt, co, h * w, ts.in_layers[0].num_groups, x.dtype)
-                and hip_ops.conv3t_n320_fills_chip(bt // t, t, h * w, co, co, CONV_N320_MIN_BLOCKS))
+                and hip_ops.conv_n320_launch_ok("t3", bt // t, t, h * w, co, co, x.dtype, CONV_N320_MIN_BLOCKS)
+                and _tok2tok_ok(bt, co, h * w, ts.in_layers[0].num_groups, x.dtype))
 
     def _time_stack_tokens(self, xt, emb, T, blend, hw, stats_in=None, tokens_out=False):
         """_time_stack_frames on token-major xt [(b T), S, c] (the spatial ResBlock's output as tokens): temporal GroupNorm + SiLU with

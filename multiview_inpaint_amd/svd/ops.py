@@ -16,7 +16,13 @@ The 3x3 convolution of token-major activations has a HIP backward too (`conv3x3_
 implicit-GEMM kernel with the transposed weight, the weight gradient on csrc/conv3x3_wgrad.hip), where `conv3x3_backward_pays` says
 so; the ResBlock reaches it through the opt-in layers.RESBLOCK_CONV_BWD. So has the (3,1,1) frame convolution of the temporal
 ResBlocks (`conv3t_tokens`: the same kernel's three-tap form for forward and input gradient, csrc/conv3t_wgrad.hip for the weight
-gradient), where `conv3t_backward_pays` says so; VideoResBlock reaches it through the opt-in layers.TIME_STACK_CONV_BWD.
+gradient), where `conv3t_backward_pays` says so; VideoResBlock reaches it through the opt-in layers.TIME_STACK_CONV_BWD. And so have the
+resampling forms (`conv3x3_down_tokens`: the zero-stuffed input gradient on the forward kernel, the stride-2 form of the weight-gradient
+kernel; `conv3x3_up_tokens` with a frozen convolution: the stride-1 input gradient at the upsampled size + csrc/token_rows.hip's 2x2 sum),
+where `conv3x3_down_backward_pays` / `conv3x3_up_backward_pays` say so; Downsample / Upsample reach them through the opt-in
+layers.RESAMPLE_CONV_BWD. These four are forms of one op and share their plumbing: hip_ops.conv_n320_launch_ok is the one "does the kernel
+take this launch?" gate (each `*_tokens_gates` is calls of it plus the weight-gradient kernel's own test), `_ConvTokensFn` the one
+autograd.Function, `_conv_tokens_route` the one triage, `conv_packed_weight` / `conv_packed_weight_transposed` the one pair of cached weights.
 The 16- / 32-channel conv + SiLU layers of the ControlNet hint stem have one as well (`stem_conv3x3_silu`: dz on csrc/stem_conv.hip's second
 epilogue, weight / bias gradient on csrc/stem_conv_bwd.hip), where `stem_conv_backward_pays` says so; ControlNet._hint_stem reaches it
 through the opt-in unet.HINT_STEM_BWD.
@@ -34,6 +40,7 @@ Reference ops: GroupNorm32 + SiLU (sgm/modules/diffusionmodules/util.py:259-276,
 openaimodel.py:257-261,292-305), Normalize (sgm/modules/attention.py:125-128),
 softmax(QK^T d^-1/2)V (sgm/modules/attention.py:332-336, :427-439).
 """
+import collections
 import os
 
 import torch
@@ -1252,84 +1259,15 @@ def conv3x3_backward_pays(N, H, W, C_in, C_out, dtype, need_dweight):
 
 
 def conv3x3_tokens_gates(N, H, W, C_in, C_out, dtype):
-    """Do the three launches of _Conv3x3TokensFn take this shape? The forward's conditions (layers._conv_tokens: the kernel's channel
-    gate, 32-bit byte offsets, enough blocks or a K split), the same with the channel roles swapped for the input gradient, and
-    csrc/conv3x3_wgrad.hip's gate."""
+    """Do the three launches of the "s1" form under autograd take this shape? The forward's launch gate (hip_ops.conv_n320_launch_ok: the
+    kernel's channel gate, 32-bit byte offsets, enough blocks or a K split), the same with the channel roles swapped for the input
+    gradient, and csrc/conv3x3_wgrad.hip's gate."""
     from . import hip_ops
-    rows = N * H * W
-    return (dtype in (torch.bfloat16, torch.float16) and rows > 0
-            and hip_ops.conv3x3_n320_supported(C_in, C_out, dtype) and hip_ops.conv3x3_n320_supported(C_out, C_in, dtype)
-            and rows * max(C_in, C_out) * 2 < 2 ** 32
-            and hip_ops.conv3x3_n320_fills_chip(N, H, W, C_in, C_out, CONV3X3_MIN_BLOCKS)
-            and hip_ops.conv3x3_n320_fills_chip(N, H, W, C_out, C_in, CONV3X3_MIN_BLOCKS)
+    ok, mb = hip_ops.conv_n320_launch_ok, CONV3X3_MIN_BLOCKS
+    # (the two byte bounds, rows C_in 2 and rows C_out 2 within 32 bits, are together rows max(C_in, C_out) 2 < 2^32)
+    return (ok("s1", N, H, W, C_in, C_out, dtype, mb) and ok("s1", N, H, W, C_out, C_in, dtype, mb)
             and hip_ops.conv3x3_wgrad_supported(C_in, C_out, dtype) and W <= hip_ops.CONV3X3_WGRAD_MAX_W)
 
-
-def _conv3x3_packed(weight):
-    """The weight in the forward kernel's order, once per parameter version (the entry layers._tap_major_weight keeps)."""
-    from . import hip_ops
-    from .derived import derived1
-    return derived1("tap_major", weight, lambda w: hip_ops.conv3x3_n320_weight(w.detach()), hip_ops.conv3x3_k_order())
-
-
-def _conv3x3_packed_transposed(weight):
-    """The transposed weight of the input gradient in the forward kernel's order: kept in svd/derived.py's table while the weight is
-    frozen, built from the live tensor while it trains (it changes every step)."""
-    from . import hip_ops
-    from .derived import derived1
-
-    def build(w):
-        return hip_ops.conv3x3_n320_weight(hip_ops.conv3x3_transposed_weight(w.detach()))
-    if weight.requires_grad:
-        return build(weight)
-    return derived1("tap_major_transposed", weight, build, hip_ops.conv3x3_k_order())
-
-
-class _Conv3x3TokensFn(torch.autograd.Function):
-    """conv3x3_tokens on the implicit-GEMM kernel with a deterministic HIP backward: dx is the same kernel on the transposed weight
-    (W'[ci, co, ky, kx] = W[co, ci, 2 - ky, 2 - kx]), dweight is csrc/conv3x3_wgrad.hip. No bias (the blocks fold it elsewhere). Holds
-    tok and weight only; nothing is cached outside ctx, so torch.utils.checkpoint may re-run the forward."""
-
-    @staticmethod
-    def forward(ctx, tok, weight, H, W):
-        from . import hip_ops
-        ctx.save_for_backward(tok, weight)
-        ctx.hw = (H, W)
-        return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), None, H, W)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        from . import hip_ops
-        tok, weight = ctx.saved_tensors
-        H, W = ctx.hw
-        n = ctx.needs_input_grad
-        dy = dy if dy.is_contiguous() else dy.contiguous()
-        dx = hip_ops.conv3x3_dgrad(dy, _conv3x3_packed_transposed(weight), H, W) if n[0] else None
-        dw = hip_ops.conv3x3_wgrad(tok, dy, H, W).to(weight.dtype) if n[1] else None
-        return dx, dw, None, None
-
-
-def conv3x3_tokens(tok, weight, H, W):
-    """3x3 / padding 1 / stride 1 convolution of token-major activations tok [N, H W, C_in] with weight [C_out, C_in, 3, 3], no bias
-    -> [N, H W, C_out]. Without autograd: the implicit-GEMM kernel. Under autograd: _Conv3x3TokensFn where the switch is on, the three
-    launches take the shape (conv3x3_tokens_gates) and conv3x3_backward_pays says so; anything else is F.conv2d on the channels-last
-    view (a recorded fallback; strict mode raises)."""
-    N, S, C = tok.shape
-    Co = weight.shape[0]
-    if tok.is_cuda and tok.dtype == weight.dtype and S == H * W and tuple(weight.shape[1:]) == (C, 3, 3):
-        from . import hip_ops
-        if not _needs_autograd(tok, weight):
-            if (hip_ops.conv3x3_n320_supported(C, Co, tok.dtype) and N * S * C * 2 < 2 ** 32
-                    and hip_ops.conv3x3_n320_fills_chip(N, H, W, C, Co, CONV3X3_MIN_BLOCKS)):
-                return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), None, H, W)
-        elif CONV3X3_BACKWARD and conv3x3_tokens_gates(N, H, W, C, Co, tok.dtype) \
-                and conv3x3_backward_pays(N, H, W, C, Co, tok.dtype, weight.requires_grad):
-            return _Conv3x3TokensFn.apply(tok, weight, H, W)
-    _fallback(tok, "conv3x3_tokens", _why(tok, weight))
-    x = tok.view(N, H, W, C).permute(0, 3, 1, 2)                  # [N, C, H, W] with channels-last strides: no copy
-    y = F.conv2d(x, weight, None, 1, 1)
-    return y.permute(0, 2, 3, 1).reshape(N, S, Co)
 
 
 # The two resampling forms of that convolution under autograd — stride 2 (Downsample.op) and the convolution of the nearest-neighbour 2x
@@ -1380,139 +1318,27 @@ def conv3x3_up_backward_pays(N, h, w, C_in, C_out, dtype):
 
 
 def conv3x3_down_tokens_gates(N, H, W, C_in, C_out, dtype):
-    """Do the three launches of _Conv3x3DownTokensFn take this shape? Even H and W; the forward's conditions at stride 2 (channel gate,
-    32-bit byte offsets, enough blocks or a K split); the input gradient's with the channel roles swapped (C_in a multiple of 320,
-    C_out of 64; it has no K split, so its N H W / 256 row blocks x C_in / 320 column groups alone must reach the line); and the
+    """Do the three launches of the "s2" form under autograd take this shape? Even H and W; the forward's launch gate at stride 2
+    (hip_ops.conv_n320_launch_ok: channel gate, 32-bit byte offsets, enough blocks or a K split); the zero-stuffed input gradient's with
+    the channel roles swapped (C_in a multiple of 320, C_out of 64: mvi_conv3x3_s2_dgrad_supported is the forward's test on swapped
+    channels; it has no K split, so its N H W / 256 row blocks x C_in / 320 column groups alone must reach the line); and the
     weight-gradient kernel's gate."""
     from . import hip_ops
-    rows = N * H * W
-    return (dtype in (torch.bfloat16, torch.float16) and rows > 0 and H % 2 == 0 and W % 2 == 0
-            and hip_ops.conv3x3_n320_supported(C_in, C_out, dtype) and hip_ops.conv3x3_s2_dgrad_supported(C_in, C_out, dtype)
-            and rows * max(C_in, C_out) * 2 < 2 ** 32
-            and hip_ops.conv3x3_n320_fills_chip(N, H, W, C_in, C_out, RESAMPLE_CONV_MIN_BLOCKS, stride=2)
-            and -(-rows // 256) * (C_in // 320) >= RESAMPLE_CONV_MIN_BLOCKS
+    ok, mb = hip_ops.conv_n320_launch_ok, RESAMPLE_CONV_MIN_BLOCKS
+    # (N H W C_in 2 of the forward and N H W C_out 2 of the input gradient within 32 bits: N H W max(C_in, C_out) 2 < 2^32)
+    return (H % 2 == 0 and W % 2 == 0 and ok("s2", N, H, W, C_in, C_out, dtype, mb) and ok("s2_dgrad", N, H, W, C_out, C_in, dtype, mb)
             and hip_ops.conv3x3_s2_wgrad_supported(C_in, C_out, dtype) and W <= hip_ops.CONV3X3_WGRAD_MAX_W)
 
 
 def conv3x3_up_tokens_gates(N, h, w, C_in, C_out, dtype):
-    """Do the launches of _Conv3x3UpTokensFn take this shape (h x w: the source)? The upsampling forward's conditions at 2 h x 2 w, the
-    stride-1 input gradient's there with the channel roles swapped, and the pooling pass's (C_in a multiple of 8: implied)."""
+    """Do the launches of the "up2" form under autograd take this shape (h x w: the source)? The upsampling forward's launch gate (no K
+    split), the stride-1 input gradient's at 2 h x 2 w with the channel roles swapped, and the pooling pass's (C_in a multiple of 8:
+    implied)."""
     from . import hip_ops
-    rows = N * 4 * h * w
-    return (dtype in (torch.bfloat16, torch.float16) and rows > 0
-            and hip_ops.conv3x3_n320_supported(C_in, C_out, dtype) and hip_ops.conv3x3_n320_supported(C_out, C_in, dtype)
-            and rows * max(C_in, C_out) * 2 < 2 ** 32
-            and -(-rows // 256) * (C_out // 320) >= RESAMPLE_CONV_MIN_BLOCKS
-            and hip_ops.conv3x3_n320_fills_chip(N, 2 * h, 2 * w, C_out, C_in, RESAMPLE_CONV_MIN_BLOCKS))
+    ok, mb = hip_ops.conv_n320_launch_ok, RESAMPLE_CONV_MIN_BLOCKS
+    # (4 N h w C_in 2 of the forward and 4 N h w C_out 2 of the input gradient within 32 bits: 4 N h w max(C_in, C_out) 2 < 2^32)
+    return ok("up2", N, h, w, C_in, C_out, dtype, mb) and ok("s1", N, 2 * h, 2 * w, C_out, C_in, dtype, mb)
 
-
-class _Conv3x3DownTokensFn(torch.autograd.Function):
-    """conv3x3_down_tokens on the implicit-GEMM kernel (stride 2, the bias in its accumulators: the inference launch, so y has the same
-    bits) with a deterministic HIP backward: dx = conv3x3(zero-stuffed dy, W') (hip_ops.conv3x3_s2_dgrad), dweight =
-    hip_ops.conv3x3_s2_wgrad, dbias = the fp32 sum of dy over rows. Holds tok and weight only; nothing is cached outside ctx, so
-    torch.utils.checkpoint may re-run the forward."""
-
-    @staticmethod
-    def forward(ctx, tok, weight, bias, H, W):
-        from . import hip_ops
-        ctx.save_for_backward(tok, weight)
-        ctx.hw = (H, W)
-        ctx.bias_dtype = None if bias is None else bias.dtype
-        return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), bias, H, W, stride=2)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        from . import hip_ops
-        tok, weight = ctx.saved_tensors
-        H, W = ctx.hw
-        n = ctx.needs_input_grad
-        dy = dy if dy.is_contiguous() else dy.contiguous()
-        dx = hip_ops.conv3x3_s2_dgrad(dy, _conv3x3_packed_transposed(weight), H, W) if n[0] else None
-        dw = hip_ops.conv3x3_s2_wgrad(tok, dy, H, W).to(weight.dtype) if n[1] else None
-        db = dy.sum(dim=(0, 1), dtype=torch.float32).to(ctx.bias_dtype) if n[2] else None
-        return dx, dw, db, None, None
-
-
-class _Conv3x3UpTokensFn(torch.autograd.Function):
-    """conv3x3_up_tokens on the upsampling form of the implicit-GEMM kernel (the inference launch) with a frozen weight: dx is the
-    stride-1 input gradient at 2 h x 2 w summed over every 2x2 cell (hip_ops.conv3x3_dgrad + hip_ops.pool2x2_sum). Holds the weight only:
-    neither the input nor the 4x upsampled activation is kept for the backward."""
-
-    @staticmethod
-    def forward(ctx, tok, weight, bias, h, w):
-        from . import hip_ops
-        ctx.save_for_backward(weight)
-        ctx.hw = (h, w)
-        return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), bias, h, w, up2=True)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        from . import hip_ops
-        weight, = ctx.saved_tensors
-        h, w = ctx.hw
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None, None
-        return conv3x3_up_dgrad(dy, weight, h, w), None, None, None, None
-
-
-def conv3x3_up_dgrad(dy, weight, h, w):
-    """dx [N, h w, C_in] of conv3x3_up_tokens from dy [N, (2 h)(2 w), C_out] — _Conv3x3UpTokensFn's backward: the stride-1 input gradient
-    at 2 h x 2 w on the forward kernel, then the sum over every 2x2 cell (one more rounding than a bare dgrad)."""
-    from . import hip_ops
-    dy = dy if dy.is_contiguous() else dy.contiguous()
-    g = hip_ops.conv3x3_dgrad(dy, _conv3x3_packed_transposed(weight), 2 * h, 2 * w)
-    return hip_ops.pool2x2_sum(g, h, w)
-
-
-def conv3x3_down_tokens(tok, weight, bias, H, W):
-    """3x3 / padding 1 / STRIDE 2 convolution (Downsample.op) of token-major activations tok [N, H W, C_in] with weight [C_out, C_in, 3, 3]
-    and bias [C_out] or None -> [N, Ho Wo, C_out], Ho = (H - 1) // 2 + 1. Without autograd: the implicit-GEMM kernel. Under autograd:
-    _Conv3x3DownTokensFn where the switch is on, the launches take the shape (conv3x3_down_tokens_gates) and conv3x3_down_backward_pays
-    says so; anything else is F.conv2d on the channels-last view (a recorded fallback; strict mode raises) — also the CPU path."""
-    N, S, C = tok.shape
-    Co = weight.shape[0]
-    if S != H * W or tuple(weight.shape[1:]) != (C, 3, 3):
-        raise ValueError("conv3x3_down_tokens: tok [N, H W, C_in] and weight [C_out, C_in, 3, 3] expected")
-    if tok.is_cuda and tok.dtype == weight.dtype:
-        from . import hip_ops
-        if not _needs_autograd(tok, weight, bias):
-            if (tok.dtype in (torch.bfloat16, torch.float16) and N * S > 0 and hip_ops.conv3x3_n320_supported(C, Co, tok.dtype)
-                    and N * S * C * 2 < 2 ** 32 and hip_ops.conv3x3_n320_fills_chip(N, H, W, C, Co, RESAMPLE_CONV_MIN_BLOCKS, stride=2)):
-                return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), bias, H, W, stride=2)
-        elif RESAMPLE_CONV_BACKWARD and conv3x3_down_tokens_gates(N, H, W, C, Co, tok.dtype) \
-                and conv3x3_down_backward_pays(N, H, W, C, Co, tok.dtype, weight.requires_grad):
-            return _Conv3x3DownTokensFn.apply(tok, weight, bias, H, W)
-    _fallback(tok, "conv3x3_down_tokens", _why(tok, weight, bias))
-    x = tok.view(N, H, W, C).permute(0, 3, 1, 2)                  # [N, C, H, W] with channels-last strides: no copy
-    y = F.conv2d(x, weight, bias, 2, 1)
-    return y.permute(0, 2, 3, 1).reshape(N, y.shape[2] * y.shape[3], Co)
-
-
-def conv3x3_up_tokens(tok, weight, bias, h, w):
-    """conv3x3(nearest 2x upsampling of x) (Upsample.conv) of token-major activations tok [N, h w, C_in] -> [N, (2 h)(2 w), C_out]. Without
-    autograd: the upsampling form of the implicit-GEMM kernel. Under autograd with a FROZEN weight and bias: _Conv3x3UpTokensFn where the
-    switch is on, the launches take the shape (conv3x3_up_tokens_gates) and conv3x3_up_backward_pays says so. Anything else — a
-    trainable weight or bias among it: this form's weight gradient is not built, no trained network has an Upsample — is
-    F.conv2d(F.interpolate(x)) on the channels-last view (a recorded fallback; strict mode raises) — also the CPU path."""
-    N, S, C = tok.shape
-    Co = weight.shape[0]
-    if S != h * w or tuple(weight.shape[1:]) != (C, 3, 3):
-        raise ValueError("conv3x3_up_tokens: tok [N, h w, C_in] and weight [C_out, C_in, 3, 3] expected")
-    if tok.is_cuda and tok.dtype == weight.dtype:
-        from . import hip_ops
-        if not _needs_autograd(tok, weight, bias):
-            if (tok.dtype in (torch.bfloat16, torch.float16) and N * S > 0 and hip_ops.conv3x3_n320_supported(C, Co, tok.dtype)
-                    and 4 * N * S * C * 2 < 2 ** 32 and -(-4 * N * S // 256) * (Co // 320) >= RESAMPLE_CONV_MIN_BLOCKS):
-                return hip_ops.conv3x3_n320(tok, _conv3x3_packed(weight), bias, h, w, up2=True)
-        elif RESAMPLE_CONV_BACKWARD and not _needs_autograd(weight, bias) and conv3x3_up_tokens_gates(N, h, w, C, Co, tok.dtype) \
-                and conv3x3_up_backward_pays(N, h, w, C, Co, tok.dtype):
-            return _Conv3x3UpTokensFn.apply(tok, weight, bias, h, w)
-    _fallback(tok, "conv3x3_up_tokens", _why(tok, weight, bias))
-    x = tok.view(N, h, w, C).permute(0, 3, 1, 2)
-    y = F.conv2d(F.interpolate(x, scale_factor=2, mode="nearest"), weight, bias, 1, 1)
-    return y.permute(0, 2, 3, 1).reshape(N, 4 * S, Co)
 
 
 # The (3, 1, 1) / padding (1, 0, 0) frame convolution of token-major activations under autograd (VideoResBlock.time_stack): forward and
@@ -1547,68 +1373,180 @@ def conv3t_backward_pays(B, T, S, C_in, C_out, dtype, need_dweight):
 
 
 def conv3t_tokens_gates(B, T, S, C_in, C_out, dtype):
-    """Do the three launches of _Conv3tTokensFn take this shape? The forward's conditions (layers.VideoResBlock._tokens_path_ok: the
+    """Do the three launches of the "t3" form under autograd take this shape? The forward's launch gate (hip_ops.conv_n320_launch_ok: the
     kernel's channel gate, 32-bit byte offsets, enough blocks or a K split), the same with the channel roles swapped for the input
     gradient, and csrc/conv3t_wgrad.hip's gate."""
     from . import hip_ops
-    rows = B * T * S
-    return (dtype in (torch.bfloat16, torch.float16) and rows > 0
-            and hip_ops.conv3x3_n320_supported(C_in, C_out, dtype) and hip_ops.conv3x3_n320_supported(C_out, C_in, dtype)
-            and rows * max(C_in, C_out) * 2 < 2 ** 32
-            and hip_ops.conv3t_n320_fills_chip(B, T, S, C_in, C_out, CONV3T_MIN_BLOCKS)
-            and hip_ops.conv3t_n320_fills_chip(B, T, S, C_out, C_in, CONV3T_MIN_BLOCKS)
+    ok, mb = hip_ops.conv_n320_launch_ok, CONV3T_MIN_BLOCKS
+    # (the two byte bounds, rows C_in 2 and rows C_out 2 within 32 bits, are together rows max(C_in, C_out) 2 < 2^32)
+    return (ok("t3", B, T, S, C_in, C_out, dtype, mb) and ok("t3", B, T, S, C_out, C_in, dtype, mb)
             and hip_ops.conv3t_wgrad_supported(C_in, C_out, dtype))
 
 
-def _conv3t_packed(weight):
-    """The weight in the forward kernel's order, once per parameter version (the entry layers._tap_major_weight keeps)."""
+# ---- the four forms of the token-major convolution on csrc/linear_n320.hip: one packed-weight pair, one Function, one route -------------
+
+def conv_packed_weight(w):
+    """A convolution weight in the implicit-GEMM kernel's order, [C_out][taps C_in] — 3x3 Conv2d weights ([C_out, C_in, 3, 3] -> 9 taps)
+    and (3,1,1) Conv3d weights ([C_out, C_in, 3, 1, 1] -> 3 taps, tap-major) — once per parameter version (svd/derived.py). The packing
+    order of the 3x3 weights is a process-global switch of the kernel: part of the signature (hip_ops.conv3x3_k_order)."""
     from . import hip_ops
     from .derived import derived1
-    return derived1("tap_major", weight, lambda w: hip_ops.conv3t_n320_weight(w.detach()))
+    if w.dim() == 5:
+        return derived1("tap_major", w, lambda w: hip_ops.conv3t_n320_weight(w.detach()))
+    return derived1("tap_major", w, lambda w: hip_ops.conv3x3_n320_weight(w.detach()), hip_ops.conv3x3_k_order())
 
 
-def _conv3t_packed_transposed(weight):
-    """The transposed weight of the input gradient in the forward kernel's order: kept in svd/derived.py's table while the weight is
-    frozen, built from the live tensor while it trains (it changes every step)."""
+def conv_packed_weight_transposed(w):
+    """The transposed weight of the input gradient (hip_ops.conv3x3_transposed_weight / conv3t_transposed_weight) in the same order:
+    kept in svd/derived.py's table while the weight is frozen, built from the live tensor while it trains (it changes every step)."""
     from . import hip_ops
     from .derived import derived1
+    if w.dim() == 5:
+        build, extra = (lambda w: hip_ops.conv3t_n320_weight(hip_ops.conv3t_transposed_weight(w.detach()))), ()
+    else:
+        build, extra = (lambda w: hip_ops.conv3x3_n320_weight(hip_ops.conv3x3_transposed_weight(w.detach()))), hip_ops.conv3x3_k_order()
+    return build(w) if w.requires_grad else derived1("tap_major_transposed", w, build, extra)
 
-    def build(w):
-        return hip_ops.conv3t_n320_weight(hip_ops.conv3t_transposed_weight(w.detach()))
-    if weight.requires_grad:
-        return build(weight)
-    return derived1("tap_major_transposed", weight, build)
+
+# One form of the op (the key is hip_ops.conv_n320_launch_ok's): the hip_ops forward launch and its keyword arguments, the hip_ops input- and
+# weight-gradient launches (wgrad None: not built, the form runs under autograd with a frozen weight and bias only; every form takes a
+# bias), and the NAMES of this module's switch, fill-the-chip line, gate and speed decision — looked up when called, so what a test or a
+# bench sets on the module holds.
+_ConvForm = collections.namedtuple("_ConvForm", "launch kwargs dgrad wgrad switch min_blocks gates pays")
+_CONV_FORMS = {
+    "s1": _ConvForm("conv3x3_n320", {}, "conv3x3_dgrad", "conv3x3_wgrad",
+                    "CONV3X3_BACKWARD", "CONV3X3_MIN_BLOCKS", "conv3x3_tokens_gates", "conv3x3_backward_pays"),
+    "s2": _ConvForm("conv3x3_n320", {"stride": 2}, "conv3x3_s2_dgrad", "conv3x3_s2_wgrad",
+                    "RESAMPLE_CONV_BACKWARD", "RESAMPLE_CONV_MIN_BLOCKS", "conv3x3_down_tokens_gates", "conv3x3_down_backward_pays"),
+    "up2": _ConvForm("conv3x3_n320", {"up2": True}, "conv3x3_up2_dgrad", None,
+                     "RESAMPLE_CONV_BACKWARD", "RESAMPLE_CONV_MIN_BLOCKS", "conv3x3_up_tokens_gates", "conv3x3_up_backward_pays"),
+    "t3": _ConvForm("conv3t_n320", {}, "conv3t_dgrad", "conv3t_wgrad",
+                    "CONV3T_BACKWARD", "CONV3T_MIN_BLOCKS", "conv3t_tokens_gates", "conv3t_backward_pays"),
+}
 
 
-class _Conv3tTokensFn(torch.autograd.Function):
-    """conv3t_tokens on the three-tap implicit-GEMM kernel with a deterministic HIP backward: dx is the same kernel on the transposed
-    weight (W'[ci, co, kt] = W[co, ci, 2 - kt]), dweight is csrc/conv3t_wgrad.hip. No bias (the blocks fold it elsewhere). Holds tok and
-    weight only; nothing is cached outside ctx, so torch.utils.checkpoint may re-run the forward."""
+def _conv_launch(f, tok, weight, bias, geom):
+    from . import hip_ops
+    return getattr(hip_ops, f.launch)(tok, conv_packed_weight(weight), bias, *geom, **f.kwargs)
+
+
+class _ConvTokensFn(torch.autograd.Function):
+    """A token-major convolution on the implicit-GEMM kernel — the inference launch, the bias in its accumulators, so y has the same
+    bits — with a deterministic HIP backward: geom is (H, W) of the image the op is handed, or (T,) for "t3".
+      dx       the form's input gradient on the forward kernel with the transposed weight (W'[ci, co, ky, kx] = W[co, ci, 2 - ky, 2 - kx];
+               "t3": W'[ci, co, kt] = W[co, ci, 2 - kt]): the same launch ("s1", "t3"), its zero-stuffed form ("s2"), or the stride-1
+               launch at 2 h x 2 w summed over every 2x2 cell ("up2": one more rounding than a bare dgrad)
+      dweight  csrc/conv3x3_wgrad.hip, its stride-2 form, csrc/conv3t_wgrad.hip
+      dbias    the fp32 sum of dy over rows
+    each only where needs_input_grad asks. Holds tok and weight — "up2", which has no weight gradient, the weight only: neither its input
+    nor the 4x upsampled activation is kept — never y, and nothing is cached outside ctx, so torch.utils.checkpoint may re-run the forward."""
 
     @staticmethod
-    def forward(ctx, tok, weight, T):
-        from . import hip_ops
-        ctx.save_for_backward(tok, weight)
-        ctx.frames = T
-        return hip_ops.conv3t_n320(tok, _conv3t_packed(weight), None, T)
+    def forward(ctx, form, tok, weight, bias, *geom):
+        f = ctx.form = _CONV_FORMS[form]
+        ctx.save_for_backward(*((tok, weight) if f.wgrad else (weight,)))
+        ctx.geom = geom
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return _conv_launch(f, tok, weight, bias, geom)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         from . import hip_ops
-        tok, weight = ctx.saved_tensors
-        T = ctx.frames
-        n = ctx.needs_input_grad
+        f, geom = ctx.form, ctx.geom
+        *tok, weight = ctx.saved_tensors
+        _, need_dx, need_dw, need_db = ctx.needs_input_grad[:4]
         dy = dy if dy.is_contiguous() else dy.contiguous()
-        dx = hip_ops.conv3t_dgrad(dy, _conv3t_packed_transposed(weight), T) if n[0] else None
-        dw = hip_ops.conv3t_wgrad(tok, dy, T).to(weight.dtype) if n[1] else None
-        return dx, dw, None
+        dx = getattr(hip_ops, f.dgrad)(dy, conv_packed_weight_transposed(weight), *geom) if need_dx else None
+        dw = getattr(hip_ops, f.wgrad)(tok[0], dy, *geom).to(weight.dtype) if need_dw else None
+        db = dy.sum(dim=(0, 1), dtype=torch.float32).to(ctx.bias_dtype) if need_db else None
+        return (None, dx, dw, db) + (None,) * len(geom)
+
+
+def _conv_tokens_route(form, tok, weight, bias, geom, dims):
+    """The triage of the four public ops below for a validated call; dims = (N, H, W, C_in, C_out) as the form's gate takes them. Without
+    autograd: the kernel where the launch gate passes. Under autograd: _ConvTokensFn where the form's switch is on, its *_tokens_gates
+    pass and its *_backward_pays says so (a form without a weight gradient: only with weight and bias frozen). None otherwise: the
+    caller records the fallback and runs its PyTorch expression."""
+    if not (tok.is_cuda and tok.dtype == weight.dtype):
+        return None
+    f, g = _CONV_FORMS[form], globals()
+    if not _needs_autograd(tok, weight, bias):
+        from . import hip_ops
+        if hip_ops.conv_n320_launch_ok(form, *dims, tok.dtype, g[f.min_blocks]):
+            return _conv_launch(f, tok, weight, bias, geom)
+    elif g[f.switch] and (f.wgrad or not _needs_autograd(weight, bias)) and g[f.gates](*dims, tok.dtype) \
+            and g[f.pays](*dims, tok.dtype, *((weight.requires_grad,) if f.wgrad else ())):
+        return _ConvTokensFn.apply(form, tok, weight, bias, *geom)
+    return None
+
+
+def conv3x3_tokens(tok, weight, H, W):
+    """3x3 / padding 1 / stride 1 convolution of token-major activations tok [N, H W, C_in] with weight [C_out, C_in, 3, 3], no bias
+    -> [N, H W, C_out]. Without autograd: the implicit-GEMM kernel. Under autograd: _ConvTokensFn where the switch is on, the three
+    launches take the shape (conv3x3_tokens_gates) and conv3x3_backward_pays says so; anything else is F.conv2d on the channels-last
+    view (a recorded fallback; strict mode raises)."""
+    N, S, C = tok.shape
+    Co = weight.shape[0]
+    if S == H * W and tuple(weight.shape[1:]) == (C, 3, 3):
+        y = _conv_tokens_route("s1", tok, weight, None, (H, W), (N, H, W, C, Co))
+        if y is not None:
+            return y
+    _fallback(tok, "conv3x3_tokens", _why(tok, weight))
+    x = tok.view(N, H, W, C).permute(0, 3, 1, 2)                  # [N, C, H, W] with channels-last strides: no copy
+    y = F.conv2d(x, weight, None, 1, 1)
+    return y.permute(0, 2, 3, 1).reshape(N, S, Co)
+
+
+def conv3x3_down_tokens(tok, weight, bias, H, W):
+    """3x3 / padding 1 / STRIDE 2 convolution (Downsample.op) of token-major activations tok [N, H W, C_in] with weight [C_out, C_in, 3, 3]
+    and bias [C_out] or None -> [N, Ho Wo, C_out], Ho = (H - 1) // 2 + 1. Without autograd: the implicit-GEMM kernel. Under autograd:
+    _ConvTokensFn where the switch is on, the launches take the shape (conv3x3_down_tokens_gates) and conv3x3_down_backward_pays
+    says so; anything else is F.conv2d on the channels-last view (a recorded fallback; strict mode raises) — also the CPU path."""
+    N, S, C = tok.shape
+    Co = weight.shape[0]
+    if S != H * W or tuple(weight.shape[1:]) != (C, 3, 3):
+        raise ValueError("conv3x3_down_tokens: tok [N, H W, C_in] and weight [C_out, C_in, 3, 3] expected")
+    y = _conv_tokens_route("s2", tok, weight, bias, (H, W), (N, H, W, C, Co))
+    if y is not None:
+        return y
+    _fallback(tok, "conv3x3_down_tokens", _why(tok, weight, bias))
+    x = tok.view(N, H, W, C).permute(0, 3, 1, 2)                  # [N, C, H, W] with channels-last strides: no copy
+    y = F.conv2d(x, weight, bias, 2, 1)
+    return y.permute(0, 2, 3, 1).reshape(N, y.shape[2] * y.shape[3], Co)
+
+
+def conv3x3_up_tokens(tok, weight, bias, h, w):
+    """conv3x3(nearest 2x upsampling of x) (Upsample.conv) of token-major activations tok [N, h w, C_in] -> [N, (2 h)(2 w), C_out]. Without
+    autograd: the upsampling form of the implicit-GEMM kernel. Under autograd with a FROZEN weight and bias: _ConvTokensFn where the
+    switch is on, the launches take the shape (conv3x3_up_tokens_gates) and conv3x3_up_backward_pays says so. Anything else — a
+    trainable weight or bias among it: this form's weight gradient is not built, no trained network has an Upsample — is
+    F.conv2d(F.interpolate(x)) on the channels-last view (a recorded fallback; strict mode raises) — also the CPU path."""
+    N, S, C = tok.shape
+    Co = weight.shape[0]
+    if S != h * w or tuple(weight.shape[1:]) != (C, 3, 3):
+        raise ValueError("conv3x3_up_tokens: tok [N, h w, C_in] and weight [C_out, C_in, 3, 3] expected")
+    y = _conv_tokens_route("up2", tok, weight, bias, (h, w), (N, h, w, C, Co))
+    if y is not None:
+        return y
+    _fallback(tok, "conv3x3_up_tokens", _why(tok, weight, bias))
+    x = tok.view(N, h, w, C).permute(0, 3, 1, 2)
+    y = F.conv2d(F.interpolate(x, scale_factor=2, mode="nearest"), weight, bias, 1, 1)
+    return y.permute(0, 2, 3, 1).reshape(N, 4 * S, Co)
+
+
+def conv3x3_up_dgrad(dy, weight, h, w):
+    """dx [N, h w, C_in] of conv3x3_up_tokens from dy [N, (2 h)(2 w), C_out] — the "up2" form's backward: the stride-1 input gradient
+    at 2 h x 2 w on the forward kernel, then the sum over every 2x2 cell (one more rounding than a bare dgrad)."""
+    from . import hip_ops
+    dy = dy if dy.is_contiguous() else dy.contiguous()
+    return hip_ops.conv3x3_up2_dgrad(dy, conv_packed_weight_transposed(weight), h, w)
 
 
 def conv3t_tokens(tok, weight, T):
     """(3, 1, 1) / padding (1, 0, 0) convolution over the frame axis of token-major activations tok [(b T), S, C_in] (the T frames of a
     video consecutive) with weight [C_out, C_in, 3, 1, 1], no bias -> [(b T), S, C_out]. Without autograd: the three-tap implicit-GEMM
-    kernel. Under autograd: _Conv3tTokensFn where the switch is on, the three launches take the shape (conv3t_tokens_gates) and
+    kernel. Under autograd: _ConvTokensFn where the switch is on, the three launches take the shape (conv3t_tokens_gates) and
     conv3t_backward_pays says so; anything else is F.conv3d on the b c t s 1 view (a recorded fallback; strict mode raises) — also the
     CPU path."""
     BT, S, C = tok.shape
@@ -1617,15 +1555,9 @@ def conv3t_tokens(tok, weight, T):
     if T < 1 or BT % T or tuple(weight.shape[1:]) != (C, 3, 1, 1):
         raise ValueError("conv3t_tokens: tok [(b T), S, C_in] and weight [C_out, C_in, 3, 1, 1] expected")
     B = BT // T
-    if tok.is_cuda and tok.dtype == weight.dtype:
-        from . import hip_ops
-        if not _needs_autograd(tok, weight):
-            if (tok.dtype in (torch.bfloat16, torch.float16) and BT * S > 0 and hip_ops.conv3x3_n320_supported(C, Co, tok.dtype)
-                    and BT * S * C * 2 < 2 ** 32 and hip_ops.conv3t_n320_fills_chip(B, T, S, C, Co, CONV3T_MIN_BLOCKS)):
-                return hip_ops.conv3t_n320(tok, _conv3t_packed(weight), None, T)
-        elif CONV3T_BACKWARD and conv3t_tokens_gates(B, T, S, C, Co, tok.dtype) \
-                and conv3t_backward_pays(B, T, S, C, Co, tok.dtype, weight.requires_grad):
-            return _Conv3tTokensFn.apply(tok, weight, T)
+    y = _conv_tokens_route("t3", tok, weight, None, (T,), (B, T, S, C, Co))
+    if y is not None:
+        return y
     _fallback(tok, "conv3t_tokens", _why(tok, weight))
     x = tok.reshape(B, T, S, C).permute(0, 3, 1, 2).unsqueeze(-1)              # b c t s 1 (a view)
     y = F.conv3d(x, weight, None, 1, (1, 0, 0))

@@ -1,5 +1,5 @@
 """GPU parity of the (3, 1, 1) frame convolution under autograd: the weight-gradient kernel (csrc/conv3t_wgrad.hip), the input gradient
-on the forward's three-tap implicit-GEMM kernel with the transposed weight, ops._Conv3tTokensFn / ops.conv3t_tokens and the temporal
+on the forward's three-tap implicit-GEMM kernel with the transposed weight, ops._ConvTokensFn / ops.conv3t_tokens and the temporal
 ResBlock route behind layers.TIME_STACK_CONV_BWD.
 
 Oracle: the fp64 formulas of tests/conv3t_bwd_helpers.py (held to fp64 autograd in tests/test_conv3t_bwd_cpu.py, 1e-12), evaluated on

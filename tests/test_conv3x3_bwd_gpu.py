@@ -1,5 +1,5 @@
 """GPU parity of the 3x3 convolution under autograd: the weight-gradient kernel (csrc/conv3x3_wgrad.hip), the input gradient on the
-forward's implicit-GEMM kernel with the transposed weight, ops._Conv3x3TokensFn / ops.conv3x3_tokens and the ResBlock route behind
+forward's implicit-GEMM kernel with the transposed weight, ops._ConvTokensFn / ops.conv3x3_tokens and the ResBlock route behind
 layers.RESBLOCK_CONV_BWD.
 
 Oracle: the fp64 formulas of tests/conv_bwd_helpers.py (held to fp64 autograd in tests/test_conv3x3_bwd_cpu.py, 1e-12), evaluated on

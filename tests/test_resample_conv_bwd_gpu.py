@@ -249,7 +249,7 @@ def _assert_inside_module_bar(name, got, old, ref):
 @pytest.mark.parametrize("tag", list(R.DTYPES))
 @pytest.mark.parametrize("shape", UP_DGRAD_SHAPES, ids=_id)
 def test_up_dgrad_against_fp64_and_the_pytorch_route(shape, tag, route_every_supported_shape):
-    """dx of the upsampling form — ops.conv3x3_up_dgrad, the backward of ops._Conv3x3UpTokensFn: conv3x3_dgrad at 2 h x 2 w + pool2x2_sum —
+    """dx of the upsampling form — ops.conv3x3_up_dgrad, the backward of ops._ConvTokensFn's "up2" form: conv3x3_dgrad at 2 h x 2 w + pool2x2_sum —
     against fp64. It carries one more rounding than a bare dgrad, so its bar is the module bar: error <= 2.0 x (max) / 1.6 x (rms) of the
     error of F.conv2d(F.interpolate(x)) under autograd on the GPU in the same dtype. Where the forward kernel takes the shape too (C_out a
     multiple of 320) the same bits come out of ops.conv3x3_up_tokens(...).backward."""
