@@ -28,65 +28,35 @@ extern "C" {
 #define MVI_DT_BF16 1
 #define MVI_DT_F16 2
 
-/* GroupNorm over groups of C/groups channels x `spatial` positions of x [N, C, spatial] (contiguous;
- * spatial = H*W or T*H*W), statistics and affine in fp32, optional fused SiLU, y has x's dtype.
- * weight/bias: fp32 [C]. workspace: mvi_groupnorm_workspace_bytes(...) bytes. */
-size_t mvi_groupnorm_workspace_bytes(int64_t N, int32_t C, int64_t spatial, int32_t groups);
-int mvi_groupnorm_silu(const void* x, void* y, const float* weight, const float* bias, int64_t N,
-                       int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu,
-                       int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
-
-/* The same GroupNorm for the temporal layers: statistics over (C/groups, T, spatial) of a tensor stored
- * [(videos*T), C, spatial] — i.e. GroupNorm of "b c t h w" (svd_inpaint1/sgm/modules/diffusionmodules/
- * video_model.py:71-75, openaimodel.py:257-261 with dims=3) computed on the "(b t) c h w" layout the
- * spatial layers produce, without the permute copies. Workspace: mvi_groupnorm_workspace_bytes(videos*T, ...). */
-int mvi_groupnorm_silu_temporal(const void* x, void* y, const float* weight, const float* bias,
-                                int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups,
-                                float eps, int32_t fuse_silu, int32_t dtype, void* workspace,
-                                size_t workspace_bytes, void* stream);
-
-/* General form. chan_bias (nullable): fp32 [(videos*T), C] added to x before the statistics — the timestep-
- * embedding bias a ResBlock adds in front of its second norm (openaimodel.py:341-352), fused so the sum is never
- * written. stack3 != 0 (requires the temporal layout; y must not alias x): y is [(videos*T), 3C, spatial] and
- * receives the normalised frame t at channel block 1 of row t, block 0 of row t+1 and block 2 of row t-1, with
- * zero frames at the sequence ends — exactly the input a kernel-(3,1,1) temporal convolution needs when it is
- * evaluated as one 1x1 convolution over 3C channels. T = 1 gives the plain [N, C, spatial] norm. */
-int mvi_groupnorm_silu_ex(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
-                          int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, float eps,
-                          int32_t fuse_silu, int32_t stack3, int32_t dtype, void* workspace, size_t workspace_bytes,
-                          void* stream);
-
-/* mvi_groupnorm_silu_ex with a sync buffer: groups that do not fit one block's registers (and every temporal / stacked call)
- * are then normalised in ONE launch that reads x once — K consecutive blocks per group exchange their partial moments through
- * `workspace` and meet at two counters per group in `sync`. `sync`: mvi_groupnorm_sync_bytes() bytes, zeroed ONCE by the
- * caller (the kernels leave it zeroed), private to one stream at a time (two launches that overlap in time must not share
- * it); NULL = the two-launch kernels of mvi_groupnorm_silu_ex. The last word is a sticky flag: non-zero if a block ever gave
- * up waiting for its group (bounded spin; the output of that call is then undefined). */
-size_t mvi_groupnorm_sync_bytes(void);
-int mvi_groupnorm_silu_ex2(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
-                           int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, float eps,
-                           int32_t fuse_silu, int32_t stack3, int32_t dtype, void* workspace, size_t workspace_bytes,
-                           void* sync, size_t sync_bytes, void* stream);
-
-/* The same norm (x [N, C, spatial], optional chan_bias, optional SiLU) with TOKEN-MAJOR output y [N, spatial, C]:
- * "b c h w -> b (h w) c" (svd_inpaint1/sgm/modules/attention.py:700-707) fused into the apply pass, for consumers that
- * contract over channels (proj_in Linear; a channels-last convolution). C and spatial must be multiples of the 16-byte
- * vector width; y must not alias x. */
-int mvi_groupnorm_silu_tokens(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
-                              int64_t N, int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu,
-                              int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
-
-/* Differentiable GroupNorm(+SiLU) (csrc/groupnorm_bwd.hip): the forward and backward of GroupNorm32 -> SiLU for training through the
- * ResBlocks of the reference (openaimodel.py:341-353 with `h + emb_out` in front, video_model.py:71-75 with dims = 3, attention.py:125-128
- * for Normalize without SiLU). Domain: that of mvi_groupnorm_silu_ex (fp32 / bf16 / f16; plain and temporal form; with or without
- * chan_bias and SiLU; the 16-byte vector path and the scalar path for odd `spatial` or unaligned bases; any eps).
+/* GroupNorm(+SiLU), planes input (csrc/groupnorm_silu.hip; backward csrc/groupnorm_bwd.hip): GroupNorm32 -> SiLU of the reference's
+ * ResBlocks (openaimodel.py:257-261, :341-353 with `h + emb_out` in front, video_model.py:71-75 with dims = 3, attention.py:125-128 for
+ * Normalize without SiLU). fp32 / bf16 / f16 I/O, statistics and affine in fp32, weight / bias fp32 [C], any eps; the 16-byte vector
+ * path, and the scalar path for odd `spatial` or unaligned bases.
  *
- * mvi_groupnorm_backward_supported: pure host function, 1 where the entries below compute (the Python gate reads it). It cannot see
- *     pointers: the token-major layout also needs x, dy and dx 16-byte aligned (MVI_EINVAL otherwise; the caller checks); the other
- *     layouts take the scalar path for unaligned bases.
- * mvi_groupnorm_forward_stats: the forward — mvi_groupnorm_silu_ex2 for out_layout MVI_GN_DY_PLANES / MVI_GN_DY_STACK3,
- *     mvi_groupnorm_silu_tokens for MVI_GN_DY_TOKENS (sync may be NULL there): the same kernels, same instructions, `y` bit-identical —
- *     that also writes stats [videos * groups, 2] fp32 = (mean, rstd) of every (video, group).
+ * mvi_groupnorm_forward: x [(videos*T), C, spatial] contiguous (spatial = H*W), groups of C/groups channels, y in x's dtype.
+ *     T: frames that share a group's statistics. T = 1 is the plain [N, C, spatial] norm; T > 1 takes them over (C/groups, T, spatial)
+ *         — GroupNorm of "b c t h w" (video_model.py:71-75) computed on the "(b t) c h w" layout the spatial layers produce, without
+ *         the permute copies.
+ *     chan_bias (nullable): fp32 [(videos*T), C] added to x before the statistics — the timestep-embedding bias a ResBlock adds in
+ *         front of its second norm (openaimodel.py:341-352), fused so the sum is never written.
+ *     out_layout: MVI_GN_DY_PLANES: y as x (y may alias x). MVI_GN_DY_STACK3 (y must not alias x): y is [(videos*T), 3C, spatial] and
+ *         receives the normalised frame t at channel block 1 of row t, block 0 of row t+1 and block 2 of row t-1, with zero frames at
+ *         the sequence ends — exactly the input a kernel-(3,1,1) temporal convolution needs when it is evaluated as one 1x1
+ *         convolution over 3C channels. MVI_GN_DY_TOKENS (T == 1; y must not alias x): y token-major [N, spatial, C], "b c h w ->
+ *         b (h w) c" (attention.py:700-707) fused into the apply pass, for consumers that contract over channels (proj_in Linear; a
+ *         channels-last convolution); C and spatial must be multiples of the 16-byte vector width, x and y 16-byte aligned.
+ *     stats (nullable): NULL runs the inference kernels; else the same kernels, same instructions, `y` bit-identical, also write
+ *         stats [videos * groups, 2] fp32 = (mean, rstd) of every (video, group), what mvi_groupnorm_backward takes.
+ *     workspace: mvi_groupnorm_workspace_bytes(videos*T, C, spatial, groups) bytes.
+ *     sync (nullable; not looked at for token-major output): with it, groups that do not fit one block's registers are normalised in
+ *         ONE launch that reads x once — K consecutive blocks per group exchange their partial moments through `workspace` and meet at
+ *         two counters per group in `sync`. mvi_groupnorm_sync_bytes() bytes, zeroed ONCE by the caller (the kernels leave it zeroed),
+ *         private to one stream at a time (two launches that overlap in time must not share it); NULL = the two-launch kernels. The
+ *         last word is a sticky flag: non-zero if a block ever gave up waiting for its group (bounded spin; the output of that call
+ *         is then undefined).
+ * mvi_groupnorm_backward_supported: pure host function, 1 where forward-with-stats and backward compute (the Python gate reads it). It
+ *     cannot see pointers: the token-major layout also needs x, dy and dx 16-byte aligned (MVI_EINVAL otherwise; the caller checks);
+ *     the other layouts take the scalar path for unaligned bases.
  * mvi_groupnorm_backward: from x, chan_bias, weight, bias as the forward took them, stats, and dy in the layout the forward wrote y in
  *     (planes [rows, C, spatial]; stack3 [rows, 3 C, spatial] — the gradient of frame t is block 1 of row t + block 0 of row t + 1 +
  *     block 2 of row t - 1, missing neighbours at the ends of a video being zero; token-major [rows, spatial, C], which needs T == 1 and
@@ -97,38 +67,29 @@ int mvi_groupnorm_silu_tokens(const void* x, void* y, const float* weight, const
 #define MVI_GN_DY_PLANES 0
 #define MVI_GN_DY_STACK3 1
 #define MVI_GN_DY_TOKENS 2
+size_t mvi_groupnorm_workspace_bytes(int64_t N, int32_t C, int64_t spatial, int32_t groups);
+size_t mvi_groupnorm_sync_bytes(void);
+int mvi_groupnorm_forward(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias, float* stats,
+                          int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu,
+                          int32_t out_layout, int32_t dtype, void* workspace, size_t workspace_bytes, void* sync,
+                          size_t sync_bytes, void* stream);
 int mvi_groupnorm_backward_supported(int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, int32_t dy_layout,
                                      int32_t dtype);
-int mvi_groupnorm_forward_stats(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias, float* stats,
-                                int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu,
-                                int32_t out_layout, int32_t dtype, void* workspace, size_t workspace_bytes, void* sync,
-                                size_t sync_bytes, void* stream);
 size_t mvi_groupnorm_backward_workspace_bytes(int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups);
 int mvi_groupnorm_backward(const void* x, const void* dy, const float* stats, const float* weight, const float* bias,
                            const float* chan_bias, void* dx, float* dweight, float* dbias, float* dchan_bias, int64_t videos, int32_t T,
                            int32_t C, int64_t spatial, int32_t groups, int32_t fuse_silu, int32_t dy_layout, int32_t dtype,
                            void* workspace, size_t workspace_bytes, void* stream);
 
-/* GroupNorm(+SiLU) with TOKEN-MAJOR input and output: x, y [N, spatial, C] (C contiguous = NHWC). The norm between the two
- * 3x3 convolutions of a ResBlock (openaimodel.py:292-305, :341-352) when the convolutions run on channels-last tensors —
- * MIOpen's kernels are NHWC and wrap NCHW tensors in transposes (csrc/groupnorm_tokens.hip). chan_bias: optional fp32 [N, C]
- * added to x before the statistics (the timestep-embedding bias). workspace: mvi_groupnorm_tok2tok_workspace_bytes(...)
- * (0 = shape not supported: C must be a multiple of groups <= 64 and of the 16-byte vector width). */
-size_t mvi_groupnorm_tok2tok_workspace_bytes(int64_t N, int32_t C, int64_t spatial, int32_t groups, int32_t dtype);
-int mvi_groupnorm_silu_tok2tok(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias, int64_t N,
-                               int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu, int32_t dtype,
-                               void* workspace, size_t workspace_bytes, void* stream);
-/* The same with TEMPORAL statistics: the N samples are videos of `frames` consecutive frames, a group's mean / variance are taken
- * over all frames of a video (the GroupNorm of VideoResBlock.time_stack on b c t h w, video_model.py:71-75); chan_bias stays per frame
- * [N, C] (the per-frame timestep embedding). Same workspace. */
-int mvi_groupnorm_silu_tok2tok_frames(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias, int64_t N,
-                                      int32_t frames, int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu,
-                                      int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
-
-/* The token-major GroupNorm(+SiLU) under training (csrc/groupnorm_tokens.hip, csrc/groupnorm_bwd.hip): x, y, dy, dx all
- * [N, spatial, C], statistics per (video of `frames` consecutive samples, group), chan_bias [N, C] per sample.
- * mvi_groupnorm_tok2tok_forward_stats: mvi_groupnorm_silu_tok2tok_frames — the same launches, `y` bit-identical — that also writes
- *     stats [N / frames * groups, 2] fp32 = (mean of x + chan_bias, rstd) of every (video, group). Same workspace.
+/* GroupNorm(+SiLU) with TOKEN-MAJOR input and output (csrc/groupnorm_tokens.hip, csrc/groupnorm_bwd.hip): x, y, dy, dx all
+ * [N, spatial, C] (C contiguous = NHWC), 16-byte aligned. The norm between the two 3x3 convolutions of a ResBlock (openaimodel.py:292-305,
+ * :341-352) when the convolutions run on channels-last tensors — MIOpen's kernels are NHWC and wrap NCHW tensors in transposes.
+ * mvi_groupnorm_tok2tok_forward: statistics per (video of `frames` consecutive samples, group): frames = 1 is the per-sample norm,
+ *     frames > 1 the GroupNorm of VideoResBlock.time_stack on b c t h w (video_model.py:71-75), N a whole number of videos.
+ *     chan_bias (nullable): fp32 [N, C] added to x before the statistics (the timestep-embedding bias), per sample whatever `frames`.
+ *     stats (nullable): NULL = inference; else the same launches, `y` bit-identical, also write stats [N / frames * groups, 2] fp32 =
+ *     (mean of x + chan_bias, rstd) of every (video, group). workspace: mvi_groupnorm_tok2tok_workspace_bytes(...) bytes (0 = shape
+ *     not supported: C must be a multiple of groups <= 64 and of the 16-byte vector width).
  * mvi_groupnorm_tok2tok_backward_supported: pure host function, 1 where the backward computes: the forward's geometry (C a multiple of
  *     groups <= 64 and of the 16-byte vector, N <= 65535), N a whole number of videos, C <= 5461 (the reduce pass's LDS image), grids and
  *     tables within 32 bits. It cannot see pointers: x, dy and dx must be 16-byte aligned (MVI_EINVAL otherwise; the caller checks).
@@ -137,9 +98,10 @@ int mvi_groupnorm_silu_tok2tok_frames(const void* x, void* y, const float* weigh
  *     token-major x and dy read in place: a reduce pass and an apply pass in which a thread keeps the same 16-byte channel vector in every
  *     token row, no transpose anywhere. fp32 math, one rounding on the way out; no atomics, two runs give the same bits.
  *     workspace: mvi_groupnorm_tok2tok_backward_workspace_bytes(...) bytes (0 = unsupported), 4-byte aligned. */
-int mvi_groupnorm_tok2tok_forward_stats(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
-                                        float* stats, int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups, float eps,
-                                        int32_t fuse_silu, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
+size_t mvi_groupnorm_tok2tok_workspace_bytes(int64_t N, int32_t C, int64_t spatial, int32_t groups, int32_t dtype);
+int mvi_groupnorm_tok2tok_forward(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
+                                  float* stats, int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups, float eps,
+                                  int32_t fuse_silu, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
 int mvi_groupnorm_tok2tok_backward_supported(int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups, int32_t dtype);
 size_t mvi_groupnorm_tok2tok_backward_workspace_bytes(int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups,
                                                       int32_t dtype);
@@ -533,7 +495,7 @@ int mvi_ff_geglu_n320(const void* x, const void* weight, const float* bias, void
  * mvi_conv3x3_n320_gnstats / mvi_conv3t_n320_gnstats are mvi_conv3x3_n320 (stride 1) / mvi_conv3t_n320 whose blocks also leave, in
  * gn_part [samples * (spatial / 256) * gn_groups][3], (count, mean, M2) of every GroupNorm group of their 256 rows — of the ROUNDED
  * outputs plus gn_chan_bias [samples, C_out] (the timestep-embedding bias the norm adds first; NULL: none) — and
- * mvi_groupnorm_silu_tok2tok_pre is mvi_groupnorm_silu_tok2tok_frames without its statistics pass, merging those partials
+ * mvi_groupnorm_silu_tok2tok_pre is mvi_groupnorm_tok2tok_forward without its statistics pass, merging those partials
  * (chunks_per_sample = spatial / 256): the tensor is read once instead of twice. A sample is an image (3x3) or a frame (3-tap:
  * spatial = pixels of a frame); `frames` > 1 merges the frames of a video as in the _frames form. Only shapes for which
  * mvi_conv_n320_gnstats_supported answers 1 (stride 1, no K split, spatial a multiple of 256, groups of <= 40 channels that tile 320);

@@ -8,7 +8,7 @@
 //   dweight_c = sum g xh, dbias_c = sum g;  A = sum_group w_c g, B = sum_group w_c g xh, m = elements of the group
 //   dx = rstd (w_c g - A / m - xh B / m);   dchan_bias[row, c] = sum_positions dx
 //
-// x [rows = videos * T, C, S] as the forward takes it; (mean, rstd) [videos * G, 2] fp32 from the forward (mvi_groupnorm_forward_stats).
+// x [rows = videos * T, C, S] as the forward takes it; (mean, rstd) [videos * G, 2] fp32 from the forward (mvi_groupnorm_forward's stats).
 // Four launches, the two that touch the tensor on 64-channel x 128-position tiles (64 positions on the scalar path):
 //   reduce   : per tile and channel sum g, sum g xh, sum xh over the tile's positions -> part [row, s_tile, C, 3]  (reads x, dy)
 //   finalize : one block per (video, group): the tiles summed in a fixed order -> sums [row, C, 3]; A, B -> coef [videos * G, 2]
@@ -20,7 +20,7 @@
 // crosses LDS once (XOR-swizzled 16-byte chunks, so that the transposed reads of a wave spread over the banks).
 //
 // Token-major x, dy AND dx [rows, S, C] (mvi_groupnorm_tok2tok_backward: the norm between the two convolutions of a ResBlock,
-// mvi_groupnorm_silu_tok2tok[_frames]) have kernels of their own for the two passes over the tensor, gn_bwd_tok_reduce_kernel and
+// mvi_groupnorm_tok2tok_forward) have kernels of their own for the two passes over the tensor, gn_bwd_tok_reduce_kernel and
 // gn_bwd_tok_apply_kernel: channels are contiguous in all three tensors, so nothing is transposed; finalize and params are the same
 // launches on the same `part` layout.
 #include <hip/hip_bf16.h>
@@ -299,12 +299,10 @@ static bool gb_plan(int64_t videos, int T, int C, int64_t S, int G, int dtype, b
 template <typename T, int LAYOUT, bool VEC>
 static void gb_launch_tiles(const void* x, const void* dy, const GbGeom& q, const GbPlan& p, float* part, const float* coef, void* dx,
                             bool apply, hipStream_t st) {
-    if (apply)
-        hipLaunchKernelGGL((gn_bwd_tile_kernel<T, LAYOUT, VEC, true>), dim3((unsigned)p.blocks), dim3(kGbBlock), 0, st, (const T*)x,
-                           (const T*)dy, q, part, coef, (T*)dx);
-    else
-        hipLaunchKernelGGL((gn_bwd_tile_kernel<T, LAYOUT, VEC, false>), dim3((unsigned)p.blocks), dim3(kGbBlock), 0, st, (const T*)x,
-                           (const T*)dy, q, part, coef, (T*)dx);
+    dispatch_flag(apply, [&](auto k) {
+        hipLaunchKernelGGL((gn_bwd_tile_kernel<T, LAYOUT, VEC, decltype(k)::value>), dim3((unsigned)p.blocks), dim3(kGbBlock), 0, st,
+                           (const T*)x, (const T*)dy, q, part, coef, (T*)dx);
+    });
 }
 
 template <typename T>

@@ -489,12 +489,10 @@ static int gn_resident_launch_bs(const void* x, void* y, const float* w, const f
     const int64_t blocks = N * G;
 #define MVI_GN_RES(NVV)                                                                                                          \
     case NVV:                                                                                                                    \
-        if (stats)                                                                                                               \
-            hipLaunchKernelGGL((gn_resident_kernel<T, NVV, BS, true>), dim3((unsigned)blocks), dim3(BS), 0, st, (const T*)x, (T*)y, w, b, \
-                               chan_bias, Cg, G, S, eps, silu, stats);                                                            \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((gn_resident_kernel<T, NVV, BS>), dim3((unsigned)blocks), dim3(BS), 0, st, (const T*)x, (T*)y, w, b, \
-                               chan_bias, Cg, G, S, eps, silu, stats);                                                            \
+        dispatch_flag(stats != nullptr, [&](auto k) {                                                                            \
+            hipLaunchKernelGGL((gn_resident_kernel<T, NVV, BS, decltype(k)::value>), dim3((unsigned)blocks), dim3(BS), 0, st,     \
+                               (const T*)x, (T*)y, w, b, chan_bias, Cg, G, S, eps, silu, stats);                                  \
+        });                                                                                                                      \
         break;
     switch (nv) {
         MVI_GN_RES(2) MVI_GN_RES(4) MVI_GN_RES(8) MVI_GN_RES(12)
@@ -741,14 +739,10 @@ static int gn_cluster_launch(const void* x, void* y, const float* w, const float
     const int need = (vpb + BS - 1) / BS;
     const unsigned blocks = (unsigned)(groups * K);                       // exactly the tickets 0 .. groups * K - 1
 #define MVI_GN_CL(NVV)                                                                                                        \
-    do {                                                                                                                      \
-        if (q.stats)                                                                                                          \
-            hipLaunchKernelGGL((gn_cluster_kernel<T, NVV, true>), dim3(blocks), dim3(BS), 0, st, (const T*)x, (T*)y, w, b, q, kps, vpb, \
-                               eps, silu, part, sync, groups);                                                                \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((gn_cluster_kernel<T, NVV>), dim3(blocks), dim3(BS), 0, st, (const T*)x, (T*)y, w, b, q, kps, vpb, eps,  \
-                               silu, part, sync, groups);                                                                     \
-    } while (0)
+    dispatch_flag(q.stats != nullptr, [&](auto k) {                                                                           \
+        hipLaunchKernelGGL((gn_cluster_kernel<T, NVV, decltype(k)::value>), dim3(blocks), dim3(BS), 0, st, (const T*)x, (T*)y, w, b, q, \
+                           kps, vpb, eps, silu, part, sync, groups);                                                          \
+    })
     if (need <= 2) MVI_GN_CL(2);
     else if (need <= 4) MVI_GN_CL(4);
     else if (need <= 8) MVI_GN_CL(8);
@@ -759,8 +753,8 @@ static int gn_cluster_launch(const void* x, void* y, const float* w, const float
 
 template <typename T>
 static int gn_launch(const void* x, void* y, const float* w, const float* b, const float* chan_bias, int stack3, int64_t N,
-                     int slices, int C, int64_t S, int G, float eps, int silu, float* part, hipStream_t st, int tokens = 0,
-                     uint32_t* sync = nullptr, float* stats = nullptr) {
+                     int slices, int C, int64_t S, int G, float eps, int silu, float* part, hipStream_t st, int tokens,
+                     uint32_t* sync, float* stats) {
     constexpr int KV = Io<T>::kVec;
     constexpr int CH = kGnBlock * kGnVecPerThread * KV;
     GnGeom q;
@@ -777,12 +771,10 @@ static int gn_launch(const void* x, void* y, const float* w, const float* b, con
         const int64_t blocks = N * s_tiles * c_tiles;
         if (blocks > 0x7FFFFFFFll) return MVI_EINVAL;
         hipLaunchKernelGGL((gn_stats_kernel<T, true>), grid, dim3(kGnBlock), 0, st, (const T*)x, part, q);
-        if (stats)
-            hipLaunchKernelGGL((gn_apply_tokens_kernel<T, true>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, (T*)y, w, b,
-                               part, q, eps, silu, s_tiles, c_tiles);
-        else
-            hipLaunchKernelGGL((gn_apply_tokens_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, (T*)y, w, b, part,
-                               q, eps, silu, s_tiles, c_tiles);
+        dispatch_flag(stats != nullptr, [&](auto k) {
+            hipLaunchKernelGGL((gn_apply_tokens_kernel<T, decltype(k)::value>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x,
+                               (T*)y, w, b, part, q, eps, silu, s_tiles, c_tiles);
+        });
         return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
     }
     // measured (tools/bench_groupnorm.py, bf16, MI355X, two launches -> resident): 11 KB groups 21.7 -> 17.8 us, 46 KB
@@ -803,15 +795,13 @@ static int gn_launch(const void* x, void* y, const float* w, const float* b, con
     // (Measured and not kept: running the two launches per BAND of samples, sized so that the statistics pass's reads are
     // still in the 256 MB Infinity Cache when the apply pass reads them again — 48 MB bands: 146 us instead of 116 at
     // (28, 320, 72, 128) bf16; smaller bands worse: the shorter grids cost more than the cached re-read saves.)
-    if (vec) {
-        hipLaunchKernelGGL((gn_stats_kernel<T, true>), grid, dim3(kGnBlock), 0, st, (const T*)x, part, q);
-        if (stats) hipLaunchKernelGGL((gn_apply_kernel<T, true, true>), grid, dim3(kGnBlock), 0, st, (const T*)x, (T*)y, w, b, part, q, eps, silu);
-        else hipLaunchKernelGGL((gn_apply_kernel<T, true>), grid, dim3(kGnBlock), 0, st, (const T*)x, (T*)y, w, b, part, q, eps, silu);
-    } else {
-        hipLaunchKernelGGL((gn_stats_kernel<T, false>), grid, dim3(kGnBlock), 0, st, (const T*)x, part, q);
-        if (stats) hipLaunchKernelGGL((gn_apply_kernel<T, false, true>), grid, dim3(kGnBlock), 0, st, (const T*)x, (T*)y, w, b, part, q, eps, silu);
-        else hipLaunchKernelGGL((gn_apply_kernel<T, false>), grid, dim3(kGnBlock), 0, st, (const T*)x, (T*)y, w, b, part, q, eps, silu);
-    }
+    dispatch_flag(vec, [&](auto v) {
+        hipLaunchKernelGGL((gn_stats_kernel<T, decltype(v)::value>), grid, dim3(kGnBlock), 0, st, (const T*)x, part, q);
+        dispatch_flag(stats != nullptr, [&](auto k) {
+            hipLaunchKernelGGL((gn_apply_kernel<T, decltype(v)::value, decltype(k)::value>), grid, dim3(kGnBlock), 0, st, (const T*)x,
+                               (T*)y, w, b, part, q, eps, silu);
+        });
+    });
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 
@@ -837,81 +827,32 @@ extern "C" size_t mvi_groupnorm_workspace_bytes(int64_t N, int32_t C, int64_t sp
     return (size_t)(N * groups) * chunks_for(E, MVI_DT_F32) * 3 * sizeof(float);
 }
 
-static int gn_dispatch(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias, int stack3,
-                       int64_t Nv, int32_t T, int32_t C,
-                       int64_t spatial, int32_t groups, float eps, int32_t fuse_silu, int32_t dtype, void* workspace,
-                       size_t workspace_bytes, void* stream, int tokens = 0, uint32_t* sync = nullptr, float* stats = nullptr) {
-    if (Nv < 0 || T <= 0 || C <= 0 || groups <= 0 || spatial < 0 || C % groups != 0)
+extern "C" size_t mvi_groupnorm_sync_bytes(void) { return (2 * (size_t)mvi::kGnSyncGroups + 3) * sizeof(uint32_t); }
+
+// The one forward of the planes family. stats == NULL: the kStats = false instantiations (inference); else the kStats = true ones,
+// which also leave (mean, rstd) for mvi_groupnorm_backward — same launches, same arithmetic, y bit-identical.
+extern "C" int mvi_groupnorm_forward(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
+                                     float* stats, int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, float eps,
+                                     int32_t fuse_silu, int32_t out_layout, int32_t dtype, void* workspace, size_t workspace_bytes,
+                                     void* sync, size_t sync_bytes, void* stream) {
+    if (out_layout < MVI_GN_DY_PLANES || out_layout > MVI_GN_DY_TOKENS) return mvi::unet_fail(MVI_EINVAL, "groupnorm: unknown output layout");
+    if (out_layout != MVI_GN_DY_PLANES && x == y) return mvi::unet_fail(MVI_EINVAL, "groupnorm: this output layout cannot alias the input");
+    const int tokens = out_layout == MVI_GN_DY_TOKENS, stack3 = out_layout == MVI_GN_DY_STACK3;
+    if (tokens && T != 1) return mvi::unet_fail(MVI_EINVAL, "groupnorm (token-major output): T must be 1");
+    if (tokens) sync = nullptr;                            // the token-major form has no cluster kernel: its sync buffer is not looked at
+    if (sync && sync_bytes < mvi_groupnorm_sync_bytes()) return mvi::unet_fail(MVI_ENOMEM, "groupnorm: sync buffer too small");
+    if (videos < 0 || T <= 0 || C <= 0 || groups <= 0 || spatial < 0 || C % groups != 0)
         return mvi::unet_fail(MVI_EINVAL, "groupnorm: C must be a positive multiple of groups");
-    if (Nv == 0 || spatial == 0) return MVI_OK;
+    if (videos == 0 || spatial == 0) return MVI_OK;
     if (!x || !y || !weight || !bias || !workspace) return mvi::unet_fail(MVI_EINVAL, "groupnorm: NULL pointer");
-    if (Nv * groups > 65535) return mvi::unet_fail(MVI_EINVAL, "groupnorm: N*groups exceeds grid.y (65535)");
-    if (workspace_bytes < mvi_groupnorm_workspace_bytes(Nv * T, C, spatial, groups))
+    if (videos * groups > 65535) return mvi::unet_fail(MVI_EINVAL, "groupnorm: N*groups exceeds grid.y (65535)");
+    if (workspace_bytes < mvi_groupnorm_workspace_bytes(videos * T, C, spatial, groups))
         return mvi::unet_fail(MVI_ENOMEM, "groupnorm: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float* part = (float*)workspace;
     return mvi::dispatch_dtype(dtype, "groupnorm: unknown dtype", [&](auto t) {
-        const int rc = mvi::gn_launch<typename decltype(t)::type>(x, y, weight, bias, chan_bias, stack3, Nv, T, C, spatial, groups, eps, fuse_silu, part, st, tokens, sync, stats);
+        const int rc = mvi::gn_launch<typename decltype(t)::type>(x, y, weight, bias, chan_bias, stack3, videos, T, C, spatial, groups, eps,
+                                                                  fuse_silu, (float*)workspace, (hipStream_t)stream, tokens, (uint32_t*)sync, stats);
         if (rc == MVI_EINVAL)
             return mvi::unet_fail(MVI_EINVAL, "groupnorm (token-major output): C and spatial must be multiples of the 16-byte vector, 16-B aligned");
         return rc ? mvi::unet_fail(MVI_EHIP, "groupnorm: kernel launch failed") : MVI_OK;
     });
-}
-
-extern "C" int mvi_groupnorm_silu(const void* x, void* y, const float* weight, const float* bias, int64_t N,
-                                  int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu,
-                                  int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    return gn_dispatch(x, y, weight, bias, nullptr, 0, N, 1, C, spatial, groups, eps, fuse_silu, dtype, workspace, workspace_bytes, stream);
-}
-
-extern "C" int mvi_groupnorm_silu_temporal(const void* x, void* y, const float* weight, const float* bias,
-                                           int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups,
-                                           float eps, int32_t fuse_silu, int32_t dtype, void* workspace,
-                                           size_t workspace_bytes, void* stream) {
-    return gn_dispatch(x, y, weight, bias, nullptr, 0, videos, T, C, spatial, groups, eps, fuse_silu, dtype, workspace, workspace_bytes, stream);
-}
-
-extern "C" int mvi_groupnorm_silu_ex(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
-                                     int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, float eps,
-                                     int32_t fuse_silu, int32_t stack3, int32_t dtype, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-    if (stack3 && x == y) return mvi::unet_fail(MVI_EINVAL, "groupnorm: stack3 output cannot alias the input");
-    return gn_dispatch(x, y, weight, bias, chan_bias, stack3 ? 1 : 0, videos, T, C, spatial, groups, eps, fuse_silu, dtype, workspace, workspace_bytes, stream);
-}
-
-extern "C" size_t mvi_groupnorm_sync_bytes(void) { return (2 * (size_t)mvi::kGnSyncGroups + 3) * sizeof(uint32_t); }
-
-extern "C" int mvi_groupnorm_silu_ex2(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
-                                      int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, float eps,
-                                      int32_t fuse_silu, int32_t stack3, int32_t dtype, void* workspace,
-                                      size_t workspace_bytes, void* sync, size_t sync_bytes, void* stream) {
-    if (stack3 && x == y) return mvi::unet_fail(MVI_EINVAL, "groupnorm: stack3 output cannot alias the input");
-    if (sync && sync_bytes < mvi_groupnorm_sync_bytes()) return mvi::unet_fail(MVI_ENOMEM, "groupnorm: sync buffer too small");
-    return gn_dispatch(x, y, weight, bias, chan_bias, stack3 ? 1 : 0, videos, T, C, spatial, groups, eps, fuse_silu, dtype, workspace,
-                       workspace_bytes, stream, 0, (uint32_t*)sync);
-}
-
-// The forward under autograd: the dispatch of mvi_groupnorm_silu_ex2 / mvi_groupnorm_silu_tokens with the kStats instantiations
-extern "C" int mvi_groupnorm_forward_stats(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
-                                           float* stats, int64_t videos, int32_t T, int32_t C, int64_t spatial, int32_t groups, float eps,
-                                           int32_t fuse_silu, int32_t out_layout, int32_t dtype, void* workspace, size_t workspace_bytes,
-                                           void* sync, size_t sync_bytes, void* stream) {
-    if (!stats) return mvi::unet_fail(MVI_EINVAL, "groupnorm: stats is NULL");
-    if (out_layout < MVI_GN_DY_PLANES || out_layout > MVI_GN_DY_TOKENS) return mvi::unet_fail(MVI_EINVAL, "groupnorm: unknown output layout");
-    if (out_layout != MVI_GN_DY_PLANES && x == y) return mvi::unet_fail(MVI_EINVAL, "groupnorm: this output layout cannot alias the input");
-    if (out_layout == MVI_GN_DY_TOKENS) {
-        if (T != 1) return mvi::unet_fail(MVI_EINVAL, "groupnorm (token-major output): T must be 1");
-        return gn_dispatch(x, y, weight, bias, chan_bias, 0, videos, 1, C, spatial, groups, eps, fuse_silu, dtype, workspace, workspace_bytes,
-                           stream, 1, nullptr, stats);
-    }
-    if (sync && sync_bytes < mvi_groupnorm_sync_bytes()) return mvi::unet_fail(MVI_ENOMEM, "groupnorm: sync buffer too small");
-    return gn_dispatch(x, y, weight, bias, chan_bias, out_layout == MVI_GN_DY_STACK3 ? 1 : 0, videos, T, C, spatial, groups, eps, fuse_silu,
-                       dtype, workspace, workspace_bytes, stream, 0, (uint32_t*)sync, stats);
-}
-
-extern "C" int mvi_groupnorm_silu_tokens(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
-                                         int64_t N, int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu,
-                                         int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    if (x == y) return mvi::unet_fail(MVI_EINVAL, "groupnorm: token-major output cannot alias the input");
-    return gn_dispatch(x, y, weight, bias, chan_bias, 0, N, 1, C, spatial, groups, eps, fuse_silu, dtype, workspace, workspace_bytes, stream, 1);
 }

@@ -2,7 +2,7 @@
 // Why it exists: MIOpen runs the 3x3 convolutions of the SVD step with NHWC kernels and, for NCHW tensors, wraps them in
 // transposes (9.3 ms per step in `batched_transpose_*`; tools/experiments/conv_layout_probe.py: 817 -> 649 us for one level-0
 // convolution, bit-identical output). Inside a ResBlock (openaimodel.py:328-354) the first norm can already write tokens
-// (mvi_groupnorm_silu_tokens) and the last add can read them (mvi_tokens_to_planes_add); this is the norm BETWEEN the two
+// (mvi_groupnorm_forward, token-major output) and the last add can read them (mvi_tokens_to_planes_add); this is the norm BETWEEN the two
 // convolutions, whose input and output are both NHWC. The timestep-embedding bias is fused as in the NCHW kernels (chan_bias).
 //
 // Three launches, x read twice, y written once (the two-launch NCHW form's traffic):
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(1024) void gt_fused_kernel(const T* __restrict__ a,
 // video_model.py:71-75): a block merges the chunks of all its frames — they are consecutive in `part` — and writes every frame's
 // scale / offset (the frames differ in chan_bias only).
 // stats (nullable; NULL on the inference path): [videos * G, 2] fp32 = (mean of x + chan_bias, rstd) per (video, group), the table
-// the backward reads (mvi_groupnorm_tok2tok_forward_stats); written by the block of the video's first frame.
+// the backward reads (mvi_groupnorm_tok2tok_forward's stats); written by the block of the video's first frame.
 __global__ __launch_bounds__(kGtMergeThreads) void gt_merge_kernel(const float* __restrict__ part, const float* __restrict__ weight,
                                                        const float* __restrict__ chan_bias, float* __restrict__ scale_shift, int C, int G,
                                                        int chunks_per_frame, float eps, int frames, float* __restrict__ stats) {
@@ -418,7 +418,7 @@ static int gt_launch_split(const float* x, void* y2, const float* w, const float
 
 template <typename T>
 static int gt_launch(const void* x, void* y, const float* w, const float* b, const float* cb, int64_t N, int C, int64_t S, int G, float eps,
-                     int silu, float* ws, hipStream_t st, int frames = 1, float* stats = nullptr) {
+                     int silu, float* ws, hipStream_t st, int frames, float* stats) {
     constexpr int V = Io<T>::kVec;
     const int vpr = C / V, rp = gt_rows_per_pass(vpr);
     const int chunks = (int)((S + kGtPasses * rp - 1) / (kGtPasses * rp));
@@ -463,9 +463,11 @@ extern "C" size_t mvi_groupnorm_tok2tok_workspace_bytes(int64_t N, int32_t C, in
     return (size_t)(N * chunks * groups * 3 + N * C * 2) * sizeof(float);
 }
 
-static int tok2tok_impl(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias, int64_t N, int32_t C,
-                        int64_t spatial, int32_t groups, float eps, int32_t fuse_silu, int32_t frames, int32_t dtype, void* workspace,
-                        size_t workspace_bytes, void* stream, float* stats = nullptr) {
+// The one forward of the token-major family. stats == NULL: inference; else the merge launch also leaves stats [N / frames * groups, 2]
+// fp32 = (mean, rstd) for mvi_groupnorm_tok2tok_backward (csrc/groupnorm_bwd.hip) — the same launches, y bit-identical.
+extern "C" int mvi_groupnorm_tok2tok_forward(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
+                                             float* stats, int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups, float eps,
+                                             int32_t fuse_silu, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
     if (N == 0 || spatial == 0) return MVI_OK;
     if (!gt_geometry_ok(N, C, spatial, groups, dtype))
         return mvi::unet_fail(MVI_EINVAL, "groupnorm_tok2tok: C must be a multiple of groups (<= 64) and of the 16-byte vector width");
@@ -497,29 +499,6 @@ extern "C" int mvi_groupnorm_silu_tok2tok_pre(const void* x, void* y, const floa
         return mvi::gt_launch_pre<typename decltype(t)::type>(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, part, chunks_per_sample, (float*)workspace, st, frames)
                    ? mvi::unet_fail(MVI_EHIP, "groupnorm_tok2tok_pre: kernel launch failed") : MVI_OK;
     });
-}
-
-extern "C" int mvi_groupnorm_silu_tok2tok(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
-                                          int64_t N, int32_t C, int64_t spatial, int32_t groups, float eps, int32_t fuse_silu,
-                                          int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    return tok2tok_impl(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, 1, dtype, workspace, workspace_bytes, stream);
-}
-
-extern "C" int mvi_groupnorm_silu_tok2tok_frames(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
-                                                 int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups, float eps,
-                                                 int32_t fuse_silu, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    return tok2tok_impl(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, frames, dtype, workspace, workspace_bytes, stream);
-}
-
-// The forward for training: mvi_groupnorm_silu_tok2tok_frames (the same launches, y bit-identical) that also leaves
-// stats [N / frames * groups, 2] fp32 = (mean, rstd) for mvi_groupnorm_tok2tok_backward (csrc/groupnorm_bwd.hip).
-extern "C" int mvi_groupnorm_tok2tok_forward_stats(const void* x, void* y, const float* weight, const float* bias, const float* chan_bias,
-                                                   float* stats, int64_t N, int32_t frames, int32_t C, int64_t spatial, int32_t groups,
-                                                   float eps, int32_t fuse_silu, int32_t dtype, void* workspace, size_t workspace_bytes,
-                                                   void* stream) {
-    if (!stats && N != 0 && spatial != 0) return mvi::unet_fail(MVI_EINVAL, "groupnorm_tok2tok_forward_stats: NULL stats");
-    return tok2tok_impl(x, y, weight, bias, chan_bias, N, C, spatial, groups, eps, fuse_silu, frames, dtype, workspace, workspace_bytes, stream,
-                        stats);
 }
 
 // GroupNorm(+SiLU) of an fp32 token-major tensor x [N, S, C] written as split bf16 y2 [N, S, 2 C] = (hi | lo) (see gt_apply_split_kernel);

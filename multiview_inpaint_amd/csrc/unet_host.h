@@ -1,11 +1,12 @@
 // The host side that the UNet kernel files share: the status codes and dtype tags of the C ABI, the error record, and the
-// dtype -> template-argument dispatch of the entry points, and the opt-in of a kernel to more than 64 KiB of dynamic LDS.
+// dtype -> and flag -> template-argument dispatch of the entry points, and the opt-in of a kernel to more than 64 KiB of dynamic LDS.
 #pragma once
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/mvi_raster.h"        // MVI_OK / MVI_E*
 #include "../../include/mvi_unet_ops.h"      // MVI_DT_*
@@ -34,6 +35,10 @@ template <typename F> int dispatch_dtype16(int dtype, const char* what, F&& f) {
         default: return unet_fail(MVI_EINVAL, what);
     }
 }
+
+// The same for a bool template argument: f receives std::true_type or std::false_type and the site spells its launch once,
+//     dispatch_flag(stats != nullptr, [&](auto k) { hipLaunchKernelGGL((kernel<T, decltype(k)::value>), ...); });
+template <typename F> auto dispatch_flag(bool on, F&& f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
 
 // A launch with more than 64 KiB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize set on the kernel, once per device.
 // kKern is the kernel's address, so the flag word (one bit per device) is per kernel by construction. Launchers run on any thread

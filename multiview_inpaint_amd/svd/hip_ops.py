@@ -1,5 +1,6 @@
 """GPU implementations of multiview_inpaint_amd.svd.ops through the C-ABI HIP library
 (include/mvi_unet_ops.h). Importing this module without libmvi_hip.so raises."""
+import collections
 import ctypes as C
 import math
 
@@ -93,7 +94,7 @@ _gn_sync = {}
 
 def _groupnorm_sync(dev):
     """Zeroed once per (device, stream): the counters of the one-launch cluster GroupNorm (include/mvi_unet_ops.h,
-    mvi_groupnorm_silu_ex2) — the kernels leave them zeroed, and launches that share a stream never overlap."""
+    mvi_groupnorm_forward) — the kernels leave them zeroed, and launches that share a stream never overlap."""
     key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
     b = _gn_sync.get(key)
     if b is None:
@@ -143,51 +144,7 @@ def _chan_bias(what, chan_bias, N, C_):
     return cb
 
 
-def _gn(x, T, num_groups, weight, bias, eps, silu, chan_bias, stack3):
-    L = _lib.lib()
-    xc, N, Cc, S, cb = _gn_args("group_norm", x, chan_bias)
-    y = torch.empty((N, 3 * Cc, *xc.shape[2:]) if stack3 else xc.shape, dtype=x.dtype, device=x.device)
-    w, b = _f32(weight), _f32(bias)
-    ws = _workspace(xc.device, L.mvi_groupnorm_workspace_bytes(N, Cc, S, num_groups))
-    sync = _groupnorm_sync(xc.device)
-    with torch.cuda.device(xc.device), _Timed("groupnorm", (2.0 + 2.0 * bool(stack3)) * xc.numel() * xc.element_size(), xc.device):
-        _check(L.mvi_groupnorm_silu_ex2(xc.data_ptr(), y.data_ptr(), w.data_ptr(), b.data_ptr(), _ptr(cb), N // T, int(T), Cc, S, num_groups,
-                                        float(eps), int(bool(silu)), int(bool(stack3)), _DT[x.dtype], ws.data_ptr(), ws.numel(), sync.data_ptr(),
-                                        sync.numel(), _stream(xc.device)), "group_norm")
-    return y
-
-
-def group_norm_silu(x, num_groups, weight, bias, eps, silu, chan_bias=None):
-    return _gn(x, 1, num_groups, weight, bias, eps, silu, chan_bias, False)
-
-
-def group_norm_silu_tokens(x, num_groups, weight, bias, eps, silu, chan_bias=None):
-    """GroupNorm(+SiLU) of x [N, C, *spatial] returned token-major [N, prod(spatial), C]."""
-    L = _lib.lib()
-    xc, N, Cc, S, cb = _gn_args("group_norm", x, chan_bias)
-    y = torch.empty((N, S, Cc), dtype=x.dtype, device=x.device)
-    ws = _workspace(xc.device, L.mvi_groupnorm_workspace_bytes(N, Cc, S, num_groups))
-    with torch.cuda.device(xc.device), _Timed("groupnorm_tokens", 2.0 * xc.numel() * xc.element_size(), xc.device):
-        _check(L.mvi_groupnorm_silu_tokens(xc.data_ptr(), y.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(), _ptr(cb), N, Cc, S,
-                                           num_groups, float(eps), int(bool(silu)), _DT[x.dtype], ws.data_ptr(), ws.numel(), _stream(xc.device)),
-                                           "group_norm_tokens")
-    return y
-
-
-def group_norm_silu_frames(x, T, num_groups, weight, bias, eps, silu, chan_bias=None, stack3=False):
-    """x [(b T), C, *spatial] contiguous; statistics per (video, group) over all T frames."""
-    return _gn(x, int(T), num_groups, weight, bias, eps, silu, chan_bias, stack3)
-
-
 GN_PLANES, GN_STACK3, GN_TOKENS = 0, 1, 2      # MVI_GN_DY_*: the layout the forward writes y in = the layout dy arrives in
-
-
-def group_norm_backward_supported(N, C, S, num_groups, T, dtype, layout=GN_PLANES):
-    """Whether group_norm_forward_stats / group_norm_backward compute x [N = videos * T, C, S] (mvi_groupnorm_backward_supported, a
-    host-only function)."""
-    if dtype not in _DT or T <= 0 or N % T != 0 or num_groups <= 0 or C % num_groups != 0:
-        return False
-    return bool(_lib.lib().mvi_groupnorm_backward_supported(int(N // T), int(T), int(C), int(S), int(num_groups), int(layout), _DT[dtype]))
 
 
 def _gn_args(what, x, chan_bias):
@@ -199,25 +156,110 @@ def _gn_args(what, x, chan_bias):
     return xc, N, Cc, S, _chan_bias(what, chan_bias, N, Cc)
 
 
+def _gn_forward(x, T, num_groups, weight, bias, eps, silu, chan_bias, layout, want_stats, kind):
+    """The one forward of x [N = videos * T, C, *spatial] (mvi_groupnorm_forward): (y in `layout`, stats), stats the fp32 (mean, rstd)
+    table [N / T * groups, 2] when want_stats, else None — the same kernels and the same y either way."""
+    L = _lib.lib()
+    what = "group_norm_forward_stats" if want_stats else "group_norm"
+    xc, N, Cc, S, cb = _gn_args(what, x, chan_bias)
+    shape = (N, S, Cc) if layout == GN_TOKENS else (N, 3 * Cc, *xc.shape[2:]) if layout == GN_STACK3 else xc.shape
+    y = torch.empty(shape, dtype=x.dtype, device=x.device)
+    stats = torch.empty((N // T * num_groups, 2), dtype=torch.float32, device=x.device) if want_stats else None
+    ws = _workspace(xc.device, L.mvi_groupnorm_workspace_bytes(N, Cc, S, num_groups))
+    sync = None if layout == GN_TOKENS else _groupnorm_sync(xc.device)      # token-major output has no cluster form: nothing allocated
+    work = (2.0 + 2.0 * (layout == GN_STACK3)) * xc.numel() * xc.element_size()
+    with torch.cuda.device(xc.device), _Timed(kind, work, xc.device):
+        _check(L.mvi_groupnorm_forward(xc.data_ptr(), y.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(), _ptr(cb), _ptr(stats),
+                                       N // T, int(T), Cc, S, num_groups, float(eps), int(bool(silu)), int(layout), _DT[x.dtype], ws.data_ptr(),
+                                       ws.numel(), _ptr(sync), 0 if sync is None else sync.numel(), _stream(xc.device)),
+               "group_norm_tokens" if kind == "groupnorm_tokens" else what)
+    return y, stats
+
+
+def group_norm_silu(x, num_groups, weight, bias, eps, silu, chan_bias=None):
+    return _gn_forward(x, 1, num_groups, weight, bias, eps, silu, chan_bias, GN_PLANES, False, "groupnorm")[0]
+
+
+def group_norm_silu_tokens(x, num_groups, weight, bias, eps, silu, chan_bias=None):
+    """GroupNorm(+SiLU) of x [N, C, *spatial] returned token-major [N, prod(spatial), C]."""
+    return _gn_forward(x, 1, num_groups, weight, bias, eps, silu, chan_bias, GN_TOKENS, False, "groupnorm_tokens")[0]
+
+
+def group_norm_silu_frames(x, T, num_groups, weight, bias, eps, silu, chan_bias=None, stack3=False):
+    """x [(b T), C, *spatial] contiguous; statistics per (video, group) over all T frames."""
+    return _gn_forward(x, int(T), num_groups, weight, bias, eps, silu, chan_bias, GN_STACK3 if stack3 else GN_PLANES, False, "groupnorm")[0]
+
+
 def group_norm_forward_stats(x, T, num_groups, weight, bias, eps, silu, chan_bias=None, layout=GN_PLANES):
     """The forward of group_norm_silu / _frames (layout GN_PLANES, GN_STACK3) or group_norm_silu_tokens (GN_TOKENS) — same kernels, y
     bit-identical — that also returns the fp32 (mean, rstd) of every (video, group) [N / T * groups, 2] for group_norm_backward."""
-    L = _lib.lib()
-    xc, N, Cc, S, cb = _gn_args("group_norm_forward_stats", x, chan_bias)
-    if layout == GN_TOKENS:
-        y = torch.empty((N, S, Cc), dtype=x.dtype, device=x.device)
-    else:
-        y = torch.empty((N, 3 * Cc, *xc.shape[2:]) if layout == GN_STACK3 else xc.shape, dtype=x.dtype, device=x.device)
-    stats = torch.empty((N // T * num_groups, 2), dtype=torch.float32, device=x.device)
-    ws = _workspace(xc.device, L.mvi_groupnorm_workspace_bytes(N, Cc, S, num_groups))
-    sync = None if layout == GN_TOKENS else _groupnorm_sync(xc.device)
-    work = (2.0 + 2.0 * (layout == GN_STACK3)) * xc.numel() * xc.element_size()
-    with torch.cuda.device(xc.device), _Timed("groupnorm_stats_fwd", work, xc.device):
-        _check(L.mvi_groupnorm_forward_stats(xc.data_ptr(), y.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(), _ptr(cb), stats.data_ptr(),
-                                             N // T, int(T), Cc, S, num_groups, float(eps), int(bool(silu)), int(layout), _DT[x.dtype], ws.data_ptr(),
-                                             ws.numel(), _ptr(sync), 0 if sync is None else sync.numel(), _stream(xc.device)),
-                                             "group_norm_forward_stats")
-    return y, stats
+    return _gn_forward(x, T, num_groups, weight, bias, eps, silu, chan_bias, layout, True, "groupnorm_stats_fwd")
+
+
+def group_norm_backward_supported(N, C, S, num_groups, T, dtype, layout=GN_PLANES):
+    """Whether group_norm_forward_stats / group_norm_backward compute x [N = videos * T, C, S] (mvi_groupnorm_backward_supported, a
+    host-only function)."""
+    if dtype not in _DT or T <= 0 or N % T != 0 or num_groups <= 0 or C % num_groups != 0:
+        return False
+    return bool(_lib.lib().mvi_groupnorm_backward_supported(int(N // T), int(T), int(C), int(S), int(num_groups), int(layout), _DT[dtype]))
+
+
+def _tok2tok_args(what, t, chan_bias, frames=1):
+    if t.dtype not in _DT:
+        raise TypeError(f"{what}: unsupported dtype {t.dtype}")
+    if t.dim() != 3:
+        raise ValueError(f"{what}: token-major [N, S, C] expected, got {tuple(t.shape)}")
+    tc = _contig(t)
+    N, S, Cc = tc.shape
+    if frames < 1 or N % frames:
+        raise ValueError(f"{what}: {N} samples are not whole videos of {frames} frames")
+    return tc, N, Cc, S, _chan_bias(what, chan_bias, N, Cc)
+
+
+# One family of the backward: its names in messages and in PROFILE, the decode of x into (xc, N, C, S, chan_bias), dy's shape, the C
+# entry with its workspace function, and how each takes the shape (T = the frames that share statistics).
+_GnBackward = collections.namedtuple("_GnBackward", "what forward kind decode dy_shape entry workspace ws_dims dims")
+_GN_BACKWARD = {
+    "planes": _GnBackward(
+        "group_norm_backward", "group_norm_forward_stats", "groupnorm_bwd", lambda what, x, cb, T: _gn_args(what, x, cb),
+        lambda xc, N, Cc, S, layout: (N, S, Cc) if layout == GN_TOKENS else (N, (3 if layout == GN_STACK3 else 1) * Cc, *xc.shape[2:]),
+        "mvi_groupnorm_backward", "mvi_groupnorm_backward_workspace_bytes",
+        lambda N, T, Cc, S, G, dt: (N // T, T, Cc, S, G), lambda N, T, Cc, S, G, silu, layout, dt: (N // T, T, Cc, S, G, silu, layout, dt)),
+    "tok2tok": _GnBackward(
+        "group_norm_tok2tok_backward", "group_norm_tok2tok_forward_stats", "groupnorm_tok2tok_bwd", _tok2tok_args,
+        lambda tc, N, Cc, S, layout: tuple(tc.shape),
+        "mvi_groupnorm_tok2tok_backward", "mvi_groupnorm_tok2tok_backward_workspace_bytes",
+        lambda N, T, Cc, S, G, dt: (N, T, Cc, S, G, dt), lambda N, T, Cc, S, G, silu, layout, dt: (N, T, Cc, S, G, silu, dt)),
+}
+
+
+def _gn_backward(family, dy, x, stats, T, num_groups, weight, bias, silu, chan_bias, layout, need_dx, need_dparams, need_dchan_bias):
+    L, f = _lib.lib(), _GN_BACKWARD[family]
+    xc, N, Cc, S, cb = f.decode(f.what, x, chan_bias, T)
+    want = f.dy_shape(xc, N, Cc, S, layout)
+    if dy.dtype != x.dtype or tuple(dy.shape) != want or not dy.is_contiguous():
+        raise ValueError(f"{f.what}: dy must be contiguous {x.dtype} {want}, got {dy.dtype} {tuple(dy.shape)}")
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (N // T * num_groups, 2) or not stats.is_contiguous():
+        raise ValueError(f"{f.what}: stats must be the fp32 [videos * groups, 2] table of {f.forward}")
+    if need_dchan_bias and cb is None:
+        raise ValueError(f"{f.what}: dchan_bias asked for without chan_bias")
+    nbytes = int(getattr(L, f.workspace)(*f.ws_dims(N, int(T), Cc, S, num_groups, _DT[x.dtype])))
+    if nbytes == 0 and xc.numel():
+        raise ValueError(f"{f.what}: unsupported shape {tuple(x.shape)} / {num_groups} groups")
+    f32 = dict(dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(xc) if need_dx else None
+    dw = torch.empty(Cc, **f32) if need_dparams else None
+    db = torch.empty(Cc, **f32) if need_dparams else None
+    dcb = torch.empty((N, Cc), **f32) if need_dchan_bias else None
+    ws = _workspace(x.device, nbytes)
+    nd = 3 if layout == GN_STACK3 else 1                 # dy blocks read per element
+    work = ((1.0 + nd) + (2.0 + nd) * bool(need_dx)) * xc.numel() * xc.element_size()     # reduce pass (+ apply pass) bytes
+    with torch.cuda.device(x.device), _Timed(f.kind + "_params" if need_dparams else f.kind, work, x.device):
+        _check(getattr(L, f.entry)(xc.data_ptr(), dy.data_ptr(), stats.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(), _ptr(cb),
+                                   _ptr(dx), _ptr(dw), _ptr(db), _ptr(dcb),
+                                   *f.dims(N, int(T), Cc, S, num_groups, int(bool(silu)), int(layout), _DT[x.dtype]),
+                                   ws.data_ptr(), ws.numel(), _stream(x.device)), f.what)
+    return dx, dw, db, dcb
 
 
 def group_norm_backward(dy, x, stats, T, num_groups, weight, bias, silu, chan_bias=None, layout=GN_PLANES, need_dx=True,
@@ -226,29 +268,7 @@ def group_norm_backward(dy, x, stats, T, num_groups, weight, bias, silu, chan_bi
     and shape, the others fp32; outputs not asked for are None and cost nothing (need_dparams adds one small launch; the PROFILE kind
     is then "groupnorm_bwd_params" instead of "groupnorm_bwd"). dy: contiguous, x's dtype, in the layout the forward wrote y in.
     Deterministic."""
-    L = _lib.lib()
-    xc, N, Cc, S, cb = _gn_args("group_norm_backward", x, chan_bias)
-    want = (N, S, Cc) if layout == GN_TOKENS else (N, (3 if layout == GN_STACK3 else 1) * Cc, *xc.shape[2:])
-    if dy.dtype != x.dtype or tuple(dy.shape) != want or not dy.is_contiguous():
-        raise ValueError(f"group_norm_backward: dy must be contiguous {x.dtype} {want}, got {dy.dtype} {tuple(dy.shape)}")
-    if stats.dtype != torch.float32 or tuple(stats.shape) != (N // T * num_groups, 2) or not stats.is_contiguous():
-        raise ValueError("group_norm_backward: stats must be the fp32 [videos * groups, 2] table of group_norm_forward_stats")
-    if need_dchan_bias and cb is None:
-        raise ValueError("group_norm_backward: dchan_bias asked for without chan_bias")
-    f32 = dict(dtype=torch.float32, device=x.device)
-    dx = torch.empty_like(xc) if need_dx else None
-    dw = torch.empty(Cc, **f32) if need_dparams else None
-    db = torch.empty(Cc, **f32) if need_dparams else None
-    dcb = torch.empty((N, Cc), **f32) if need_dchan_bias else None
-    nbytes = int(L.mvi_groupnorm_backward_workspace_bytes(N // T, int(T), Cc, S, num_groups))
-    ws = _workspace(x.device, nbytes)
-    nd = 3 if layout == GN_STACK3 else 1                 # dy blocks read per element
-    work = ((1.0 + nd) + (2.0 + nd) * bool(need_dx)) * xc.numel() * xc.element_size()     # reduce pass (+ apply pass) bytes
-    with torch.cuda.device(x.device), _Timed("groupnorm_bwd_params" if need_dparams else "groupnorm_bwd", work, x.device):
-        _check(L.mvi_groupnorm_backward(xc.data_ptr(), dy.data_ptr(), stats.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(), _ptr(cb),
-                                        _ptr(dx), _ptr(dw), _ptr(db), _ptr(dcb), N // T, int(T), Cc, S, num_groups, int(bool(silu)), int(layout),
-                                        _DT[x.dtype], ws.data_ptr(), ws.numel(), _stream(x.device)), "group_norm_backward")
-    return dx, dw, db, dcb
+    return _gn_backward("planes", dy, x, stats, T, num_groups, weight, bias, silu, chan_bias, layout, need_dx, need_dparams, need_dchan_bias)
 
 
 def _check_qkv(what, q, k, v, shapes=True):
@@ -1569,38 +1589,37 @@ def group_norm_tok2tok_supported(N, C_, S, groups, dtype):
     return _lib.lib().mvi_groupnorm_tok2tok_workspace_bytes(int(N), int(C_), int(S), int(groups), _DT[dtype]) != 0
 
 
+def _gn_tok2tok_forward(what, t, num_groups, weight, bias, eps, silu, chan_bias, frames, want_stats, kind, work, partials=None):
+    """The one forward of token-major t [N, S, C] (mvi_groupnorm_tok2tok_forward; with `partials`, mvi_groupnorm_silu_tok2tok_pre):
+    (y, stats), stats the fp32 (mean, rstd) table [N / frames * groups, 2] when want_stats, else None — the same launches and y either way."""
+    L = _lib.lib()
+    tc, N, Cc, S, cb = _tok2tok_args(what, t, chan_bias, frames)
+    nbytes = L.mvi_groupnorm_tok2tok_workspace_bytes(N, Cc, S, num_groups, _DT[t.dtype])
+    if nbytes == 0:
+        raise ValueError(f"{what}: unsupported shape {tuple(t.shape)} / {num_groups} groups")
+    y = torch.empty_like(tc)
+    stats = torch.empty((N // frames * num_groups, 2), dtype=torch.float32, device=t.device) if want_stats else None
+    ws = _workspace(tc.device, nbytes)
+    head = (tc.data_ptr(), y.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(), _ptr(cb))
+    dims = (N, int(frames), Cc, S, num_groups, float(eps), int(bool(silu)), _DT[t.dtype])
+    with torch.cuda.device(tc.device), _Timed(kind, work * tc.numel() * tc.element_size(), tc.device):
+        if partials is None:
+            _check(L.mvi_groupnorm_tok2tok_forward(*head, _ptr(stats), *dims, ws.data_ptr(), ws.numel(), _stream(tc.device)), what)
+        else:
+            _check(L.mvi_groupnorm_silu_tok2tok_pre(*head, *dims, partials.part.data_ptr(), partials.chunks, ws.data_ptr(), ws.numel(),
+                                                    _stream(tc.device)), what + " (pre)")
+    return y, stats
+
+
 def group_norm_silu_tok2tok(t, num_groups, weight, bias, eps, silu, chan_bias=None, frames=1, partials=None):
     """GroupNorm(+SiLU) of token-major t [N, S, C] -> [N, S, C] (csrc/groupnorm_tokens.hip); frames > 1: statistics over the `frames`
     consecutive samples of a video (the temporal ResBlock's norm), chan_bias still per sample. partials (GnPartials): the statistics
     the producer of t left (same groups, same chan_bias object) — no statistics pass (mvi_groupnorm_silu_tok2tok_pre)."""
-    L = _lib.lib()
-    if t.dtype not in _DT:
-        raise TypeError(f"group_norm_tok2tok: unsupported dtype {t.dtype}")
-    tc = _contig(t)
-    N, S, Cc = tc.shape
-    nbytes = L.mvi_groupnorm_tok2tok_workspace_bytes(N, Cc, S, num_groups, _DT[t.dtype])
-    if nbytes == 0:
-        raise ValueError(f"group_norm_tok2tok: unsupported shape {tuple(t.shape)} / {num_groups} groups")
-    cb = _chan_bias("group_norm_tok2tok", chan_bias, N, Cc)
-    y = torch.empty_like(tc)
-    ws = _workspace(tc.device, nbytes)
-    if frames < 1 or N % frames:
-        raise ValueError(f"group_norm_tok2tok: {N} samples are not whole videos of {frames} frames")
-    if partials is not None:
-        if partials.groups != num_groups or (partials.chan_bias is None) != (chan_bias is None) or \
-                partials.part.numel() != N * partials.chunks * num_groups * 3:
-            raise ValueError("group_norm_tok2tok: the producer's statistics do not belong to this norm")
-        with torch.cuda.device(tc.device), _Timed("groupnorm_tok2tok", 2.0 * tc.numel() * tc.element_size(), tc.device):
-            _check(L.mvi_groupnorm_silu_tok2tok_pre(tc.data_ptr(), y.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(), _ptr(cb), N,
-                                                    int(frames), Cc, S, num_groups, float(eps), int(bool(silu)), _DT[t.dtype],
-                                                    partials.part.data_ptr(), partials.chunks, ws.data_ptr(), ws.numel(), _stream(tc.device)),
-                                                    "group_norm_tok2tok (pre)")
-        return y
-    with torch.cuda.device(tc.device), _Timed("groupnorm_tok2tok", 2.0 * tc.numel() * tc.element_size(), tc.device):
-        _check(L.mvi_groupnorm_silu_tok2tok_frames(tc.data_ptr(), y.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(), _ptr(cb), N,
-                                                   int(frames), Cc, S, num_groups, float(eps), int(bool(silu)), _DT[t.dtype], ws.data_ptr(),
-                                                   ws.numel(), _stream(tc.device)), "group_norm_tok2tok")
-    return y
+    if partials is not None and (partials.groups != num_groups or (partials.chan_bias is None) != (chan_bias is None)
+                                 or partials.part.numel() != t.shape[0] * partials.chunks * num_groups * 3):
+        raise ValueError("group_norm_tok2tok: the producer's statistics do not belong to this norm")
+    return _gn_tok2tok_forward("group_norm_tok2tok", t, num_groups, weight, bias, eps, silu, chan_bias, frames, False, "groupnorm_tok2tok", 2.0,
+                               partials)[0]
 
 
 def group_norm_tok2tok_backward_supported(N, C_, S, num_groups, frames, dtype):
@@ -1611,33 +1630,11 @@ def group_norm_tok2tok_backward_supported(N, C_, S, num_groups, frames, dtype):
     return bool(_lib.lib().mvi_groupnorm_tok2tok_backward_supported(int(N), int(frames), int(C_), int(S), int(num_groups), _DT[dtype]))
 
 
-def _tok2tok_args(what, t, chan_bias):
-    if t.dtype not in _DT:
-        raise TypeError(f"{what}: unsupported dtype {t.dtype}")
-    if t.dim() != 3:
-        raise ValueError(f"{what}: token-major [N, S, C] expected, got {tuple(t.shape)}")
-    tc = _contig(t)
-    N, S, Cc = tc.shape
-    return tc, N, S, Cc, _chan_bias(what, chan_bias, N, Cc)
-
-
 def group_norm_tok2tok_forward_stats(t, num_groups, weight, bias, eps, silu, chan_bias=None, frames=1):
     """The forward of group_norm_silu_tok2tok (same kernels, y bit-identical) that also returns the fp32 (mean, rstd) of every
     (video, group) [N / frames * groups, 2] for group_norm_tok2tok_backward."""
-    L = _lib.lib()
-    tc, N, S, Cc, cb = _tok2tok_args("group_norm_tok2tok_forward_stats", t, chan_bias)
-    nbytes = L.mvi_groupnorm_tok2tok_workspace_bytes(N, Cc, S, num_groups, _DT[t.dtype])
-    if nbytes == 0 or frames < 1 or N % frames:
-        raise ValueError(f"group_norm_tok2tok_forward_stats: unsupported shape {tuple(t.shape)} / {num_groups} groups / {frames} frames")
-    y = torch.empty_like(tc)
-    stats = torch.empty((N // frames * num_groups, 2), dtype=torch.float32, device=t.device)
-    ws = _workspace(tc.device, nbytes)
-    with torch.cuda.device(tc.device), _Timed("groupnorm_tok2tok_stats_fwd", 3.0 * tc.numel() * tc.element_size(), tc.device):
-        _check(L.mvi_groupnorm_tok2tok_forward_stats(tc.data_ptr(), y.data_ptr(), _f32(weight).data_ptr(), _f32(bias).data_ptr(), _ptr(cb),
-                                                     stats.data_ptr(), N, int(frames), Cc, S, num_groups, float(eps), int(bool(silu)),
-                                                     _DT[t.dtype], ws.data_ptr(), ws.numel(), _stream(tc.device)),
-               "group_norm_tok2tok_forward_stats")
-    return y, stats
+    return _gn_tok2tok_forward("group_norm_tok2tok_forward_stats", t, num_groups, weight, bias, eps, silu, chan_bias, frames, True,
+                               "groupnorm_tok2tok_stats_fwd", 3.0)
 
 
 def group_norm_tok2tok_backward(dy, t, stats, num_groups, weight, bias, silu, chan_bias=None, frames=1, need_dx=True, need_dparams=False,
@@ -1646,32 +1643,8 @@ def group_norm_tok2tok_backward(dy, t, stats, num_groups, weight, bias, silu, ch
     gn_bwd_tok_*): dx in t's dtype and shape, the others fp32; outputs not asked for are None and cost nothing (need_dparams adds one
     small launch; the PROFILE kind is then "groupnorm_tok2tok_bwd_params" instead of "groupnorm_tok2tok_bwd"). dy: contiguous, t's dtype
     and shape. Deterministic."""
-    L = _lib.lib()
-    tc, N, S, Cc, cb = _tok2tok_args("group_norm_tok2tok_backward", t, chan_bias)
-    if dy.dtype != t.dtype or dy.shape != tc.shape or not dy.is_contiguous():
-        raise ValueError(f"group_norm_tok2tok_backward: dy must be contiguous {t.dtype} {tuple(tc.shape)}, got {dy.dtype} {tuple(dy.shape)}")
-    if frames < 1 or N % frames:
-        raise ValueError(f"group_norm_tok2tok_backward: {N} samples are not whole videos of {frames} frames")
-    if stats.dtype != torch.float32 or tuple(stats.shape) != (N // frames * num_groups, 2) or not stats.is_contiguous():
-        raise ValueError("group_norm_tok2tok_backward: stats must be the fp32 [videos * groups, 2] table of group_norm_tok2tok_forward_stats")
-    if need_dchan_bias and cb is None:
-        raise ValueError("group_norm_tok2tok_backward: dchan_bias asked for without chan_bias")
-    nbytes = int(L.mvi_groupnorm_tok2tok_backward_workspace_bytes(N, int(frames), Cc, S, num_groups, _DT[t.dtype]))
-    if nbytes == 0:
-        raise ValueError(f"group_norm_tok2tok_backward: unsupported shape {tuple(t.shape)} / {num_groups} groups")
-    f32 = dict(dtype=torch.float32, device=t.device)
-    dx = torch.empty_like(tc) if need_dx else None
-    dw = torch.empty(Cc, **f32) if need_dparams else None
-    db = torch.empty(Cc, **f32) if need_dparams else None
-    dcb = torch.empty((N, Cc), **f32) if need_dchan_bias else None
-    ws = _workspace(t.device, nbytes)
-    work = (2.0 + 3.0 * bool(need_dx)) * tc.numel() * tc.element_size()           # reduce pass (+ apply pass) bytes
-    with torch.cuda.device(t.device), _Timed("groupnorm_tok2tok_bwd_params" if need_dparams else "groupnorm_tok2tok_bwd", work, t.device):
-        _check(L.mvi_groupnorm_tok2tok_backward(tc.data_ptr(), dy.data_ptr(), stats.data_ptr(), _f32(weight).data_ptr(),
-                                                _f32(bias).data_ptr(), _ptr(cb), _ptr(dx), _ptr(dw), _ptr(db), _ptr(dcb), N, int(frames), Cc, S,
-                                                num_groups, int(bool(silu)), _DT[t.dtype], ws.data_ptr(), ws.numel(), _stream(t.device)),
-               "group_norm_tok2tok_backward")
-    return dx, dw, db, dcb
+    return _gn_backward("tok2tok", dy, t, stats, frames, num_groups, weight, bias, silu, chan_bias, GN_PLANES, need_dx, need_dparams,
+                        need_dchan_bias)
 
 
 def attention_kernel_variant(Sq, Sk, D, dtype):

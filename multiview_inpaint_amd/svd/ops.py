@@ -109,16 +109,22 @@ def group_norm_backward_pays(N, C, S, T, dtype, layout=0):
     return N * C * S >= GROUPNORM_BACKWARD_MIN_ELEMENTS[layout]
 
 
+_GN_TOK2TOK = 3      # beside hip_ops.GN_PLANES / GN_STACK3 / GN_TOKENS (y's layout, x in planes): token-major in AND out, T carries `frames`
+
+
 class _GroupNormFn(torch.autograd.Function):
-    """GroupNorm(+SiLU) on the HIP kernels with a deterministic HIP backward, behind group_norm, group_norm_tokens and
-    group_norm_frames. Holds x, weight, bias, chan_bias and the (mean, rstd) table — not y, nothing tensor-sized in fp32; nothing is
-    cached outside ctx, so torch.utils.checkpoint may re-run the forward."""
+    """GroupNorm(+SiLU) on the HIP kernels with a deterministic HIP backward, behind group_norm, group_norm_tokens, group_norm_frames
+    and (layout _GN_TOK2TOK) group_norm_tok2tok. Holds x, weight, bias, chan_bias and the (mean, rstd) table — not y, nothing
+    tensor-sized in fp32; nothing is cached outside ctx, so torch.utils.checkpoint may re-run the forward."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, chan_bias, num_groups, eps, silu, T, layout):
         from . import hip_ops
         xc = x if x.is_contiguous() else x.contiguous()
-        y, stats = hip_ops.group_norm_forward_stats(xc, T, num_groups, weight, bias, eps, silu, chan_bias=chan_bias, layout=layout)
+        if layout == _GN_TOK2TOK:
+            y, stats = hip_ops.group_norm_tok2tok_forward_stats(xc, num_groups, weight, bias, eps, silu, chan_bias=chan_bias, frames=T)
+        else:
+            y, stats = hip_ops.group_norm_forward_stats(xc, T, num_groups, weight, bias, eps, silu, chan_bias=chan_bias, layout=layout)
         ctx.save_for_backward(xc, weight, bias, chan_bias, stats)
         ctx.cfg = (num_groups, bool(silu), T, layout)
         return y
@@ -130,21 +136,32 @@ class _GroupNormFn(torch.autograd.Function):
         x, weight, bias, chan_bias, stats = ctx.saved_tensors
         num_groups, silu, T, layout = ctx.cfg
         n = ctx.needs_input_grad
-        dx, dw, db, dcb = hip_ops.group_norm_backward(dy.contiguous(), x, stats, T, num_groups, weight, bias, silu, chan_bias=chan_bias,
-                                                      layout=layout, need_dx=n[0], need_dparams=n[1] or n[2], need_dchan_bias=n[3])
+        need = dict(chan_bias=chan_bias, need_dx=n[0], need_dparams=n[1] or n[2], need_dchan_bias=n[3])
+        if layout == _GN_TOK2TOK:
+            dx, dw, db, dcb = hip_ops.group_norm_tok2tok_backward(dy.contiguous(), x, stats, num_groups, weight, bias, silu, frames=T, **need)
+        else:
+            dx, dw, db, dcb = hip_ops.group_norm_backward(dy.contiguous(), x, stats, T, num_groups, weight, bias, silu, layout=layout, **need)
         return (dx, dw.to(weight.dtype) if n[1] else None, db.to(bias.dtype) if n[2] else None,
                 dcb.to(chan_bias.dtype).reshape(chan_bias.shape) if n[3] else None, None, None, None, None, None)
 
 
 def _gn_hip_autograd(x, T, num_groups, weight, bias, chan_bias, layout):
-    """Under autograd: does this norm run _GroupNormFn? (switch on, kernels compute the shape, and it pays)"""
-    if not (x.is_cuda and GROUPNORM_BACKWARD and x.dim() >= 2 and x.numel() > 0):
+    """Under autograd: does this norm run _GroupNormFn? (switch on, kernels compute the shape, and it pays; the token-major family also
+    wants a contiguous tensor 16-byte aligned — one that is not contiguous is copied by the Function, and the copy is aligned)"""
+    tok = layout == _GN_TOK2TOK
+    switch = GROUPNORM_TOK2TOK_BACKWARD if tok else GROUPNORM_BACKWARD
+    if not (x.is_cuda and switch and (x.dim() == 3 if tok else x.dim() >= 2) and x.numel() > 0):
         return False
     from . import hip_ops
-    N, C = x.shape[0], x.shape[1]
+    N, C = x.shape[0], x.shape[2 if tok else 1]
     S = x.numel() // (N * C)
     if chan_bias is not None and tuple(chan_bias.shape) != (N, C):
         return False
+    if tok:
+        if T < 1 or (x.is_contiguous() and x.data_ptr() % 16 != 0):
+            return False
+        return (hip_ops.group_norm_tok2tok_backward_supported(N, C, S, num_groups, T, x.dtype)
+                and group_norm_tok2tok_backward_pays(N, C, S, T, x.dtype))
     return (hip_ops.group_norm_backward_supported(N, C, S, num_groups, T, x.dtype, layout)
             and group_norm_backward_pays(N, C, S, T, x.dtype, layout))
 
@@ -201,46 +218,10 @@ def group_norm_tok2tok_backward_pays(N, C, S, frames, dtype):
     return line is not None and N * C * S >= line
 
 
-class _GroupNormTok2TokFn(torch.autograd.Function):
-    """Token-major GroupNorm(+SiLU) on the HIP kernels with a deterministic HIP backward, behind group_norm_tok2tok. Holds t, weight,
-    bias, chan_bias and the (mean, rstd) table — not y, nothing tensor-sized in fp32; nothing is cached outside ctx, so
-    torch.utils.checkpoint may re-run the forward."""
-
-    @staticmethod
-    def forward(ctx, t, weight, bias, chan_bias, num_groups, eps, silu, frames):
-        from . import hip_ops
-        tc = t if t.is_contiguous() else t.contiguous()
-        y, stats = hip_ops.group_norm_tok2tok_forward_stats(tc, num_groups, weight, bias, eps, silu, chan_bias=chan_bias, frames=frames)
-        ctx.save_for_backward(tc, weight, bias, chan_bias, stats)
-        ctx.cfg = (num_groups, bool(silu), frames)
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        from . import hip_ops
-        t, weight, bias, chan_bias, stats = ctx.saved_tensors
-        num_groups, silu, frames = ctx.cfg
-        n = ctx.needs_input_grad
-        dx, dw, db, dcb = hip_ops.group_norm_tok2tok_backward(dy.contiguous(), t, stats, num_groups, weight, bias, silu, chan_bias=chan_bias,
-                                                              frames=frames, need_dx=n[0], need_dparams=n[1] or n[2], need_dchan_bias=n[3])
-        return (dx, dw.to(weight.dtype) if n[1] else None, db.to(bias.dtype) if n[2] else None,
-                dcb.to(chan_bias.dtype).reshape(chan_bias.shape) if n[3] else None, None, None, None, None)
-
-
 def group_norm_tok2tok_hip_autograd(t, num_groups, chan_bias=None, frames=1):
-    """Under autograd: does group_norm_tok2tok run _GroupNormTok2TokFn for this tensor? (switch on, kernels compute the shape, 16-byte
+    """Under autograd: does group_norm_tok2tok run _GroupNormFn for this tensor? (switch on, kernels compute the shape, 16-byte
     aligned, and it pays) — layers asks before it keeps the ResBlock's middle token-major."""
-    if not (t.is_cuda and GROUPNORM_TOK2TOK_BACKWARD and t.dim() == 3 and t.numel() > 0 and frames >= 1):
-        return False
-    from . import hip_ops
-    N, S, C = t.shape
-    if chan_bias is not None and tuple(chan_bias.shape) != (N, C):
-        return False
-    if t.is_contiguous() and t.data_ptr() % 16 != 0:
-        return False
-    return (hip_ops.group_norm_tok2tok_backward_supported(N, C, S, num_groups, frames, t.dtype)
-            and group_norm_tok2tok_backward_pays(N, C, S, frames, t.dtype))
+    return _gn_hip_autograd(t, frames, num_groups, None, None, chan_bias, _GN_TOK2TOK)
 
 
 def group_norm_tok2tok(t, num_groups, weight, bias, eps, silu=False, chan_bias=None, frames=1, partials=None):
@@ -252,7 +233,7 @@ def group_norm_tok2tok(t, num_groups, weight, bias, eps, silu=False, chan_bias=N
         from . import hip_ops
         return hip_ops.group_norm_silu_tok2tok(t, num_groups, weight, bias, eps, silu, chan_bias=chan_bias, frames=frames, partials=partials)
     if group_norm_tok2tok_hip_autograd(t, num_groups, chan_bias, frames):
-        return _GroupNormTok2TokFn.apply(t, weight, bias, chan_bias, num_groups, eps, silu, int(frames))
+        return _GroupNormFn.apply(t, weight, bias, chan_bias, num_groups, eps, silu, int(frames), _GN_TOK2TOK)
     _fallback(t, "group_norm_tok2tok", _why(t, weight, bias, chan_bias))
     N, S, C = t.shape
     if t.dtype == torch.float64:

@@ -1,4 +1,4 @@
-"""GPU parity of the token-major GroupNorm(+SiLU) under autograd: ops.group_norm_tok2tok through ops._GroupNormTok2TokFn
+"""GPU parity of the token-major GroupNorm(+SiLU) under autograd: ops.group_norm_tok2tok through ops._GroupNormFn
 (csrc/groupnorm_tokens.hip's forward with the statistics kept, csrc/groupnorm_bwd.hip's gn_bwd_tok_reduce_kernel / gn_bwd_tok_apply_kernel)
 and the ResBlock middle that stays token-major behind layers.RESBLOCK_CONV_BWD.
 

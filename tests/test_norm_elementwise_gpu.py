@@ -206,6 +206,41 @@ def test_group_norm_silu_tok2tok(ops, C, frames, with_cb, tag):
 
 
 @pytest.mark.parametrize("tag", TAGS)
+def test_forward_with_statistics_is_the_inference_forward(ops, tag):
+    """One C entry per family serves inference (stats NULL) and autograd (stats kept): y of *_forward_stats is torch.equal — no tolerance —
+    to y of the matching inference wrapper on the scalar two-launch, vector, resident, multi-chunk and cluster forms, the stack3 and
+    token-major outputs, and the token-major family at frames 1 and 2; the (mean, rstd) table has the same bits on a second call."""
+    dtype = H.DTYPES[tag]
+    for N, C, sp, G, T in H.GN_PLANES + [H.MULTI_CHUNK, H.CLUSTER]:
+        c = H.gn_case(tag, N, C, H.spatial_size(sp), G, T, True, True)
+        x, w, b, cb = dev(c.x, dtype).reshape(N, C, *sp), par(c.w), par(c.b), par(c.cb)
+        for layout in (ops.GN_PLANES,) if T == 1 else (ops.GN_PLANES, ops.GN_STACK3):
+            if T == 1:
+                y = ops.group_norm_silu(x, G, w, b, c.eps, True, chan_bias=cb)
+            else:
+                y = ops.group_norm_silu_frames(x, T, G, w, b, c.eps, True, chan_bias=cb, stack3=layout == ops.GN_STACK3)
+            ys, stats = twice(lambda: ops.group_norm_forward_stats(x, T, G, w, b, c.eps, True, chan_bias=cb, layout=layout))
+            assert stats.shape == (N // T * G, 2) and stats.dtype == torch.float32
+            assert torch.equal(ys, y), ("group_norm_forward_stats", (N, C) + tuple(sp), T, layout, tag)
+    torch.cuda.synchronize()                                                         # the cluster shape came last
+    assert ops.groupnorm_cluster_timeouts() == 0
+    assert all(int(buf.view(torch.int32).abs().sum()) == 0 for buf in ops._gn_sync.values())
+    for N, C, sp in TOKENS_SHAPES:
+        c = H.gn_case(tag, N, C, H.spatial_size(sp), 32, 1, True, True, 0)
+        x, w, b, cb = dev(c.x, dtype).reshape(N, C, *sp), par(c.w), par(c.b), par(c.cb)
+        y = ops.group_norm_silu_tokens(x, 32, w, b, c.eps, True, chan_bias=cb)
+        ys, stats = twice(lambda: ops.group_norm_forward_stats(x, 1, 32, w, b, c.eps, True, chan_bias=cb, layout=ops.GN_TOKENS))
+        assert stats.shape == (N * 32, 2) and torch.equal(ys, y), ("group_norm_forward_stats, token-major output", (N, C) + tuple(sp), tag)
+    for C, frames in ((64, 1), (64, 2), (96, 1), (96, 2), (320, 1), (320, 2)):
+        N, S = 2 * frames, tok_block_rows(ops, C, dtype) + 37
+        c = H.gn_case(tag, N, C, S, 32, frames, True, True)
+        t, w, b, cb = dev(c.x.transpose(1, 2).contiguous(), dtype), par(c.w), par(c.b), par(c.cb)
+        y = ops.group_norm_silu_tok2tok(t, 32, w, b, c.eps, True, chan_bias=cb, frames=frames)
+        ys, stats = twice(lambda: ops.group_norm_tok2tok_forward_stats(t, 32, w, b, c.eps, True, chan_bias=cb, frames=frames))
+        assert stats.shape == (N // frames * 32, 2) and torch.equal(ys, y), ("group_norm_tok2tok_forward_stats", (N, S, C), frames, tag)
+
+
+@pytest.mark.parametrize("tag", TAGS)
 @pytest.mark.parametrize("D", [8, 64])
 @pytest.mark.parametrize("frames", [1, 3])
 @pytest.mark.parametrize("C", [64, 96, 320])

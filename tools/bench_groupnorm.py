@@ -32,7 +32,7 @@ for shp in shapes:
     print(f"{str(shp):22s} {ms * 1e3:8.1f} us  {gb / ms * 1e3:7.0f} GB/s algorithmic ({gb / ms * 1e3 / 8000:.3f} of 8 TB/s)  rel err {err:.2e}", flush=True)
 
 # token-major forms used inside the ResBlocks when their convolutions run channels-last (planes -> tokens, tokens -> tokens)
-print("planes -> tokens (mvi_groupnorm_silu_tokens) | tokens -> tokens (mvi_groupnorm_silu_tok2tok), fused bias + SiLU")
+print("planes -> tokens (mvi_groupnorm_forward, token-major output) | tokens -> tokens (mvi_groupnorm_tok2tok_forward), fused bias + SiLU")
 for shp in [(28, 320, 72, 128), (28, 640, 72, 128), (28, 640, 36, 64), (28, 1280, 18, 32), (28, 1280, 9, 16)]:
     if only and shp != only:
         continue

@@ -1,7 +1,7 @@
 """Forward + backward time of the ResBlock's middle norm — GroupNorm + SiLU with the embedding bias, token-major input [N, H W, C] from
 one convolution and token-major output for the next — under autograd at the ResBlock shapes of the training latent (64 x 48, 32 groups;
 N = 14 and 28), bf16 and f16, random data, on three routes:
-  (a) hip     ops.group_norm_tok2tok on ops._GroupNormTok2TokFn (csrc/groupnorm_tokens.hip forward with the statistics kept +
+  (a) hip     ops.group_norm_tok2tok on ops._GroupNormFn (csrc/groupnorm_tokens.hip forward with the statistics kept +
               csrc/groupnorm_bwd.hip gn_bwd_tok_*)
   (b) torch   the same call with ops.GROUPNORM_TOK2TOK_BACKWARD off: the PyTorch fallback, this op's behaviour before the HIP backward
   (c) planes  the ResBlock middle before it: a transposing copy to planes + ops.group_norm_tokens on its HIP backward
