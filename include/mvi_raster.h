@@ -265,7 +265,13 @@ typedef struct mvi_raster_views {
                                    * pair i is tile_ids_sorted[i] << 32 | bits(depths[point_list[i]]). No kernel reads it and
                                    * the forward does not write it (grids up to 256 x 256 tiles): the array is valid after
                                    * mvi_raster_materialize_tile_ids, which derives it from `ranges` */
-    const uint32_t* point_list;   /* [D] Gaussian index per sorted pair */
+    const uint32_t* point_list;   /* [D] Gaussian index per sorted pair. Lists expanded on demand (mvi_raster_list_expansion(1),
+                                   * binning version 2): after the forward, only the positions the render kernel staged are
+                                   * written — of every tile t the whole rounds of 256 from ranges[t][0] on that it composited
+                                   * (the last one cut at ranges[t][1]), which cover [ranges[t][0], ranges[t][0] + largest
+                                   * n_contrib of the tile), all that any kernel reads afterwards; the rest is scratch memory.
+                                   * The whole array is valid after mvi_raster_materialize_point_list. Under mode 0, binning
+                                   * version 1 and grids above 256 x 256 tiles the forward writes all of it. */
     const uint32_t* ranges;       /* [tiles,2] */
     const float* final_T;         /* [H,W] */
     const uint32_t* n_contrib;    /* [H,W] */
@@ -279,6 +285,8 @@ typedef struct mvi_raster_views {
     const uint32_t* tile_class_queue; /* [8,16,(tiles + 7) / 8 + 1] the tile indices of each (band, class) in the order the
                                    * forward's blocks finished; entries behind tile_class_count[band][class] are unwritten.
                                    * Read by the render backward under mvi_raster_backward_order(1) */
+    const uint8_t* front;         /* [P] deferred SH colours: 1 = the Gaussian was named by a leading entry of a sampled tile's list
+                                   * and its colour evaluated ahead of the render kernel; zeroed by every forward_geom */
 } mvi_raster_views;
 int mvi_raster_get_views(int32_t P, int64_t num_rendered, int32_t image_width, int32_t image_height,
                          const void* geom, const void* binning, const void* image,
@@ -297,6 +305,19 @@ int mvi_raster_materialize_geom_views(const mvi_raster_settings* s, int32_t P, c
  * so it may run before or after the backward. A no-op when num_rendered is 0. */
 int mvi_raster_materialize_tile_ids(int32_t P, int64_t num_rendered, int32_t image_width, int32_t image_height,
                                     void* binning, const void* image, void* stream);
+
+/* Fills point_list of a finished forward (same P, num_rendered, size and scratch buffers) in full: the pass-2 scatter of binning
+ * version 2 over the column segments, the chunk table (geom scratch) and the row tables (binning scratch) the forward left. No
+ * call between a forward and the next mvi_raster_forward_geom on the geom scratch writes those regions, so nothing has to be
+ * recomputed, and the call may be repeated: it writes the same bits every time, into the positions a forward under
+ * mvi_raster_list_expansion(1) stored the values that forward stored, and the tile ranges again. After a forward that wrote
+ * the whole list itself it rewrites it (version 2) or does nothing (version 1). Enqueued on `stream`; may run before or after
+ * the backward. A no-op when num_rendered is 0. Precondition: mvi_raster_binning_version is what it was when the forward ran
+ * (as for the backward and mvi_raster_get_views: the scratch layout and which tables exist follow from it, and the call reads
+ * the current selection, not a record of the forward's). After a change it would do nothing on a partial list or scatter over
+ * tables the forward never wrote. */
+int mvi_raster_materialize_point_list(int32_t P, int64_t num_rendered, int32_t image_width, int32_t image_height,
+                                      const void* geom, void* binning, void* image, void* stream);
 
 /* Stage timing (measurement aid for bench.py): while enabled, every kernel stage the library
  * enqueues is bracketed by hipEvents on the caller's stream. mvi_raster_timing_read waits for the
@@ -332,6 +353,16 @@ int mvi_raster_forward_group(int group);
  * last 64 scratches by address and size); any other state runs in the plain order. Pass 0 or 1 to select, -1 to query;
  * returns the previous selection, or MVI_EINVAL (nothing changed) for any other value. Not thread-safe. */
 int mvi_raster_backward_order(int order);
+/* Tile lists under binning version 2. 1 = expanded on demand: pass 2 stops behind its row scan (whose last block writes the
+ * tile ranges), and the render kernel finds the entries of a round by walking the column segments of its tile column that
+ * cover its tile row, as far as it composites; it stores the Gaussians of the rounds it staged to their places in point_list
+ * (see mvi_raster_views.point_list). A tile's pixels saturate after a fifth of its list on a dense scene: the other four fifths
+ * are never written. 0 = the pass-2 scatter writes every list in full (MVI_RASTER_LAZY_LISTS=0 | 1 selects at start-up).
+ * Images, ranges, n_contrib, num_rendered and the numbering of list positions are identical bit for bit; gradients differ as
+ * they do from run to run (order of float atomics). Binning version 1 and grids above 256 x 256 tiles always write the lists
+ * in full. Pass 0 or 1 to select, -1 to query; returns the previous selection, or MVI_EINVAL (nothing changed) for any other
+ * value. Read by mvi_raster_forward_render*; not thread-safe. */
+int mvi_raster_list_expansion(int mode);
 /* Evaluates every colour still pending after a deferred forward (no-op after an eager one), so that mvi_raster_views.rgbd /
  * clamped are complete: for the parity tests and for callers that inspect colours of Gaussians that were never composited.
  * Needs the means3D / shs arrays of the forward still valid. */

@@ -34,7 +34,8 @@ class RasterViews(C.Structure):
         "tile_ids_sorted", "point_list", "ranges", "final_T", "n_contrib")] + [("tile_id_bytes", C.c_int32),
                                                                                    ("grad_support", C.c_void_p),
                                                                                    ("tile_class_count", C.c_void_p),
-                                                                                   ("tile_class_queue", C.c_void_p)]
+                                                                                   ("tile_class_queue", C.c_void_p),
+                                                                                   ("front", C.c_void_p)]
 
 
 class AdamGroup(C.Structure):
@@ -137,6 +138,8 @@ def lib():
     L.mvi_raster_materialize_geom_views.argtypes = [C.POINTER(RasterSettings), i32] + [vp] * 7
     L.mvi_raster_materialize_tile_ids.restype = C.c_int
     L.mvi_raster_materialize_tile_ids.argtypes = [i32, i64, i32, i32, vp, vp, vp]
+    L.mvi_raster_materialize_point_list.restype = C.c_int
+    L.mvi_raster_materialize_point_list.argtypes = [i32, i64, i32, i32, vp, vp, vp, vp]
     L.mvi_raster_timing_enable.restype = C.c_int
     L.mvi_raster_timing_enable.argtypes = [C.c_int]
     L.mvi_raster_timing_enable_stages.restype = C.c_int
@@ -155,6 +158,8 @@ def lib():
     L.mvi_raster_forward_group.argtypes = [C.c_int]
     L.mvi_raster_backward_order.restype = C.c_int
     L.mvi_raster_backward_order.argtypes = [C.c_int]
+    L.mvi_raster_list_expansion.restype = C.c_int
+    L.mvi_raster_list_expansion.argtypes = [C.c_int]
     L.mvi_raster_resolve_colors.restype = C.c_int
     L.mvi_raster_resolve_colors.argtypes = [C.POINTER(RasterSettings), i32, vp, sz, vp]
     L.mvi_raster_dev_stamps.restype = C.c_int

@@ -144,6 +144,10 @@ int mvi_raster_backward_order(int order) {
     const int old = mvi::set_backward_order(order);
     return old < 0 ? fail(MVI_EINVAL, "backward order: 1 (heaviest first), 0 (plain band order) or -1 (query)%s") : old;
 }
+int mvi_raster_list_expansion(int mode) {
+    const int old = mvi::set_list_expansion(mode);
+    return old < 0 ? fail(MVI_EINVAL, "list expansion: 1 (on demand), 0 (pass 2 writes every list) or -1 (query)%s") : old;
+}
 int mvi_raster_color_mode(int deferred) {
     const int old = g_defer_colors;
     if (deferred == 0 || deferred == 1) g_defer_colors = deferred;
@@ -642,6 +646,7 @@ int mvi_raster_get_views(int32_t P, int64_t D, int32_t W, int32_t H, const void*
         out->conic_opacity = reinterpret_cast<const float*>(g.conic_opacity); out->rgbd = reinterpret_cast<const float*>(g.rgbd);
         out->tiles_touched = g.tiles_touched; out->clamped = g.clamped;
         out->grad_support = g.touched;
+        out->front = g.front;
     }
     if (binning) {
         mvi::BinningView b = mvi::carve_binning(const_cast<void*>(binning), D, W, H);
@@ -669,6 +674,22 @@ int mvi_raster_materialize_geom_views(const mvi_raster_settings* s, int32_t P, c
     mvi::GeomView g = mvi::carve_geom(geom, P);
     if (mvi::launch_materialize_geom_views(f, means3D, scales, rotations, cov3D_precomp, radii, g, (hipStream_t)stream))
         return hip_fail("materialize_geom_views", hipGetLastError());
+    return MVI_OK;
+}
+
+int mvi_raster_materialize_point_list(int32_t P, int64_t D, int32_t W, int32_t H, const void* geom, void* binning, void* image,
+                                      void* stream) {
+    if (P < 0 || D < 0 || W < 0 || H < 0) return fail(MVI_EINVAL, "negative size in materialize_point_list%s");
+    if (D > 0xFFFFFFFFll) return fail(MVI_EINVAL, "num_rendered out of range%s: %lld", "", D);
+    if (P == 0 || D == 0 || W == 0 || H == 0) return MVI_OK;
+    if (!geom || !binning || !image) return fail(MVI_EINVAL, "NULL scratch in materialize_point_list%s");
+    mvi::BinningView b = mvi::carve_binning(binning, D, W, H);
+    if (!b.v2) return MVI_OK;                            // version 1 (and grids version 2 does not take) always write the list
+    const int gx = (W + mvi::kTile - 1) / mvi::kTile, gy = (H + mvi::kTile - 1) / mvi::kTile;
+    mvi::GeomView g = mvi::carve_geom(const_cast<void*>(geom), P);
+    mvi::ImageView im = mvi::carve_image(image, W, H);
+    if (mvi::launch_binning2_scatter(gx, gy, g, b, im, recall_segments(geom, P), D, (hipStream_t)stream))
+        return hip_fail("materialize_point_list", hipGetLastError());
     return MVI_OK;
 }
 

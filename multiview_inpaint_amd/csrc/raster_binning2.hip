@@ -37,6 +37,25 @@ int set_binning_version(int v) {
     return old;
 }
 
+// Tile lists of version 2 (mvi_raster_list_expansion): 1 = pass 2 stops behind its row scan, whose last block writes the tile
+// ranges; render_forward expands a tile's list from the column segments as far as it composites and stores that prefix
+// (raster_render.hip, LAZY). 0 = expand_scatter_kernel<2> writes every list in full. MVI_RASTER_LAZY_LISTS=0 | 1 selects at
+// start-up. launch_binning2_scatter writes the full list of a finished forward for whoever wants to read all of it.
+// 1 is the default: on the bench view the step went from 0.8137 - 0.8186 to 0.7933 - 0.7976 ms and render_forward + mark_front +
+// pass 2 from 289.6 - 293.7 to 269.3 - 271.8 us under the kernel trace, every repetition below every one of the parent's
+// (profiles/lazy_lists_ab.txt).
+constexpr int kListExpansionDefault = 1;
+static int g_list_expansion = [] { const char* e = getenv("MVI_RASTER_LAZY_LISTS");
+                                   return e && (e[0] == '0' || e[0] == '1') && e[1] == 0 ? e[0] - '0' : kListExpansionDefault; }();
+int set_list_expansion(int mode) {
+    const int old = g_list_expansion;
+    if (mode == -1) return old;
+    if (mode != 0 && mode != 1) return MVI_EINVAL;
+    g_list_expansion = mode;
+    return old;
+}
+bool lazy_lists(const Frame& f, int64_t D) { return f.bin_v2 && g_list_expansion == 1 && D > 0 && f.P > 0 && f.W > 0 && f.H > 0; }
+
 // exclusive scan over the values of the first 256 threads of a block (the others pass 0); every thread must call it
 __device__ __forceinline__ uint32_t block_excl_scan256(uint32_t v, int tid, uint32_t* s_w4, uint32_t* total) {
     const int lane = tid & 63, wave = tid >> 6;
@@ -431,10 +450,12 @@ __global__ __launch_bounds__(kExThreads) void row_count_kernel(int gx, int gy, c
 __global__ __launch_bounds__(1024) void row_scan_kernel(int gx, const uint32_t* __restrict__ chunk_first,
                                                         uint32_t* __restrict__ row_table, int stride,
                                                         uint32_t* __restrict__ row_tot, uint32_t* __restrict__ col_rel,
-                                                        uint32_t* __restrict__ class_count) {
+                                                        uint32_t* __restrict__ class_count, uint32_t* __restrict__ arrivals,
+                                                        uint32_t* __restrict__ ranges) {
     __shared__ uint32_t s_first[257];
     __shared__ uint32_t s_wave[16];
     __shared__ uint32_t s_carry;
+    __shared__ uint32_t s_last, s_w4[4], s_row0[256];
     const int tid = threadIdx.x;
     // the render kernel's tile class counts (raster_common.h, ImageView) start every forward at zero: this kernel runs in
     // front of it whenever there are pairs, so no launch is spent on 512 bytes
@@ -446,8 +467,47 @@ __global__ __launch_bounds__(1024) void row_scan_kernel(int gx, const uint32_t* 
     // the offsets just written by this block are read back by it, behind the barrier (which drains the stores)
     __syncthreads();
     uint32_t* cr = col_rel + (size_t)blockIdx.x * (gx + 1);
-    if (tid < gx) cr[tid] = __hip_atomic_load(row + s_first[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // L2, not L1
-    if (tid == 0) { cr[gx] = total; row_tot[blockIdx.x] = total; }
+    if (!ranges) {
+        if (tid < gx) cr[tid] = __hip_atomic_load(row + s_first[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // L2, not L1
+        if (tid == 0) { cr[gx] = total; row_tot[blockIdx.x] = total; }
+        return;
+    }
+    // Lists expanded on demand: no scatter follows that could write the tile ranges, so the block that arrives last writes
+    // them (the pattern of columns_scan_kernel: agent-scope stores, drained before the arrival; the counter is the one that
+    // kernel left at zero, and the last block leaves it at zero again). Tile (row y, column x) starts at the pairs of the rows
+    // above + col_rel[y][x] and holds col_rel[y][x + 1] - col_rel[y][x] pairs: what the first chunk of column x wrote from
+    // the same numbers; an empty tile gets (0, 0). No block waits for another.
+    if (tid < gx) {
+        const uint32_t v = __hip_atomic_load(row + s_first[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(cr + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (tid == 0) {
+        __hip_atomic_store(cr + gx, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(row_tot + blockIdx.x, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                           // every thread's stores have left ...
+    __syncthreads();                                                           // ... before the block's arrival
+    if (tid == 0) {
+        const uint32_t prev = __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = prev == (uint32_t)gridDim.x - 1u;
+        if (s_last) __hip_atomic_store(arrivals, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!s_last) return;
+    const int gy = (int)gridDim.x;                                             // <= 256 tile rows
+    const uint32_t rt = tid < gy ? __hip_atomic_load(row_tot + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+    const uint32_t r_ex = block_excl_scan256(rt, tid, s_w4, nullptr);
+    if (tid < 256) s_row0[tid] = r_ex;
+    __syncthreads();
+    uint2* rg = reinterpret_cast<uint2*>(ranges);
+    for (int i = tid; i < gy * gx; i += 1024) {
+        const int y = i / gx, x = i - y * gx;
+        const uint32_t* c = col_rel + (size_t)y * (gx + 1) + x;
+        const uint32_t a = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t n = __hip_atomic_load(c + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - a;
+        const uint32_t start = s_row0[y] + a;
+        rg[i] = n ? make_uint2(start, start + n) : make_uint2(0u, 0u);
+    }
 }
 
 // =================================================================================================== expanding partition
@@ -714,6 +774,12 @@ int launch_binning2_level1(const Frame& f, GeomView g, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
 }
 
+// chunks of pass 2: at most segments / kEx2Chunk + gx; the table (stride b.nsort) was sized for segments <= D
+static int pass2_chunks(int gx, const BinningView& b, int64_t segments, int64_t D) {
+    if (segments > 0 && segments <= D) return (int)min((int64_t)b.nsort, segments / kEx2Chunk + gx + 1);
+    return b.nsort;
+}
+
 // pass 1, pass 2 (count, scan, scatter + tile ranges). Result: b.vals[1] = point list. The tile id of each pair, b.keys[1], is
 // NOT written: the ranges come out of the row scan and no kernel reads the ids (2 bytes per pair, a third of pass 2's traffic);
 // launch_tile_ids_from_ranges (raster_binning.hip) derives them from the ranges for whoever asks (the parity tests).
@@ -732,27 +798,38 @@ int launch_binning2(const Frame& f, GeomView g, BinningView b, ImageView im, int
             hipLaunchKernelGGL((expand_scatter_kernel<1, 256, kExItems, 64 * 256>), dim3(g.nblk1), dim3(kExThreads), 0, st, a1);
         else hipLaunchKernelGGL((expand_scatter_kernel<1, 128, kExItems, 64 * 128>), dim3(g.nblk1), dim3(kExThreads), 0, st, a1);
     }
-    // chunks: at most segments / kEx2Chunk + gx; the table (stride b.nsort) was sized for segments <= D
-    int nchunk = b.nsort;
-    if (segments > 0 && segments <= D) nchunk = (int)min((int64_t)b.nsort, segments / kEx2Chunk + f.gx + 1);
+    const int nchunk = pass2_chunks(f.gx, b, segments, D);
+    const bool lazy = lazy_lists(f, D);
+    StageTimer tm(kStSort, st);
+    hipLaunchKernelGGL(row_count_kernel, dim3(nchunk), dim3(kExThreads), 0, st, f.gx, f.gy, g.chunk_first, g.col_start,
+                       (const uint16_t*)b.keys[0], b.block_hist, b.nsort);
+    // lists expanded on demand: the row scan's last block writes the ranges and pass 2 ends here (render_forward, LAZY)
+    hipLaunchKernelGGL(row_scan_kernel, dim3(f.gy), dim3(1024), 0, st, f.gx, g.chunk_first, b.block_hist, b.nsort,
+                       b.digit_tot, b.col_rel, im.class_count, g.arrivals, lazy ? im.ranges : (uint32_t*)nullptr);
+    if (lazy) return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;
+    return launch_binning2_scatter(f.gx, f.gy, g, b, im, segments, D, st);
+}
+
+// The pass-2 scatter over the segments (b.keys[0], b.vals[0]), the chunk table (g.chunk_first, g.col_start) and the row tables
+// (b.block_hist, b.digit_tot, b.col_rel) of this forward: the sorted point list, whole, and every tile range. Nothing between
+// a forward and the next forward_geom on the scratch writes any of these regions (the backward, the splat and the lift only
+// read the list and the ranges), so it may run again at any later time and writes the same bits: into the places of a
+// prefix that a LAZY render_forward stored, the values that kernel stored.
+int launch_binning2_scatter(int gx, int gy, GeomView g, BinningView b, ImageView im, int64_t segments, int64_t D, hipStream_t st) {
+    const int nchunk = pass2_chunks(gx, b, segments, D);
     ExpandArgs a2{};
-    a2.nbins = f.gy; a2.gx = f.gx;
+    a2.nbins = gy; a2.gx = gx;
     a2.chunk_first = g.chunk_first; a2.col_start = g.col_start;
     a2.seg_idx_in = b.vals[0]; a2.seg_yh_in = (const uint16_t*)b.keys[0];
     a2.col_rel = b.col_rel; a2.ranges = im.ranges;
     a2.table = b.block_hist; a2.tot = b.digit_tot; a2.stride = b.nsort;
     a2.out_idx = b.vals[1];
     a2.stamps = g_dev_stamps[1];
-    StageTimer tm(kStSort, st);
-    hipLaunchKernelGGL(row_count_kernel, dim3(nchunk), dim3(kExThreads), 0, st, f.gx, f.gy, g.chunk_first, g.col_start,
-                       (const uint16_t*)b.keys[0], b.block_hist, b.nsort);
-    hipLaunchKernelGGL(row_scan_kernel, dim3(f.gy), dim3(1024), 0, st, f.gx, g.chunk_first, b.block_hist, b.nsort,
-                       b.digit_tot, b.col_rel, im.class_count);
     // bins = tile rows: up to 80 rows the small instantiation (~50 KB of LDS, three blocks per CU instead of two)
-    if (f.gy <= kEx2SmallNB)
+    if (gy <= kEx2SmallNB)
         hipLaunchKernelGGL((expand_scatter_kernel<2, kEx2SmallNB, kEx2Items, kEx2SmallCap>), dim3(nchunk), dim3(kExThreads), 0,
                            st, a2);
-    else if (f.gy <= 128)
+    else if (gy <= 128)
         hipLaunchKernelGGL((expand_scatter_kernel<2, 128, kEx2Items, 64 * 128>), dim3(nchunk), dim3(kExThreads), 0, st, a2);
     else hipLaunchKernelGGL((expand_scatter_kernel<2, 256, kEx2Items, 64 * 256>), dim3(nchunk), dim3(kExThreads), 0, st, a2);
     return hipGetLastError() == hipSuccess ? 0 : MVI_EHIP;

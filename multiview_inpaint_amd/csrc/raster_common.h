@@ -69,7 +69,9 @@ void set_dev_stamps(int pass, void* buf);            // diagnostics: shader-cloc
 int set_binning_version(int v);                     // 1 | 2 (anything else: query only); returns the previous version
 int set_forward_group(int g);                       // render_forward's strip-walk group: a built size | 0 = default | -1 = query
 int set_backward_order(int order);                  // render_backward's tile order: 1 heaviest first | 0 plain band order | -1 = query
+int set_list_expansion(int mode);                   // tile lists: 1 expanded on demand by render_forward | 0 written by pass 2 | -1 = query
 inline bool binning_v2_ok(int gx, int gy) { return gx <= 256 && gy <= 256 && binning_v2_enabled(); }
+bool lazy_lists(const Frame& f, int64_t D);         // this forward leaves the point list to render_forward (version 2, pairs, mode 1)
 
 // Deferred SH colours. With SH input the forward preprocess does NOT evaluate SH -> RGB for every visible Gaussian (192 bytes
 // of coefficients each at degree 3, 63 % of everything that kernel reads, for colours of which ~3 % are ever composited: a
@@ -603,6 +605,8 @@ int launch_binning2_totals(GeomView g, int P, unsigned long long* totals_host_de
 int launch_binning2_level1(const Frame& f, GeomView g, hipStream_t st);
 // segments: the exact number of column segments if known (> 0), else the bound D is used to size the pass-2 grids
 int launch_binning2(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D, int64_t segments, hipStream_t st);
+// the pass-2 scatter alone, over the tables a finished version-2 forward left in its scratch: the whole point list (and the ranges again)
+int launch_binning2_scatter(int gx, int gy, GeomView g, BinningView b, ImageView im, int64_t segments, int64_t D, hipStream_t st);
 int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView im, int64_t D,
                           float* out_color, float* out_depth, hipStream_t st, float* zero_rows = nullptr,
                           float* out_expected_depth = nullptr, float* out_alpha = nullptr);   // both or neither: the aux outputs

@@ -35,14 +35,29 @@ namespace mvi {
 // AUX: the kernel also accumulates the expected depth sum z alpha T over exactly the entries it composites (one fma per entry
 // beside the colour's) and writes it and alpha = 1 - T_final; with AUX clear the two pointers are never read and the
 // instantiation is the colour-only kernel.
-template <int G, bool AUX>
+// LAZY (binning version 2 under mvi_raster_list_expansion(1)): nobody has written the tile's list. The block finds a round's
+// entries itself, by walking the segments of its tile column (lazy_list_step, raster_render_shared.h), just in time: at the
+// top of the round, behind the saturation test, so that no segment is looked at for a round that is never composited. The
+// thread that stages an entry takes the Gaussian from the segment and stores it to point_list[r0 + position] (coalesced):
+// the prefix of the list that this kernel consumed — all that the backward, the aux backward, the splat and the lift replay —
+// lies where pass 2 would have put it, with the same values. What the eager kernel gathers one round ahead is gathered here
+// at the top of its own round: the other five blocks of the CU cover the wait, and eleven registers are free while a round
+// is composited. With LAZY clear the instantiation is the eager kernel.
+struct LazyLists {
+    const uint16_t* seg_yh;             // pass 1: first row | rows - 1 << 8 of every column segment
+    const uint32_t* seg_idx;            // pass 1: its Gaussian
+    const uint32_t* col_start;          // [gx + 1] first segment of every tile column
+};
+template <int G, bool AUX, bool LAZY>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G == 1 ? 1 : 6, G == 1 ? 8 : 6))) void render_forward_kernel(
-    Frame f, const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ point_list,
+    Frame f, const uint32_t* __restrict__ ranges, uint32_t* __restrict__ point_list,
     const float2* __restrict__ xy, float4* rgbd, const float4* __restrict__ conic_opacity,
     float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color,
     float* __restrict__ out_depth, ZeroRegions zero, const ColorSource* __restrict__ color_src, uint8_t* clamped,
-    float* __restrict__ out_expected_depth, float* __restrict__ out_alpha, uint32_t* __restrict__ class_count) {
+    float* __restrict__ out_expected_depth, float* __restrict__ out_alpha, uint32_t* __restrict__ class_count, LazyLists lz) {
     __shared__ uint32_t s_wmax[4];
+    __shared__ uint32_t s_q[LAZY ? kBlock : 1];                // segments of the round's entries, by position in the round
+    __shared__ uint32_t s_tot[LAZY ? 2 : 1][kLazySubs * 4];
     __shared__ float2 s_xy[kBlock];
     __shared__ float s_t2[kBlock];
     __shared__ float4 s_co[kBlock];
@@ -80,23 +95,49 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G == 1 ?
     float2 n_xy = make_float2(0.f, 0.f);
     float4 n_co = make_float4(0.f, 0.f, 0.f, 0.f), n_cd = n_co;
     uint32_t n_id = 0;
+    // LAZY: the walk of the tile column (block-uniform)
+    [[maybe_unused]] uint32_t c0 = 0, c1 = 0, cur = 0, have = 0;
+    if constexpr (LAZY)
+        if (rounds > 0) { c0 = lz.col_start[tile_x]; c1 = lz.col_start[tile_x + 1]; cur = c0 & ~1u; }
     auto fetch = [&](int r) {
-        const uint32_t q = r0 + (uint32_t)(r * kBlock + tid);
-        if (q < r1) {
-            n_id = point_list[q];
-            n_xy = xy[n_id]; n_co = conic_opacity[n_id]; n_cd = rgbd[n_id];
+        if constexpr (LAZY) {
+            const uint32_t lo = (uint32_t)(r * kBlock), hi = min(lo + (uint32_t)kBlock, r1 - r0);
+            uint32_t reached = have;
+            int par = 0;
+            while (cur < c1) {
+                reached = lazy_list_step(lz.seg_yh, c0, c1, (uint32_t)tile_y, cur, have, lo, hi, s_tot, par, tid,
+                                         [&](uint32_t pos, uint32_t seg) { s_q[pos - lo] = seg; });
+                if (reached >= hi) break;
+            }
+            __syncthreads();
+            // the ranges hold the column's count for this row, so the round is complete; a state that says otherwise stages
+            // opacity 0 (never kept) for what is missing and reads nothing
+            const uint32_t avail = reached > lo ? min(reached, hi) - lo : 0u;
+            n_co = make_float4(0.f, 0.f, 0.f, 0.f);
+            if ((uint32_t)tid < avail) {
+                n_id = lz.seg_idx[s_q[tid]];
+                point_list[r0 + lo + (uint32_t)tid] = n_id;
+                n_xy = xy[n_id]; n_co = conic_opacity[n_id]; n_cd = rgbd[n_id];
+            }
+        } else {
+            const uint32_t q = r0 + (uint32_t)(r * kBlock + tid);
+            if (q < r1) {
+                n_id = point_list[q];
+                n_xy = xy[n_id]; n_co = conic_opacity[n_id]; n_cd = rgbd[n_id];
+            }
         }
     };
-    if (rounds > 0) fetch(0);
+    if (!LAZY && rounds > 0) fetch(0);
     for (int r = 0; r < rounds; ++r, todo -= kBlock) {
         if (__syncthreads_count(T <= 0.0f) == kBlock) break;
+        if constexpr (LAZY) fetch(r);
         if (cs.deferred && tid < todo && color_pending(n_cd)) n_cd = resolve_color_small(cs, f.campos, n_id, n_cd.w, rgbd, clamped);
         s_xy[tid] = n_xy;
         s_co[tid] = n_co;
         s_t2[tid] = active_t2(n_co);
         s_cd[tid] = n_cd;
         __syncthreads();
-        if (r + 1 < rounds) fetch(r + 1);
+        if (!LAZY && r + 1 < rounds) fetch(r + 1);
         const int n = todo < kBlock ? todo : kBlock;
         for (int c = 0; c < n; c += 64) {
             if (ballot64(T > 0.0f) == 0ull) break;
@@ -245,6 +286,34 @@ __global__ __launch_bounds__(kBlock) void mark_front_kernel(int tiles, const uin
         for (uint32_t e = tid; e < n; e += kBlock) front[point_list[r0 + e]] = 1;
     }
 }
+// The same marks with no list to read (lists expanded on demand): the leading entries of a sampled tile are the first
+// min(n_front, length) segments of its column that cover its row, found by the walk the render kernel uses. Nothing is stored
+// but the marks.
+__global__ __launch_bounds__(kBlock) void mark_front_lazy_kernel(int tiles, const uint32_t* __restrict__ ranges, LazyLists lz,
+                                                                 uint8_t* __restrict__ front, int n_front,
+                                                                 const ColorSource* __restrict__ color_src, int gx, int every) {
+    if (!color_src->deferred) return;
+    __shared__ uint32_t s_tot[2][kLazySubs * 4];
+    const int tid = threadIdx.x;
+    const int sx = (gx + every - 1) / every;
+    int par = 0;                                         // carried from tile to tile: see lazy_list_step
+    for (int t = 0; t < kFrontTiles; ++t) {
+        const int j = blockIdx.x * kFrontTiles + t;
+        const int tile = every == 1 ? j : (j / sx) * every * gx + (j % sx) * every;
+        if (tile >= tiles) break;
+        const uint32_t r0 = ranges[2 * tile], r1 = ranges[2 * tile + 1];
+        const uint32_t n = min(r1 - r0, (uint32_t)n_front);
+        if (n == 0) continue;                            // block-uniform; an empty column is never walked
+        const int tile_y = tile / gx, tile_x = tile - tile_y * gx;
+        const uint32_t c0 = lz.col_start[tile_x], c1 = lz.col_start[tile_x + 1];
+        uint32_t cur = c0 & ~1u, have = 0;
+        while (cur < c1) {
+            const uint32_t reached = lazy_list_step(lz.seg_yh, c0, c1, (uint32_t)tile_y, cur, have, 0u, n, s_tot, par, tid,
+                                                    [&](uint32_t, uint32_t seg) { front[lz.seg_idx[seg]] = 1; });
+            if (reached >= n) break;
+        }
+    }
+}
 constexpr int kMarkedPer = 4;                            // flags per thread: one 4-byte load
 __global__ __launch_bounds__(kBlock) void resolve_marked_kernel(Frame f, GeomView g) {
     const ColorSource cs = *g.color_src;
@@ -337,8 +406,12 @@ int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView i
                                                                   // (inside the scratch segment's 256-byte padding)
     }
     if (f.W <= 0 || f.H <= 0) return launch_zero_regions(z, st);
-    const uint32_t* plist = b.vals[b.passes & 1];
+    uint32_t* plist = b.vals[b.passes & 1];
     const unsigned blocks = (unsigned)(f.gx * f.gy);
+    // lists expanded on demand: the binning of this call (launch_binning2, same test) wrote the ranges and no list
+    const bool lazy = lazy_lists(f, D);
+    LazyLists lz{};
+    if (lazy) { lz.seg_yh = (const uint16_t*)b.keys[0]; lz.seg_idx = b.vals[0]; lz.col_start = g.col_start; }
     if (f.defer_colors && D > 0) {
         // MVI_RASTER_FRONT_ENTRIES: leading entries per tile evaluated ahead of the render kernel (0: none, A/B runs)
         static const int n_front = [] { const char* e = getenv("MVI_RASTER_FRONT_ENTRIES"); const int v = e ? atoi(e) : kBlock;
@@ -346,21 +419,29 @@ int launch_render_forward(const Frame& f, GeomView g, BinningView b, ImageView i
         static const int every = [] { const char* e = getenv("MVI_RASTER_FRONT_EVERY"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : v; }();
         if (n_front > 0) {
             const unsigned sampled = (unsigned)(((f.gx + every - 1) / every) * ((f.gy + every - 1) / every));
-            hipLaunchKernelGGL(mark_front_kernel, dim3((sampled + kFrontTiles - 1) / kFrontTiles), dim3(kBlock), 0, st, (int)blocks,
-                               im.ranges, plist, g.front, n_front, g.color_src, f.gx, every);
+            if (lazy)
+                hipLaunchKernelGGL(mark_front_lazy_kernel, dim3((sampled + kFrontTiles - 1) / kFrontTiles), dim3(kBlock), 0, st,
+                                   (int)blocks, im.ranges, lz, g.front, n_front, g.color_src, f.gx, every);
+            else
+                hipLaunchKernelGGL(mark_front_kernel, dim3((sampled + kFrontTiles - 1) / kFrontTiles), dim3(kBlock), 0, st, (int)blocks,
+                                   im.ranges, plist, g.front, n_front, g.color_src, f.gx, every);
             hipLaunchKernelGGL(resolve_marked_kernel, dim3((f.P + kBlock * kMarkedPer - 1) / (kBlock * kMarkedPer)), dim3(kBlock), 0, st,
                                f, g);
         }
     }
-#define MVI_RENDER_FORWARD(G, AUX)                                                                                          \
-    hipLaunchKernelGGL((render_forward_kernel<G, AUX>), dim3(blocks), dim3(kBlock), 0, st, f, im.ranges, plist, g.xy, g.rgbd, \
-                       g.conic_opacity, im.final_T, im.n_contrib, out_color, out_depth, z, g.color_src, g.clamped,            \
-                       out_expected_depth, out_alpha, im.class_count)
-    switch (g_forward_group * 2 + (out_alpha ? 1 : 0)) {
-        case 2: MVI_RENDER_FORWARD(1, false); break;
-        case 3: MVI_RENDER_FORWARD(1, true); break;
-        case 8: MVI_RENDER_FORWARD(4, false); break;
-        case 9: MVI_RENDER_FORWARD(4, true); break;
+#define MVI_RENDER_FORWARD(G, AUX, LAZY)                                                                                          \
+    hipLaunchKernelGGL((render_forward_kernel<G, AUX, LAZY>), dim3(blocks), dim3(kBlock), 0, st, f, im.ranges, plist, g.xy, g.rgbd, \
+                       g.conic_opacity, im.final_T, im.n_contrib, out_color, out_depth, z, g.color_src, g.clamped,                  \
+                       out_expected_depth, out_alpha, im.class_count, lz)
+    switch (g_forward_group * 4 + (out_alpha ? 2 : 0) + (lazy ? 1 : 0)) {
+        case 4: MVI_RENDER_FORWARD(1, false, false); break;
+        case 5: MVI_RENDER_FORWARD(1, false, true); break;
+        case 6: MVI_RENDER_FORWARD(1, true, false); break;
+        case 7: MVI_RENDER_FORWARD(1, true, true); break;
+        case 16: MVI_RENDER_FORWARD(4, false, false); break;
+        case 17: MVI_RENDER_FORWARD(4, false, true); break;
+        case 18: MVI_RENDER_FORWARD(4, true, false); break;
+        case 19: MVI_RENDER_FORWARD(4, true, true); break;
         default: return MVI_EINVAL;                              // a kernel that is not built is an error, never another kernel
     }
 #undef MVI_RENDER_FORWARD

@@ -46,6 +46,72 @@ __device__ __forceinline__ int xcd_band_tile(int bid, int tiles) {
     return x * q + (x < r ? x : r) + i;
 }
 
+// ---- tile lists expanded on demand (binning version 2, mvi_raster_list_expansion(1)) -----------------------------------------
+// The list of tile (row, column x) is the column segments [col_start[x], col_start[x + 1]) of pass 1 that cover the row
+// (first row <= row <= first row + rows - 1), in segment order: pass 1 leaves a column's segments in depth order. A block of
+// 256 threads walks its column with a block-uniform cursor and numbers the covering segments as pass 2 would have placed them.
+// One step looks at kLazySubs sub-steps of kLazySub segments: a thread reads one aligned 4-byte word (two segments) per
+// sub-step, every index clamped to the column's last word so that the four loads travel together; what lies outside
+// [c0, c1) is dropped by the compare. Two ballots per sub-step give a thread its place among the wave's covering segments,
+// the wave totals go through LDS (one barrier per step) and every thread sums the same totals: cursor and counts stay
+// block-uniform without another exchange.
+//   cur    first segment of the first sub-step that still holds an entry nobody consumed (even; starts at c0 & ~1)
+//   have   covering segments of the column in front of `cur`
+// emit(position, segment) is called for every covering segment whose position in the tile's list lies in [lo, hi). A sub-step
+// is left behind (cur, have move past it) only when all its entries lie below `hi`; a sub-step that holds entries at or
+// beyond `hi` is looked at again by the next call, which emits them when its own [lo, hi) names them: nothing is dropped,
+// nothing emitted twice, and no queue can overflow because nothing is kept between calls but the two numbers. Returns the
+// number of covering segments in front of the step's end: below `hi` means that all sub-steps were consumed and the caller
+// goes on while cur < c1. s_tot: two buffers used in turn (`par`), so that a step's totals are not overwritten by the step
+// after the next while a late wave still reads them. Every thread of the block calls it (barrier inside); c1 > c0.
+constexpr int kLazySub = 512;
+constexpr int kLazySubs = 4;
+template <class Emit>
+__device__ __forceinline__ uint32_t lazy_list_step(const uint16_t* __restrict__ seg_yh, uint32_t c0, uint32_t c1, uint32_t row,
+                                                   uint32_t& cur, uint32_t& have, uint32_t lo, uint32_t hi,
+                                                   uint32_t (*s_tot)[kLazySubs * 4], int& par, int tid, Emit emit) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const uint32_t* yh2 = reinterpret_cast<const uint32_t*>(seg_yh);      // the array starts 256-byte aligned
+    const uint32_t dlast = (c1 - 1u) >> 1;                                // word of the column's last segment
+    uint32_t w[kLazySubs];
+#pragma unroll
+    for (int j = 0; j < kLazySubs; ++j) w[j] = yh2[min((cur >> 1) + (uint32_t)(j * (kLazySub / 2) + tid), dlast)];
+    unsigned long long m0[kLazySubs], m1[kLazySubs];
+    bool k0[kLazySubs], k1[kLazySubs];
+    uint32_t* tot = s_tot[par];
+    par ^= 1;
+#pragma unroll
+    for (int j = 0; j < kLazySubs; ++j) {
+        const uint32_t s0 = cur + (uint32_t)(j * kLazySub + 2 * tid), s1 = s0 + 1u;
+        k0[j] = s0 >= c0 && s0 < c1 && (row - (w[j] & 255u)) <= ((w[j] >> 8) & 255u);
+        k1[j] = s1 >= c0 && s1 < c1 && (row - ((w[j] >> 16) & 255u)) <= (w[j] >> 24);
+        m0[j] = ballot64(k0[j]);
+        m1[j] = ballot64(k1[j]);
+        if (lane == 0) tot[j * 4 + wave] = (uint32_t)(__popcll(m0[j]) + __popcll(m1[j]));
+    }
+    __syncthreads();
+    uint32_t base = have, consumed = 0;
+    bool open = true;
+#pragma unroll
+    for (int j = 0; j < kLazySubs; ++j) {
+        const uint32_t t0 = tot[j * 4], t1 = tot[j * 4 + 1], t2 = tot[j * 4 + 2], t3 = tot[j * 4 + 3];
+        if (base < hi) {                                                  // block-uniform
+            const uint32_t off = base + (wave > 0 ? t0 : 0u) + (wave > 1 ? t1 : 0u) + (wave > 2 ? t2 : 0u);
+            const uint32_t b0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m0[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0[j], 0u));
+            const uint32_t b1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m1[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1[j], 0u));
+            const uint32_t p0 = off + b0 + b1, p1 = p0 + (k0[j] ? 1u : 0u);
+            const uint32_t s0 = cur + (uint32_t)(j * kLazySub + 2 * tid);     // cur: still the step's start
+            if (k0[j] && p0 >= lo && p0 < hi) emit(p0, s0);
+            if (k1[j] && p1 >= lo && p1 < hi) emit(p1, s0 + 1u);
+        }
+        base += t0 + t1 + t2 + t3;
+        open = open && base <= hi;
+        if (open) { have = base; consumed = (uint32_t)(j + 1); }
+    }
+    cur += consumed * (uint32_t)kLazySub;
+    return base;
+}
+
 typedef float f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f2 splat(float v) { return f2{v, v}; }

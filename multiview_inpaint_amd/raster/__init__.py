@@ -82,6 +82,19 @@ class RasterState:
                 _ptr(self.radii), _ptr(self.geom), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
                 "materialize_geom_views")
 
+    def materialize_point_list(self):
+        """Writes the whole sorted point list (include/mvi_raster.h: mvi_raster_materialize_point_list). With tile lists
+        expanded on demand (mvi_raster_list_expansion, the default) the forward stores only the prefix of every tile's list that
+        it composited, which is all the backward, the splat and the lift read. `tensor("point_list", ..)` calls this; pass
+        `_derive=False` there to read what the forward itself left. Tests and introspection only."""
+        if self.P == 0 or self.D == 0 or self.binning is None or self.image is None:
+            return
+        dev = self.binning.device
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mvi_raster_materialize_point_list(
+                self.P, self.D, self.W, self.H, _ptr(self.geom), _ptr(self.binning), _ptr(self.image),
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "materialize_point_list")
+
     def resolve_colors(self):
         """Evaluates the SH colours no tile needed (deferred colours, include/mvi_raster.h: mvi_raster_color_mode), so that
         the `rgbd` / `clamped` views are complete. Tests and introspection only; the forward's inputs are kept alive in
@@ -133,6 +146,8 @@ class RasterState:
                 _lib.check(_lib.lib().mvi_raster_materialize_tile_ids(
                     self.P, self.D, self.W, self.H, _ptr(self.binning), _ptr(self.image),
                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "materialize_tile_ids")
+        if _derive and name == "point_list":
+            self.materialize_point_list()
         n = 1
         for s in shape:
             n *= s

@@ -12,6 +12,7 @@ from multiview_inpaint_amd import _lib, raster as R, synthetic as syn  # noqa: E
 
 N, W, H = (int(a) for a in sys.argv[1:4]) if len(sys.argv) > 3 else (1_500_000, 1920, 1080)
 L = _lib.lib()
+L.mvi_raster_list_expansion(0)          # the forward runs the pass-2 scatter only when it writes every tile list itself
 cam = syn.make_camera(W, H, 50.0)
 sc = syn.make_scene(N, cam, 3, seed=0)
 t = {k: torch.tensor(v, device="cuda") for k, v in sc.items() if k != "sh_degree"}
